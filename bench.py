@@ -10,6 +10,12 @@ the timed region.  N > 1 (torch.distributed.run, one rank per GPU, RCCL): the SI
 model does not shard, so every rank trains its own replica (weak scaling, no data-path
 collective); the prediction leg shards the imputations over the ranks with one all-reduce.
 Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`).
+Everything else it can measure -- step accounting, roofline passes, the sustained train(N) rate,
+the prediction leg, the Vecchia / SExp / factorisation tables, the N > 1 split and strong-scaling
+legs and the CPU baselines -- runs only with --full.  --dump-outputs DIR writes what the last timed
+step left in the model (every node's latent output and hyper-parameters) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -60,6 +66,20 @@ def build_model(n, d, seed, device):
     return dgp(X, Y, layers, seed=seed, device=device), X, Y
 
 
+def dump_outputs(model, out_dir):
+    """What the timed path hands its caller: the model's state after the last timed step -- every node's output (the imputed
+    latent of a first-layer node, the data of the output node) and its hyper-parameters -- as float64 .npy files."""
+    os.makedirs(out_dir, exist_ok=True)
+    names = []
+    for l, layer in enumerate(model.all_layer):
+        for k, nd in enumerate(layer):
+            for attr in ('output', 'length', 'scale', 'nugget'):
+                name = 'layer%d_node%d_%s' % (l + 1, k + 1, attr)
+                np.save(os.path.join(out_dir, name + '.npy'), np.array(getattr(nd, attr), dtype=np.float64))
+                names.append(name)
+    return names
+
+
 def cpu_baseline(model, counts, ess_burn):
     """The oracle (numpy/scipy-LAPACK restatement of dgpsi's formulation, kind 'port') timed on this
     host on a bounded sample of the same workload: a few prior draws, ESS log-likelihoods and M-step
@@ -71,13 +91,16 @@ def cpu_baseline(model, counts, ess_burn):
     l1, l2 = model.all_layer[0][0], model.all_layer[1][0]
     n = len(l1.output)
     reps_f, reps_l, reps_g = 3, 3, 3     # after one untimed call of each: a few seconds in all (the baseline must not outlast the GPU legs)
-    # BLAS threads = physical cores.  The OpenBLAS inside numpy / scipy wheels is built with a fixed maximum (64 in
-    # the wheels of this image): asking for more is clamped by the library, and the count it reports afterwards goes into the line.
+    # BLAS threads = physical cores, but never more than the pool the OpenBLAS inside the numpy / scipy wheels
+    # started with: it sizes that pool when it loads (OMP_NUM_THREADS / OPENBLAS_NUM_THREADS, else the CPU count, at most its
+    # compile-time maximum of 64), and a later request for more threads than that segfaults inside the first factorisation.
+    # The count it reports afterwards goes into the line.
     phys = psutil.cpu_count(logical=False) or 1
     limiter, blas_note = None, None
     try:
-        from threadpoolctl import threadpool_limits
-        limiter = threadpool_limits(limits=phys, user_api='blas')
+        from threadpoolctl import threadpool_limits, threadpool_info
+        pool = min([i.get('num_threads') or phys for i in threadpool_info() if i.get('user_api') == 'blas'] or [phys])
+        limiter = threadpool_limits(limits=min(phys, pool), user_api='blas')
     except Exception as exc:   # noqa: BLE001
         blas_note = 'threadpoolctl: %s' % exc
 
@@ -113,8 +136,8 @@ def cpu_baseline(model, counts, ess_burn):
         pass
     blas_threads = max([t['threads'] for t in (threads or []) if t.get('api') == 'blas'] or [phys])
     if blas_threads < phys and blas_note is None:
-        blas_note = ('asked the BLAS for %d threads (= physical cores), it runs %d: the OpenBLAS built into the numpy / scipy wheels has a '
-                     'compile-time maximum' % (phys, blas_threads))
+        blas_note = ('%d physical cores, the BLAS runs %d threads: the pool the OpenBLAS built into the numpy / scipy wheels started with '
+                     '(OMP_NUM_THREADS / OPENBLAS_NUM_THREADS, else its compile-time maximum); asking it for more crashes it' % (phys, blas_threads))
     if limiter is not None:
         limiter.restore_original_limits()
     return dict(value=1.0 / per_iter, unit='SI it/s', cores=int(blas_threads), physical_cores=phys, kind='port',
@@ -197,7 +220,7 @@ def cpu_baseline_predict(model, d, imputations, points_per_worker=1):
     import pickle
     import shutil
     import tempfile
-    shm = '/dev/shm' if os.path.isdir('/dev/shm') and os.access('/dev/shm', os.W_OK) else None
+    shm = '/dev/shm' if os.path.isdir('/dev/shm') and os.access('/dev/shm', os.W_OK) and shutil.disk_usage('/dev/shm').free > 1e9 else None
     path = tempfile.mkdtemp(prefix='dgp_amd_cpu_baseline_', dir=shm)   # (~0.2 GB: the six nodes' R^-1; removed below)
     try:
         with open(os.path.join(path, 'meta.pkl'), 'wb') as f:
@@ -430,6 +453,11 @@ def main():
     ap.add_argument('--prof-kernel', default='syrk',
                     help="kernel class timed with HIP events for the roofline ('syrk' = the fused block-step kernel "
                          "of the factorisation, the dominant kernel; 'lauum', 'trtri', 'kmatrix', ...)")
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beside the headline: step accounting, roofline passes, sustained train(N), prediction leg, '
+                         'factorisation / Vecchia / SExp tables, N > 1 split and strong-scaling legs, CPU baselines')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the model state the last timed step left (every node\'s output and hyper-parameters) as DIR/<name>.npy')
     args = ap.parse_args()
 
     world_env = int(os.environ.get('WORLD_SIZE', '1'))
@@ -488,7 +516,8 @@ def main():
     def counted(self, host):
         calls[layer_of[id(self)]] += 1
         return orig_finish(self, host)
-    kernel_class.kernel._llik_finish = counted
+    if args.full:
+        kernel_class.kernel._llik_finish = counted
 
     # ... and the lock-step optimiser rounds of every M-step: the reference's L-BFGS-B runs take between 6 and 45 rounds per
     # iteration along a training path (the slowest node's evaluations; maxfun = 45), so the work inside K timed steps varies
@@ -546,7 +575,8 @@ def main():
             acct['tail'] += time.perf_counter() - st['last']
         rounds['n'] += r
         return r
-    mstep_mod.minimize_lockstep = counted_lock
+    if args.full:
+        mstep_mod.minimize_lockstep = counted_lock
 
     # one step = one iteration of dgp.train's own loop (dgp_amd.dgp._si_iteration <- dgp.py:1377-1398: imputer.sample, then the M-step; iteration numbers >= 2:
     # the first iteration of a train() call initialises the scales).  The stamps at the I / M boundary ride on the two calls it makes.
@@ -559,7 +589,8 @@ def main():
             acct['t1'] = time.perf_counter()
             eng.record(acct['events'][acct['k']][1])
         return r
-    model.imp.sample = stamped_sample
+    if args.full:
+        model.imp.sample = stamped_sample
 
     def step():
         it_no['i'] += 1
@@ -582,12 +613,13 @@ def main():
     calls['l1'] = calls['l2'] = 0
     rounds['n'] = 0
     st0 = dict(model.imp.stats)
-    acct['events'] = [(eng.event(), eng.event(), eng.event()) for _ in range(args.steps)]
+    if args.full:
+        acct['events'] = [(eng.event(), eng.event(), eng.event()) for _ in range(args.steps)]
     dd.barrier()
     torch.cuda.synchronize()
     ev0, ev1 = eng.event(), eng.event()
     eng.record(ev0)
-    acct['on'] = True
+    acct['on'] = args.full   # (the step accounts for itself only in a --full run)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -601,14 +633,21 @@ def main():
     value = steps_total / wall
     st1 = model.imp.stats
     upd = max(1, st1['updates'] - st0['updates'])
-    counts = dict(proposals_per_iter=(st1['proposals'] - st0['proposals']) / args.steps,
-                  batches_per_update=(st1['batches'] - st0['batches']) / upd,
-                  llik_l1_per_iter=calls['l1'] / args.steps, llik_l2_per_iter=calls['l2'] / args.steps,
-                  mstep_rounds_per_iter=rounds['n'] / args.steps)
+    counts = None
+    if args.full:
+        counts = dict(proposals_per_iter=(st1['proposals'] - st0['proposals']) / args.steps,
+                      batches_per_update=(st1['batches'] - st0['batches']) / upd,
+                      llik_l1_per_iter=calls['l1'] / args.steps, llik_l2_per_iter=calls['l2'] / args.steps,
+                      mstep_rounds_per_iter=rounds['n'] / args.steps)
+
+    # ---- what the last timed step computed, before anything below steps the model again ----
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(model, args.dump_outputs)
 
     # ---- step_split: where the timed region's wall time went (per step, ms) ----
     step_split = None
-    if rank == 0:
+    if args.full and rank == 0:
         K = float(args.steps)
         gi = sum(eng.elapsed_ms(a, b) for a, b, _ in acct['events']) / K
         gm = sum(eng.elapsed_ms(b, c) for _, b, c in acct['events']) / K
@@ -634,7 +673,7 @@ def main():
 
     # ---- roofline of the dominant kernel: HIP events around each of its launches, same steps ----
     roof = None
-    if rank == 0 and args.prof_kernel != 'none':
+    if args.full and rank == 0 and args.prof_kernel != 'none':
         engines = [eng]
         for e in engines:
             e.prof_enable(args.prof_kernel)
@@ -672,7 +711,7 @@ def main():
                              'load the chip holds ~1.85 of its 2.4 GHz, i.e. ~60 of the 78.6 TFLOP/s datasheet peak are attainable')
     # K assembly against the HBM roofline on the same steps (its own pass: one kernel class is timed at a time)
     roof_k = None
-    if rank == 0 and args.prof_kernel != 'none':
+    if args.full and rank == 0 and args.prof_kernel != 'none':
         eng.prof_enable('kmatrix')
         step()
         k_n, k_ms, k_w = eng.prof_collect()
@@ -686,7 +725,7 @@ def main():
     # ---- the sustained figure: the reference's own entry point, train(N), over 100 iterations (the optimiser rounds per iteration range
     #      6-45 along a training path, so a 20-step window reads +-10 %; SURVEY 8(d) defines the metric on train(N)) ----
     sustained = None
-    if args.sustained_steps > 0:
+    if args.full and args.sustained_steps > 0:
         r0 = rounds['n']
         dd.barrier()
         torch.cuda.synchronize()
@@ -704,7 +743,7 @@ def main():
     # ---- K assembly alone against the HBM roofline, cache-defeating: full symmetric n = 5000, D = 10 (cfg3's node shape),
     #      200 MB per matrix, three output buffers in turn (600 MB > the 256-MB Infinity Cache), HIP events on the engine's stream
     roof_ks = None
-    if rank == 0 and args.prof_kernel != 'none':
+    if args.full and rank == 0 and args.prof_kernel != 'none':
         roof_ks = {}
         nk, Dk = 5000, 10
         Xk = eng.tensor(np.random.default_rng(3).uniform(size=(nk, Dk)))
@@ -750,7 +789,7 @@ def main():
         del outs, outs_al
 
     ptab = vleg = sxleg = None
-    if rank == 0 and args.prof_kernel != 'none':
+    if args.full and rank == 0 and args.prof_kernel != 'none':
         try:
             ptab = potrf_table(eng, torch, args.n)
         except Exception as exc:   # noqa: BLE001  (informational: must not cost the run its result line)
@@ -766,7 +805,7 @@ def main():
 
     # ---- prediction leg: emulator with the imputations sharded over the ranks --------------------
     pred = None
-    if not args.no_predict:
+    if args.full and not args.no_predict:
         from dgp_amd import emulator
         model.N = max(model.N, 1)
         for layer in model.all_layer:
@@ -828,7 +867,7 @@ def main():
     #      runs the same I-step from the same seed, node i is fitted by rank i mod N, one all-gather per M-step) -- the
     #      informational strong-scaling companion of the replicas above
     split = None
-    if world > 1 and not args.no_split_leg:
+    if args.full and world > 1 and not args.no_split_leg:
         # (informational: a failure here must not cost the run its result line)
         try:
             dd.split_training(nodes=True)
@@ -857,7 +896,7 @@ def main():
     #      cfg3-shaped prediction with the imputations sharded over the ranks (one all-reduce of the moments), and
     #      cfg4-shaped Vecchia training with the likelihood rows split (one all-reduce per speculative batch / optimiser round)
     strong = None
-    if world > 1 and not args.no_strong_legs:
+    if args.full and world > 1 and not args.no_strong_legs:
         strong = {}
         try:
             strong['cfg3_predict_imputations_sharded'] = strong_leg_cfg3(dd, torch, local, dev, world)
@@ -879,7 +918,7 @@ def main():
     gpu_leg_seconds = time.perf_counter() - t_gpu0
 
     cpu = cpu_pred = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(model, counts, args.ess_burn)
         if pred is not None:
             try:
@@ -901,7 +940,8 @@ def main():
             'metric': 'SI iterations/sec (train) + predict pts/sec, 2-layer DGP n=2000 d=5',
             'value': value, 'unit': 'SI it/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
             'ms_per_step': 1e3 * wall / args.steps, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-            'dtype': 'f64', 'data': 'synthetic',
+            'dtype': 'f64', 'data': 'synthetic', 'full': args.full,
+            'outputs_dumped': None if dumped is None else dict(dir=args.dump_outputs, arrays=dumped),
             'scaling_metric': None if world == 1 else dict(
                 columns=['predict.point_imputations_per_s', 'strong_scaling.cfg3_predict_imputations_sharded.point_imputations_per_s',
                          'strong_scaling.cfg4_train_rows_split.si_it_per_s', 'mstep_nodes_split.si_it_per_s'],

@@ -30,7 +30,7 @@ def _finite(x):
 
 def test_bench_two_ranks_on_one_gpu():
     d = _run(['--gpus', '2', '--backend', 'gloo', '--steps', '2', '--warmup', '1', '--predict-points', '256', '--predict-seconds', '0.1',
-              '--sustained-steps', '2', '--prof-kernel', 'none'])
+              '--sustained-steps', '2', '--prof-kernel', 'none', '--full'])
     assert d['n_gpus'] == 2 and d['steps'] == 2 and _finite(d['value']) and d['value'] > 0
     assert d['distributed']['world_size'] == 2 and d['distributed']['backend'] == 'gloo' and len(d['distributed']['ranks']) == 2
     assert d['distributed']['ranks_share_a_device'] is True
@@ -50,7 +50,7 @@ def test_bench_two_ranks_on_one_gpu():
 
 def test_bench_one_rank_through_rccl():
     d = _run(['--gpus', '1', '--backend', 'nccl', '--steps', '2', '--warmup', '1', '--predict-points', '256', '--predict-seconds', '0.1',
-              '--sustained-steps', '2', '--prof-kernel', 'none', '--no-cpu-baseline'], env_extra={'DGPAMD_DIST_FORCE': '1'})
+              '--sustained-steps', '2', '--prof-kernel', 'none', '--no-cpu-baseline', '--full'], env_extra={'DGPAMD_DIST_FORCE': '1'})
     assert d['n_gpus'] == 1 and _finite(d['value']) and d['scaling_metric'] is None
     assert d['distributed']['world_size'] == 1 and d['distributed']['backend'] == 'nccl'
     assert d['predict']['finite']

@@ -7,10 +7,10 @@ export TMPDIR=/tmp
 O=gpurun_out
 mkdir -p $O
 timeout 3000 python -m pytest tests -m gpu -x -q --durations=12 2>&1 | tail -24 > $O/r6_pytest_gpu.txt; tail -3 $O/r6_pytest_gpu.txt
-timeout 900 python bench.py > $O/r6_bench_default.json 2> $O/r6_bench_default.err; tail -c 300 $O/r6_bench_default.err
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/r6_bench_steps20.json 2> $O/r6_bench_steps20.err
+timeout 900 python bench.py --full > $O/r6_bench_default.json 2> $O/r6_bench_default.err; tail -c 300 $O/r6_bench_default.err
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/r6_bench_steps20.json 2> $O/r6_bench_steps20.err
 python3 -c "import json;d=json.load(open('$O/r6_bench_default.json'));print('default: it/s', round(d['value'],2), 'sustained', round(d['sustained_it_per_s'],2), 'pts/s', round(d['predict']['pts_per_s'],1), 'frac', round(d['roofline']['frac'],4), 'cpu', d['cpu_baseline']['value'], d['cpu_baseline_predict'].get('value'))"
-TR="bench.py --steps 20 --warmup 5 --no-cpu-baseline --prof-kernel none --sustained-steps 0 --no-predict"
+TR="bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --prof-kernel none --sustained-steps 0 --no-predict"
 rm -rf /tmp/pf_trace; timeout 900 rocprofv3 --kernel-trace --output-format csv -d /tmp/pf_trace -- python3 $TR > $O/r6_trace_bench.json 2> $O/r6_trace.err
 { echo "# rocprofv3 --kernel-trace -- python3 $TR ; tools/analyze_step.py (the iterations behind the first 25 % of the trace), tools/analyze_gaps.py, tools/analyze_round.py"
   echo "# the same run's own line (host clock, no profiler hooks in the timed region's arithmetic -- but the profiler's launch interception is in it):"
@@ -21,7 +21,7 @@ rm -rf /tmp/pf_trace; timeout 900 rocprofv3 --kernel-trace --output-format csv -
   python3 tools/analyze_round.py /tmp/pf_trace
 } > $O/r6_idle_gaps.txt 2>&1
 head -30 $O/r6_idle_gaps.txt
-ST="bench.py --steps 20 --warmup 5 --no-cpu-baseline --prof-kernel none --sustained-steps 0"
+ST="bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --prof-kernel none --sustained-steps 0"
 rm -rf /tmp/pf_stats; timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pf_stats -- python3 $ST > $O/r6_bench_stats.log 2>&1
 python3 tools/summarize_rocprof.py /tmp/pf_stats python3 $ST > $O/r6_bench_kernel_stats.txt 2>&1
 head -8 $O/r6_bench_kernel_stats.txt

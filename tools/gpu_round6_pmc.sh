@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 O=gpurun_out/${1:-r6pmc}
 mkdir -p "$O"
-BENCH="bench.py --steps 10 --warmup 3 --no-cpu-baseline --prof-kernel none --sustained-steps 0 --predict-points 4096 --predict-seconds 0.3"
+BENCH="bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --prof-kernel none --sustained-steps 0 --predict-points 4096 --predict-seconds 0.3"
 SETS=("SQ_INSTS_VALU SQ_WAVES" "SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES" "SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" "SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_ACTIVE_INST_VALU" "FETCH_SIZE" "WRITE_SIZE")
 # (1) calibration of FETCH_SIZE per load width
 rm -rf /tmp/pm_cal; rocprofv3 --kernel-trace --pmc FETCH_SIZE -d /tmp/pm_cal --output-format csv -- build_ubench/fetch_calib > "$O/calib.log" 2>&1
