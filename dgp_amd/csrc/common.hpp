@@ -82,6 +82,21 @@ struct dgpamd_ctx {
         return DGPAMD_BAD_ARG;                                                \
     } while (0)
 
+#define LDS_CU_BYTES (160 * 1024)   // LDS of one gfx950 CU: the most dynamic LDS one workgroup can be given
+#define LDS_DEFAULT_BYTES (48 * 1024)   // dynamic LDS a launch gets without opting in
+
+// Every launch with dynamic LDS that can pass LDS_DEFAULT_BYTES goes through here first: above that the kernel opts in to
+// `shm` bytes; above LDS_CU_BYTES nothing can run it, and the caller gets DGPAMD_BAD_ARG before anything is launched.
+static inline int set_lds(dgpamd_ctx *ctx, const void *fn, size_t shm) {
+    if (shm > LDS_CU_BYTES) {
+        snprintf(ctx->err, sizeof(ctx->err), "a launch would need %zu bytes of LDS per workgroup, more than the %d of a CU "
+                 "(input width or conditioning set too large)", shm, LDS_CU_BYTES);
+        return DGPAMD_BAD_ARG;
+    }
+    if (shm > LDS_DEFAULT_BYTES) HIP_TRY(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    return DGPAMD_OK;
+}
+
 // Run `body` (a sequence of launches on ctx->stream with a static shape) through a cached hipGraph.
 // Falls back to direct launches on the null stream (not capturable), while a kernel class is being
 // timed, or if capture fails.

@@ -182,7 +182,9 @@ extern "C" int dgpamd_gp_predict(dgpamd_ctx *ctx, int kind, int64_t n, int64_t M
     for (int d = 0; d < D; ++d) c.inv_len[d] = 1.0 / length_h[nlen == 1 ? 0 : d];
     GpQuadArgs q;
     q.Rinv = Rinv; q.ldr = ldr; q.n = n; q.Mc = Mc; q.R = R; q.partial = partial;
-    const size_t shm = (size_t)2 * D * 64 * sizeof(double);
+    const size_t shm = (size_t)2 * D * 64 * sizeof(double);   // (64 KB at D = DGPAMD_MAXD)
+    int rc = set_lds(ctx, kind == DGPAMD_SEXP ? (const void *)cross_corr_kernel<DGPAMD_SEXP> : (const void *)cross_corr_kernel<DGPAMD_MATERN25>, shm);
+    if (rc) return rc;
     for (int64_t t0 = 0; t0 < M; t0 += Mc) {
         c.t0 = t0;
         int64_t mc = M - t0 < Mc ? M - t0 : Mc;
@@ -286,27 +288,28 @@ __global__ __launch_bounds__(256) void linkgp_mean_kernel(LinkArgs a) {
 // LOO: test point t conditions on every training point but d = drop[t].  With u = Rinv[:, d], rho = u_d the inverse of
 // the reduced correlation matrix (embedded, zero row / column d) is Rinv - u u^T / rho, so the pair weight becomes
 //   wt [ (ry_i - c u_i)(ry_j - c u_j) - scale (Rinv_ij - u_i u_j / rho) ],   c = ry_d / rho.
-template <int KIND, bool LOO>
+// TC: test points per workgroup (TCH; half of it where the Matern leave-one-out form would not fit in a CU's LDS)
+template <int KIND, bool LOO, int TC = TCH>
 __global__ __launch_bounds__(256) void linkgp_J_kernel(LinkArgs a) {
     extern __shared__ double lds[];
     const int Dw = a.Dw, Dz = a.Dz, DT = Dw + Dz;
     double *WiT = lds;                    // [DT][64]
     double *WjT = WiT + DT * 64;          // [DT][64]
-    double *tm = WjT + DT * 64;           // [TCH][Dw]
-    double *tv = tm + TCH * Dw;           // [TCH][Dw]
-    double *tz = tv + TCH * Dw;           // [TCH][Dz]
-    double *red = tz + TCH * Dz;          // [TCH][4]
-    double *Cs = red + TCH * 4;           // [64][65]  (matern only)
-    double *ui = Cs + (KIND == DGPAMD_MATERN25 ? 64 * 65 : 0);   // LOO only: [TCH][64] u rows of the tile
-    double *uj = ui + TCH * 64;           // [TCH][64] u columns of the tile
-    double *ryi = uj + TCH * 64, *ryj = ryi + 64;
-    double *ct = ryj + 64, *gt = ct + TCH;   // [TCH] c and wt scale / rho
+    double *tm = WjT + DT * 64;           // [TC][Dw]
+    double *tv = tm + TC * Dw;            // [TC][Dw]
+    double *tz = tv + TC * Dw;            // [TC][Dz]
+    double *red = tz + TC * Dz;           // [TC][4]
+    double *Cs = red + TC * 4;            // [64][65]  (matern only)
+    double *ui = Cs + (KIND == DGPAMD_MATERN25 ? 64 * 65 : 0);   // LOO only: [TC][64] u rows of the tile
+    double *uj = ui + TC * 64;            // [TC][64] u columns of the tile
+    double *ryi = uj + TC * 64, *ryj = ryi + 64;
+    double *ct = ryj + 64, *gt = ct + TC;   // [TC] c and wt scale / rho
     int bi, bj;
     tri_decode(blockIdx.x, bi, bj);
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4, wave = tid >> 6, lane = tid & 63;
     const int64_t i0 = (int64_t)bi * 64, j0 = (int64_t)bj * 64, n = a.n;
-    const int64_t tbase = a.t0 + (int64_t)blockIdx.y * TCH;
-    int nt = TCH;
+    const int64_t tbase = a.t0 + (int64_t)blockIdx.y * TC;
+    int nt = TC;
     if (tbase + nt > a.M) nt = (int)(a.M - tbase);
     if (tbase + nt > a.t0 + a.Mc) nt = (int)(a.t0 + a.Mc - tbase);
 
@@ -1322,14 +1325,37 @@ static int linkgp_run(dgpamd_ctx *ctx, int kind, int64_t n, int64_t M, int Dw, i
     a.gfac = sx2 ? a.recs + Mc * a.npad * (int64_t)((Dw + 2 + 3) & ~3)   // (SExp second form: [Mc][npad][KPA] records, then the ss values)
                  : a.recs + Mc * (int64_t)Dw * a.npad * REC;
     const int DT = Dw + Dz;
-    size_t shm = ((size_t)2 * DT * 64 + (size_t)TCH * (2 * Dw + Dz) + TCH * 4) * sizeof(double);
-    if (kind == DGPAMD_MATERN25) shm += 64 * 65 * sizeof(double);
-    if (drop) {
-        shm += ((size_t)2 * TCH * 64 + 128 + 2 * TCH) * sizeof(double);
+    // LDS of the direct / leave-one-out J kernel with tc test points per workgroup
+    auto j_lds = [&](int tc) {
+        size_t s = ((size_t)2 * DT * 64 + (size_t)tc * (2 * Dw + Dz) + tc * 4) * sizeof(double);
+        if (kind == DGPAMD_MATERN25) s += 64 * 65 * sizeof(double);
+        if (drop) s += ((size_t)2 * tc * 64 + 128 + 2 * tc) * sizeof(double);
+        return s;
+    };
+    size_t shm = j_lds(TCH);
+    // Matern leave-one-out from Dw + Dz = 63 on: past a CU's LDS at TCH test points per workgroup; half of them fit
+    const int tcj = (drop && kind == DGPAMD_MATERN25 && shm > LDS_CU_BYTES) ? TCH / 2 : TCH;
+    if (tcj != TCH) shm = j_lds(tcj);
+    // SExp: the second form up to Dw = 14; the first form (MFMA) above, while it fits in a CU's LDS (to Dw = 39..48, by Dz);
+    // past that the direct kernel (99 KB at Dw = 64)
+    const bool sexp2 = sx2 && !getenv("DGPAMD_SEXP_FORM1");
+    const int KP = (Dw + 3) & ~3, LDU = KP + 2;
+    const size_t shm_s = ((size_t)2 * DT * 64 + (size_t)KP * LDK + (size_t)TCH * (2 * Dw + Dz) + TCH * 4 + 2 * 64 * LDU + 4 * 64 + Dz) * sizeof(double);
+    const bool sexp1 = kind == DGPAMD_SEXP && !direct && !sexp2 && shm_s <= LDS_CU_BYTES;
+    const bool jdirect = direct || (kind == DGPAMD_SEXP && !sexp2 && !sexp1);
+    const void *jfn = nullptr;
+    if (jdirect) {
         if (kind == DGPAMD_SEXP)
-            HIP_TRY(ctx, hipFuncSetAttribute((const void *)linkgp_J_kernel<DGPAMD_SEXP, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+            jfn = drop ? (const void *)linkgp_J_kernel<DGPAMD_SEXP, true> : (const void *)linkgp_J_kernel<DGPAMD_SEXP, false>;
+        else if (!drop)
+            jfn = (const void *)linkgp_J_kernel<DGPAMD_MATERN25, false>;
         else
-            HIP_TRY(ctx, hipFuncSetAttribute((const void *)linkgp_J_kernel<DGPAMD_MATERN25, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+            jfn = tcj == TCH ? (const void *)linkgp_J_kernel<DGPAMD_MATERN25, true> : (const void *)linkgp_J_kernel<DGPAMD_MATERN25, true, TCH / 2>;
+        int rc = set_lds(ctx, jfn, shm);
+        if (rc) return rc;
+    } else if (sexp1) {
+        int rc = set_lds(ctx, (const void *)linkgp_Jsexp_kernel, shm_s);
+        if (rc) return rc;
     }
     for (int64_t t0 = 0; t0 < M; t0 += Mc) {
         a.t0 = t0;
@@ -1337,11 +1363,12 @@ static int linkgp_run(dgpamd_ctx *ctx, int kind, int64_t n, int64_t M, int Dw, i
         const unsigned tb = (unsigned)((mc + TCH - 1) / TCH);
         if (kind == DGPAMD_SEXP) {
             hipLaunchKernelGGL(linkgp_mean_kernel<DGPAMD_SEXP>, dim3((unsigned)mc), dim3(256), 0, ctx->stream, a);
-            if (drop) {
-                hipLaunchKernelGGL((linkgp_J_kernel<DGPAMD_SEXP, true>), dim3(ntiles, tb), dim3(256), shm, ctx->stream, a);
-            } else if (direct) {
-                hipLaunchKernelGGL((linkgp_J_kernel<DGPAMD_SEXP, false>), dim3(ntiles, tb), dim3(256), shm, ctx->stream, a);
-            } else if (Dw + 2 <= 4 * SX_KS && !getenv("DGPAMD_SEXP_FORM1")) {
+            if (jdirect) {
+                if (drop)
+                    hipLaunchKernelGGL((linkgp_J_kernel<DGPAMD_SEXP, true>), dim3(ntiles, tb), dim3(256), shm, ctx->stream, a);
+                else
+                    hipLaunchKernelGGL((linkgp_J_kernel<DGPAMD_SEXP, false>), dim3(ntiles, tb), dim3(256), shm, ctx->stream, a);
+            } else if (sexp2) {
                 const int KPA = (Dw + 2 + 3) & ~3;
                 const size_t shm2 = ((size_t)2 * Dw * 64 + a.tch * 4 + EXPN_TAB) * sizeof(double);
                 const bool poly = getenv("DGPAMD_SEXP_POLY") != nullptr;   // (comparison run: the table-free exponential)
@@ -1360,17 +1387,17 @@ static int linkgp_run(dgpamd_ctx *ctx, int kind, int64_t n, int64_t M, int Dw, i
 #undef JSEXP2
                 PROF_END(ctx, PROF_LINKGP_J);
             } else {
-                const int KP = (Dw + 3) & ~3, LDU = KP + 2;
-                const size_t shm_s = ((size_t)2 * DT * 64 + (size_t)KP * LDK + (size_t)TCH * (2 * Dw + Dz) + TCH * 4 + 2 * 64 * LDU + 4 * 64 + Dz) * sizeof(double);
-                if (shm_s > 48 * 1024)
-                    HIP_TRY(ctx, hipFuncSetAttribute((const void *)linkgp_Jsexp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_s));
                 hipLaunchKernelGGL(linkgp_Jsexp_kernel, dim3(ntiles, tb), dim3(256), shm_s, ctx->stream, a);
             }
             hipLaunchKernelGGL(linkgp_finalize_kernel<DGPAMD_SEXP>, dim3((unsigned)((mc + 3) / 4)), dim3(256), 0, ctx->stream, a, ntiles);
         } else {
             hipLaunchKernelGGL(linkgp_mean_kernel<DGPAMD_MATERN25>, dim3((unsigned)mc), dim3(256), 0, ctx->stream, a);
             if (drop) {
-                hipLaunchKernelGGL((linkgp_J_kernel<DGPAMD_MATERN25, true>), dim3(ntiles, tb), dim3(256), shm, ctx->stream, a);
+                if (tcj == TCH)
+                    hipLaunchKernelGGL((linkgp_J_kernel<DGPAMD_MATERN25, true>), dim3(ntiles, tb), dim3(256), shm, ctx->stream, a);
+                else
+                    hipLaunchKernelGGL((linkgp_J_kernel<DGPAMD_MATERN25, true, TCH / 2>), dim3(ntiles, (unsigned)((mc + tcj - 1) / tcj)), dim3(256),
+                                       shm, ctx->stream, a);
             } else if (direct) {
                 hipLaunchKernelGGL((linkgp_J_kernel<DGPAMD_MATERN25, false>), dim3(ntiles, tb), dim3(256), shm, ctx->stream, a);
             } else {
@@ -1381,8 +1408,8 @@ static int linkgp_run(dgpamd_ctx *ctx, int kind, int64_t n, int64_t M, int Dw, i
                 const bool plog = ctx->tlog != nullptr && getenv("DGPAMD_JSEP_LOG") != nullptr;
                 auto jsep = plog ? linkgp_Jsep_kernel<2, true> : (pipe == 0 ? linkgp_Jsep_kernel<0, false> : linkgp_Jsep_kernel<2, false>);
                 a.dbg = (plog && ctx->tlog_words >= 64 + (long long)ntiles * ((mc + a.tch - 1) / a.tch) * JSEP_LOG_WORDS) ? ctx->tlog : nullptr;
-                if (shm_sep > 48 * 1024)
-                    HIP_TRY(ctx, hipFuncSetAttribute((const void *)jsep, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_sep));
+                int rc = set_lds(ctx, (const void *)jsep, shm_sep);
+                if (rc) return rc;
                 hipLaunchKernelGGL(matern_records_kernel, dim3((unsigned)((a.npad + 127) / 128), Dw, (unsigned)mc), dim3(256), 0, ctx->stream, a);
                 if (Dz)
                     hipLaunchKernelGGL(global_factor_kernel, dim3((unsigned)((a.npad + 255) / 256), (unsigned)mc), dim3(256), 0, ctx->stream, a);

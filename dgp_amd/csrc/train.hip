@@ -435,7 +435,9 @@ extern "C" int dgpamd_grad_reduce(dgpamd_ctx *ctx, int kind, int64_t n, const do
     a.partial = (double *)work;
     a.alpha_col = nullptr;
     const int nb = (int)((n + 63) / 64), ntiles = nb * (nb + 1) / 2;
-    size_t shm = ((size_t)2 * D * 64 + 4 * 2 * a.P + KM_EXP_TAB * EXPN_TAB) * sizeof(double);
+    size_t shm = ((size_t)2 * D * 64 + 4 * 2 * a.P + KM_EXP_TAB * EXPN_TAB) * sizeof(double);   // (beyond the default from D = 44)
+    rc = set_lds(ctx, kind == DGPAMD_SEXP ? (const void *)grad_reduce_kernel<DGPAMD_SEXP> : (const void *)grad_reduce_kernel<DGPAMD_MATERN25>, shm);
+    if (rc) return rc;
     if (kind == DGPAMD_SEXP)
         hipLaunchKernelGGL(grad_reduce_kernel<DGPAMD_SEXP>, dim3(ntiles), dim3(256), shm, ctx->stream, a);
     else
@@ -588,6 +590,8 @@ extern "C" int dgpamd_llik_batch_launch(dgpamd_ctx *ctx, int64_t n, int batch, c
                            (const int32_t *)info, (const double *)A, Np, stride_a, n, dev_out, stride_out, batch);
     {
         const size_t shm = ((size_t)2 * Dmax * 64 + 4 * 2 * Pmax + KM_EXP_TAB * EXPN_TAB) * sizeof(double);
+        rc = set_lds(ctx, by_value ? (const void *)grad_reduce_multi_val_kernel : (const void *)grad_reduce_multi_kernel, shm);
+        if (rc) return rc;
         if (by_value) {
             GradMulti3 v;
             for (int c = 0; c < 3; ++c) v.g[c] = ga[c < batch ? c : 0];

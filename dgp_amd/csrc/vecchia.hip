@@ -29,12 +29,6 @@ static int fill_vparams(dgpamd_ctx *ctx, VParams &p, int kind, int D, const doub
     return DGPAMD_OK;
 }
 
-static int set_lds(dgpamd_ctx *ctx, const void *fn, size_t shm) {
-    if (shm > 160 * 1024) BAD_ARG(ctx, "conditioning set too large for LDS (160 KiB)");
-    if (shm > 48 * 1024) HIP_TRY(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-    return DGPAMD_OK;
-}
-
 // correlation of two SCALED points held in LDS
 template <int KIND>
 __device__ __forceinline__ double corr_pts(const double *xa, const double *xb, int D) {
@@ -830,8 +824,8 @@ static int launch_nn(dgpamd_ctx *ctx, int64_t nq, int64_t nx, int D, const doubl
     double *scratch = nullptr;
     HIP_TRY(ctx, hipMallocAsync((void **)&scratch, (size_t)grid * nx * sizeof(double), ctx->stream));
     size_t shm = (D + 8 + NN_CMAX) * sizeof(double) + (NN_CMAX + 4 + (size_t)m_out) * sizeof(int64_t) + (NN_NB + 256 + 4) * sizeof(int);
-    if (shm > 48 * 1024)
-        HIP_TRY(ctx, hipFuncSetAttribute((const void *)nn_select_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    int rc = set_lds(ctx, (const void *)nn_select_big_kernel, shm);
+    if (rc) return rc;
     hipLaunchKernelGGL(nn_select_big_kernel, dim3(grid), dim3(256), shm, ctx->stream, nq, nx, D, q, x, m_out, ordered, out, scratch);
     HIP_TRY(ctx, hipFreeAsync(scratch, ctx->stream));
     return DGPAMD_OK;
