@@ -91,6 +91,10 @@ SIGNATURES = {
     'dgpamd_potrf_inv': (_i, [_p, _l, _p, _p, _p, _l, _i, _p, _p, _p]),
     'dgpamd_gp_workspace': (_z, [_l, _l]),
     'dgpamd_gp_predict': (_i, [_p, _i, _l, _l, _i, _p, _p, _p, _i, _p, _l, _p, _i, _d, _d, _p, _p, _p]),
+    'dgpamd_joint_workspace': (_z, [_l, _l, _i, _i]),
+    'dgpamd_joint_cov': (_i, [_p, _i, _l, _l, _i, _i, _i, _p, _l, _p, _i, _p, _l, _p, _l, _l, _p, _l, _p, _i, _d, _d, _p, _l,
+                              _p, _p]),
+    'dgpamd_mvn_paths': (_i, [_p, _l, _i, _i, _i, _p, _l, _p, _l, _p, _l, _p, _l]),
     'dgpamd_linkgp_workspace': (_z, [_l, _l, _i]),
     'dgpamd_linkgp_predict': (_i, [_p, _i, _l, _l, _i, _i, _p, _p, _p, _p, _p, _p, _i, _p, _l, _p, _d, _d, _p, _p, _p]),
     'dgpamd_linkgp_loo': (_i, [_p, _i, _l, _l, _i, _i, _p, _p, _p, _p, _p, _p, _i, _p, _l, _p, _p, _d, _d, _p, _p, _p]),

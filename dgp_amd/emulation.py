@@ -462,6 +462,104 @@ class emulator:
                 out.append(list(draws.transpose(2, 1, 0)))
         return out if full_layer else out[0]
 
+    def sample_paths(self, x, sample_size=50, full_layer=False):
+        """Joint posterior draws of the emulated function at the rows of x (dense emulators).  Returns the container of
+        predict(x, method='sampling'): a list over the final layer's nodes of (M, N*sample_size) arrays, or with full_layer
+        a list over layers of such lists -- but column s*sample_size + j is ONE draw over all M rows: path j of
+        imputation s.  Each path walks the layers: a first-layer GP node is drawn jointly from its posterior at x; a
+        deeper one is conditioned on imputation s's latents and drawn jointly at that path's outputs of the layer below
+        (its input_dim columns, plus x[:, connect]); likelihood nodes sample from the path's latents (nd.sampling, or
+        cat.sampling for a Categorical node).  Normals come from the emulator's sampling generator, layer by layer and
+        node by node, one standard_normal((N, sample_size, M)) block per GP node.  At most 8192 rows of x; an imputation
+        whose training correlation matrix is not positive definite raises numpy.linalg.LinAlgError."""
+        from . import paths
+        if self.vecch:
+            raise NotImplementedError('sample_paths needs a dense emulator: joint draws of a Vecchia emulator need a sparse '
+                                      'algorithm of their own (use remove_vecchia())')
+        if self.shard or getattr(self, 'shard_points', False):
+            raise NotImplementedError("sample_paths with the imputations sharded over ranks would return partial draws; use "
+                                      "emulator(..., shard=False)")
+        paths.check_points(x)
+        e = self.engine
+        M, S, J = len(x), self.N, int(sample_size)
+        P = S * J
+        xd = e.tensor(x)
+        rng = self._sample_rng
+        cat = self._cat()
+        out, prev, prev_np = [], None, None
+        for l, layer in enumerate(self.all_layer):
+            if l == self.n_layer - 1 and cat is not None:   # class probabilities at the paths' latents (as _draw_samples)
+                out.append(np.stack([cat.sampling(prev_np[j][:, cat.input_dim]) for j in range(P)]))
+                continue
+            cur = e.empty(P, M, len(layer))
+            for k, nd in enumerate(layer):
+                if nd.type != 'gp':
+                    continue
+                Z = rng.standard_normal((S, J, M))
+                st = self._joint_stats(l, k)
+                z = None if nd.connect is None else xd[:, torch.as_tensor(nd.connect, device=xd.device)]
+                if l == 0:
+                    xin = xd[:, torch.as_tensor(nd.input_dim, device=xd.device)]
+                    xin = (xin if z is None else torch.cat((xin, z), 1)).contiguous()
+                    E = e.tensor(np.ascontiguousarray(Z.transpose(2, 0, 1).reshape(M, P)))
+                    cur[:, :, k] = paths.draw_shared(e, nd.name, xin, st['W'], st['Linv'], st['Y'], nd.length, nd.scale[0],
+                                                     nd.nugget[0], E, J).T
+                    continue
+                idx = torch.as_tensor(nd.input_dim, device=xd.device)
+                for s in range(S):
+                    ps = st['per'][s]
+                    xs = prev[s * J:(s + 1) * J][:, :, idx]
+                    if z is not None:
+                        xs = torch.cat((xs, z[None].expand(J, M, z.shape[1])), 2)
+                    cur[s * J:(s + 1) * J, :, k] = paths.draw_per_path(e, nd.name, xs.contiguous(), ps['W'], ps['Linv'], ps['y'],
+                                                                        nd.length, nd.scale[0], nd.nugget[0], e.tensor(Z[s]))
+            cur_np = cur.cpu().numpy()
+            for k, nd in enumerate(layer):
+                if nd.type != 'gp':   # likelihood nodes sample y from the path's latents (emulation.py:785-822)
+                    for j in range(P):
+                        cur_np[j, :, k] = nd.sampling(prev_np[j][:, nd.input_dim])
+            out.append(cur_np)
+            prev, prev_np = cur, cur_np
+        out = [list(a.transpose(2, 1, 0)) for a in out]
+        return out if full_layer else out[-1]
+
+    def _joint_stats(self, l, k):
+        """sample_paths' statistics of GP node k of layer l, built when first asked for beside predict's: L^-1 of the
+        training correlation matrix (not the Matern cell reordering of the linked predictor: a permuted L^-1 is not
+        triangular).  First layer: one L^-1 shared by every imputation, the N imputations' outputs as rows Y; deeper
+        layers: L^-1 and y per imputation, through _LazyPer under the same byte budget."""
+        from . import paths
+        if self._stats is None:
+            self._build_stats()
+        key = ('joint', l, k)
+        st = self._stats.get(key)
+        if st is not None:
+            return st
+        e = self.engine
+        nd = self.all_layer[l][k]
+        Xg_h = peek(nd, 'global_input')
+        Xg = None if Xg_h is None else e.tensor(Xg_h)
+        W = None if nd.rep is None else e.tensor(nd.W_diag)
+
+        def ys(s):
+            return self.latents[s][l][:, k] if l < self.n_layer - 1 else np.asarray(nd.output, float).reshape(-1)
+
+        if l == 0:
+            Linv = paths.factor_inverse(e, nd.name, e.tensor(peek(nd, 'input')), Xg, W, nd.length, nd.nugget[0],
+                                        'layer 1, node %d (shared by every imputation)' % (k + 1))
+            st = dict(Linv=Linv, W=e.tensor(nd._X()), Y=e.tensor(np.stack([ys(s) for s in range(self.N)])))
+        else:
+            def build(s):
+                Xin = self.latents[s][l - 1][:, nd.input_dim]
+                Linv = paths.factor_inverse(e, nd.name, e.tensor(Xin), Xg, W, nd.length, nd.nugget[0],
+                                            'layer %d, node %d, imputation %d' % (l + 1, k + 1, s + 1))
+                Wall = Xin if Xg_h is None else np.concatenate((Xin, Xg_h), 1)
+                return dict(Linv=Linv, W=e.tensor(np.ascontiguousarray(Wall)), y=e.tensor(ys(s)))
+            Np = e.padded_dim(len(nd.output))
+            st = dict(per=_LazyPer(self, key, build, Np * Np * 8))
+        self._stats[key] = st
+        return st
+
     def nllik(self, x, y, m=50):
         """Negative predicted log-likelihood of test data under a DGP with ONE likelihood node on top
         (emulation.py:856-914): per imputation the latents' moments at x, the likelihood integrated by

@@ -177,6 +177,31 @@ class gp:
             return np.random.normal(mu, np.sqrt(s2), size=(sample_size, len(x))).T
         raise Exception("method must be 'mean_var' or 'sampling'.")
 
+    def sample_paths(self, x, sample_size=50):
+        """Joint posterior draws of the GP at the rows of x: (M, sample_size), each column one draw over all M rows
+        (predict(method='sampling') draws every row on its own).  The normals come from numpy's global generator,
+        np.random.standard_normal((sample_size, M)), as predict's do.  Dense mode only, at most 8192 rows; a training
+        correlation matrix that is not positive definite raises numpy.linalg.LinAlgError."""
+        from . import paths
+        if self.vecch:
+            raise NotImplementedError('sample_paths needs a dense GP: joint draws in Vecchia mode need a sparse algorithm '
+                                      'of their own (use remove_vecchia())')
+        paths.check_points(x)
+        k = self.kernel
+        e = k.engine
+        if k._stats is None:
+            k.compute_stats()
+        st = k._stats
+        if 'joint' not in st:   # (dropped with the statistics when compute_stats runs again)
+            st['joint'] = paths.factor_inverse(e, k.name, st['W'], st['Wg'], None if k.rep is None else e.tensor(k.W_diag),
+                                               k.length, k.nugget[0], 'the gp model')
+        xin = x[:, k.input_dim] if k.connect is None else np.concatenate((x[:, k.input_dim], x[:, k.connect]), 1)
+        Z = np.random.standard_normal((sample_size, len(x)))
+        y = e.tensor(np.asarray(k.output, float).reshape(1, -1))
+        out = paths.draw_shared(e, k.name, e.tensor(xin), st['Wall'], st['joint'], y, k.length, k.scale[0], k.nugget[0],
+                                e.tensor(np.ascontiguousarray(Z.T)), sample_size)
+        return out.cpu().numpy()
+
     def ppredict(self, x, method='mean_var', sample_size=50, m=50, chunk_num=None, core_num=None):
         """gp.py:373-410 (`chunk_num` / `core_num` are accepted and unused)."""
         return self.predict(x, method=method, sample_size=sample_size, m=m)

@@ -78,7 +78,8 @@ def _ensure_stats(nd):
 
 
 class lgp:
-    """all_layer: list of layers of containers; N imputations (1 if the system has GP emulators only)  (linkgp.py:140-165)."""
+    """all_layer: list of layers of containers; N imputations (1 if the system has GP emulators only)  (linkgp.py:140-165).
+    Joint sample paths (emulator.sample_paths / gp.sample_paths) are not offered for linked systems."""
 
     def __init__(self, all_layer, N=10):
         self.L = len(all_layer)

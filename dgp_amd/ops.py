@@ -513,6 +513,51 @@ class Engine:
                                         ldr, _dp(ry), nry, float(scale), float(nugget), _dp(mean), _dp(var), _dp(work)))
         return mean, var
 
+    def joint_cov(self, kind, x, W, Linv, y, length, scale, nugget, group=None, A=None, mean=None):
+        """Joint posterior covariance and mean of test points (dgpamd_joint_cov).  x: (batch, M, D) or (M, D); W: (G, n, D)
+        or (n, D); Linv: (G, ld, ld) or (ld, ld) with L^-1 in its lower tiles; y: (G, r, n), (r, n) or None; group: host
+        ints (batch,) picking each item's W / Linv / y (None: all 0).  Returns (A, mean): A (batch, Mp, Mp) dgpamd_potrf
+        buffers holding scale (K** + nugget I - V^T V), Mp = padded_dim(M); mean (batch, M, r) or None."""
+        xb = x if x.dim() == 3 else x[None]
+        Wb = W if W.dim() == 3 else W[None]
+        Lb = Linv if Linv.dim() == 3 else Linv[None]
+        batch, M, D = xb.shape
+        G, n = Wb.shape[0], Wb.shape[1]
+        r = 0 if y is None else y.shape[-2]
+        yb = None if y is None else (y if y.dim() == 3 else y[None])
+        assert Wb.shape[2] == D and Lb.shape[0] == G and (yb is None or (yb.shape[0] == G and yb.shape[2] == n))
+        for t in (xb, Wb, Lb) + (() if yb is None else (yb,)):
+            assert t.is_contiguous() and t.dtype == torch.float64
+        length = _f64(length)
+        Mp = self.padded_dim(M)
+        g = np.zeros(batch, dtype=np.int32) if group is None else np.ascontiguousarray(np.asarray(group, dtype=np.int32))
+        assert g.shape == (batch,)
+        if A is None:
+            A = self.empty(batch, Mp, Mp)
+        if mean is None and r > 0:
+            mean = self.empty(batch, M, r)
+        work = self.workspace(('joint',), lib.dgpamd_joint_workspace(n, M, r, batch))
+        ldl = Lb.shape[-1]
+        self._chk(self._enter() or lib.dgpamd_joint_cov(self.h, KIND[kind], n, M, D, r, batch, _dp(xb), M * D, _hp(g), G, _dp(Wb),
+                                                         n * D, _dp(Lb), ldl, Lb.shape[-2] * ldl, _dp(yb), r * n, _hp(length),
+                                                         len(length), float(scale), float(nugget), _dp(A), Mp * Mp, _dp(mean),
+                                                         _dp(work)))
+        return A, mean
+
+    def mvn_paths(self, L, mean, E, rep=1, out=None):
+        """out_b = mean_b(:, q // rep) + L_b E_b (dgpamd_mvn_paths).  L: (batch, Mp, Mp) factored joint_cov buffers;
+        E: (batch, M, c) standard normals; mean: (batch, M, c // rep) or None.  Returns out (batch, M, c)."""
+        batch, M, c = E.shape
+        Mp = self.padded_dim(M)
+        assert L.shape[-1] == Mp and L.is_contiguous() and E.is_contiguous()
+        assert mean is None or (mean.is_contiguous() and mean.shape == (batch, M, c // rep))
+        if out is None:
+            out = self.empty(batch, M, c)
+        sm = 0 if mean is None else M * (c // rep)
+        self._chk(self._enter() or lib.dgpamd_mvn_paths(self.h, M, c, rep, batch, _dp(L), Mp * Mp, _dp(mean), sm, _dp(E), M * c,
+                                                         _dp(out), M * c))
+        return out
+
     def linkgp_predict(self, kind, m, v, z, Wtr, Wg, length, Rinv, ldr, ry, scale, nugget, mean=None, var=None,
                        drop=None):
         """drop (M,) int32 device tensor: leave training point drop[t] out of test point t's conditioning set."""

@@ -1,0 +1,128 @@
+"""Joint posterior sample paths of GP nodes (emulator.sample_paths, gp.sample_paths).
+
+A node with training inputs W (global columns appended), outputs y and R = L L^T has at test inputs X* the joint posterior
+    mu = K(X*,W) R^-1 y = V^T w,   Sigma = scale (K(X*,X*) + nugget I - V^T V),   V = L^-1 K(W,X*),  w = L^-1 y.
+The statistics are L^-1 (what dgpamd_potri leaves in the factored buffer); dgpamd_joint_cov forms V, Sigma and mu,
+dgpamd_potrf factors Sigma and dgpamd_mvn_paths draws mu + chol(Sigma) e.  Dense nodes only: a joint draw of a Vecchia
+node needs a sparse algorithm of its own.
+"""
+import warnings
+
+import numpy as np
+import torch
+
+from .ops import raise_not_pd
+
+MAX_POINTS = 8192   # test points per call (Sigma is M x M on the device)
+JITTERS = (1e-10, 1e-8)   # multiples of scale added to Sigma's diagonal when it does not factor
+
+
+def check_points(x):
+    if x.ndim != 2:
+        raise Exception('The testing input has to be a numpy 2d-array')
+    if len(x) > MAX_POINTS:
+        raise ValueError('sample_paths draws at most %d test points jointly (got %d): split x' % (MAX_POINTS, len(x)))
+
+
+def factor_inverse(e, kind, Xl, Xg, W, length, nugget, where):
+    """L^-1 of R = K(W, W) + nugget diag(W_diag) as a padded (Np x Np) device buffer (lower tiles valid).  Raises
+    numpy.linalg.LinAlgError naming `where` when R is not positive definite (predict falls back to pinvh there; a joint
+    Gaussian draw has no sound equivalent)."""
+    n = Xl.shape[0]
+    Np = e.padded_dim(n)
+    A = e.empty(Np, Np)
+    e.kmatrix(kind, Xl, None, Xg, length, nugget, W=W, out=A, full=False)
+    work = e.potrf_workspace(n, 1)
+    _, info = e.potrf(n, A, work=work)
+    bad = int(e.fetch(info)[0])
+    if bad < 0:
+        raise_not_pd(bad)
+    if bad > 0:
+        raise np.linalg.LinAlgError('sample_paths: the training correlation matrix of %s is not positive definite (leading '
+                                    'minor %d); predict() uses its pseudo-inverse there, a joint draw cannot' % (where, bad))
+    e.potri(n, A, e.workspace(('pathsAinv', n), Np * Np * 8).view(torch.float64)[:Np * Np].view(Np, Np), 0, work)
+    return A
+
+
+def _chunk(e, n, M, r, c):
+    """Items per dgpamd_joint_cov / dgpamd_potrf call: <= 64 and within half of the free device memory."""
+    Mp = e.padded_dim(M)
+    npad, Mc = -(-n // 64) * 64, -(-M // 64) * 64 + (-(-r // 64) * 64 if r else 0)
+    per = 8 * (Mp * Mp + 2 * npad * Mc + M * (r + c) * 2) + e.potrf_workspace(M, 1).numel()
+    free = torch.cuda.mem_get_info(e.device)[0]
+    return int(max(1, min(64, free // 2 // per)))
+
+
+def _factor(e, M, A, scale, build):
+    """dgpamd_potrf on the joint_cov buffers A (batch, Mp, Mp).  A lost hand-off (info < 0) switches the engine to the
+    per-block-step factorisation and rebuilds the buffers once, as dgp.train does; a buffer that does not factor
+    (info > 0) is rebuilt alone and retried with scale * JITTERS added to its diagonal, one warning each."""
+    B = A.shape[0]
+    _, info = e.potrf(M, A, batch=B)
+    info = e.fetch(info).astype(np.int64)
+    if (info < 0).any():
+        warnings.warn('dgp_amd: sample_paths: the one-launch factorisation lost a hand-off; this engine now factors with one '
+                      'launch per block step (set_potrf_mode(0))', RuntimeWarning)
+        e.sync()
+        e.set_potrf_mode(0)
+        build(None, A)
+        _, info = e.potrf(M, A, batch=B)
+        info = e.fetch(info).astype(np.int64)
+        if (info < 0).any():
+            raise_not_pd(int(info[info < 0][0]))
+    for b in np.nonzero(info > 0)[0]:
+        ok = False
+        for jit in JITTERS:
+            warnings.warn('dgp_amd: sample_paths: a joint covariance did not factor; retried with %g added to its diagonal'
+                          % (jit * scale), RuntimeWarning)
+            Ab = A[b:b + 1]
+            build(int(b), Ab)
+            Ab[0].diagonal()[:M] += jit * scale
+            _, i1 = e.potrf(M, Ab, batch=1)
+            i1 = int(e.fetch(i1)[0])
+            if i1 < 0:
+                raise_not_pd(i1)
+            if i1 == 0:
+                ok = True
+                break
+        if not ok:
+            raise np.linalg.LinAlgError('sample_paths: a joint posterior covariance is not positive definite, even with %g '
+                                        'added to its diagonal' % (JITTERS[-1] * scale))
+
+
+def draw_shared(e, kind, x, W, Linv, Y, length, scale, nugget, Z, rep):
+    """One node, one set of test inputs x (M, D) shared by every path, rows Y (r, n) of right-hand sides: Sigma is
+    factored once; column q of the result is mean column q // rep + chol(Sigma) Z[:, q].  Z: (M, c) device normals.
+    Returns (M, c)."""
+    M = x.shape[0]
+
+    def build(_, A):
+        e.joint_cov(kind, x, W, Linv, Y, length, scale, nugget, A=A)
+
+    A = e.empty(1, e.padded_dim(M), e.padded_dim(M))
+    _, mean = e.joint_cov(kind, x, W, Linv, Y, length, scale, nugget, A=A)
+    _factor(e, M, A, scale, build)
+    return e.mvn_paths(A, mean, Z[None].contiguous(), rep=rep)[0]
+
+
+def draw_per_path(e, kind, xs, W, Linv, y, length, scale, nugget, Z):
+    """One node, one group (W, Linv, y (n,)), every path its own test inputs xs (P, M, D) and normals Z (P, M):
+    Sigma is formed and factored per path.  Returns (P, M)."""
+    P, M, _ = xs.shape
+    n = W.shape[0]
+    out = e.empty(P, M)
+    Y = y.reshape(1, n)
+    step = _chunk(e, n, M, 1, 1)
+    for p0 in range(0, P, step):
+        p1 = min(P, p0 + step)
+        xc = xs[p0:p1].contiguous()
+
+        def build(b, A, xc=xc):
+            xb = xc if b is None else xc[b:b + 1].contiguous()
+            e.joint_cov(kind, xb, W, Linv, Y, length, scale, nugget, A=A)
+
+        A = e.empty(p1 - p0, e.padded_dim(M), e.padded_dim(M))
+        _, mean = e.joint_cov(kind, xc, W, Linv, Y, length, scale, nugget, A=A)
+        _factor(e, M, A, scale, build)
+        out[p0:p1] = e.mvn_paths(A, mean, Z[p0:p1].reshape(p1 - p0, M, 1).contiguous())[:, :, 0]
+    return out

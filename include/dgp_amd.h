@@ -353,6 +353,31 @@ int dgpamd_gp_predict(dgpamd_ctx *ctx, int kind, int64_t n, int64_t M, int D,
                       const double *Rinv, int64_t ldr, const double *ry, int nry, double scale, double nugget,
                       double *mean, double *var, void *work);
 
+/* ---- joint posterior of test points and sample paths (emulator.sample_paths / gp.sample_paths) ------------------
+ * The joint form of functions.gp  functions.py:379-394 (which returns the diagonal only) -- the posterior analogue of
+ * the prior paths of path.generate  synthetic.py:20-44.  Item b (batch <= DGPAMD_MAXB) has test inputs x_b (M x D,
+ * batch stride stride_x, [local | global]) and a group g = group_h[b] (host; NULL: all 0) < ngroups that selects
+ * training inputs W_g (n x D, stride_w), Linv_g = L^-1 of the training correlation matrix R = L L^T (ld = ldl,
+ * stride_l; the lower 64x64 tiles of [0,n)^2 are read, entries above the diagonal ignored: what dgpamd_potri leaves
+ * in A) and r right-hand-side rows y_g (r x n, stride_y).  With K* = K(W, x_b), V = L^-1 K*, w = L^-1 y^T:
+ *   A_b    = Sigma_b = scale (K(x_b, x_b) + nugget I - V^T V): lower tiles of a dgpamd_potrf buffer (ld =
+ *            dgpamd_padded_dim(M), batch stride stride_a, padding zero, no right-hand sides);
+ *   mean_b = V^T w  (M x r, batch stride M r; may be NULL iff r == 0).
+ * diag(Sigma_b) is dgpamd_gp_predict's variance, mean_b its mean.  work: dgpamd_joint_workspace(n, M, r, batch) bytes. */
+size_t dgpamd_joint_workspace(int64_t n, int64_t M, int r, int batch);
+int dgpamd_joint_cov(dgpamd_ctx *ctx, int kind, int64_t n, int64_t M, int D, int r, int batch,
+                     const double *x, int64_t stride_x, const int32_t *group_h, int ngroups,
+                     const double *W, int64_t stride_w, const double *Linv, int64_t ldl, int64_t stride_l,
+                     const double *y, int64_t stride_y, const double *length_h, int nlen, double scale, double nugget,
+                     double *A, int64_t stride_a, double *mean, void *work);
+/* Joint draws from the factored covariances: out_b = mean_b(:, q / rep) + L_b E_b, with L_b the factor
+ * dgpamd_potrf left in a buffer of dgpamd_joint_cov (ld = dgpamd_padded_dim(M), batch stride stride_l; scale is
+ * already inside it), E_b (M x c) standard normals, mean_b (M x c / rep; may be NULL) and out_b (M x c), each with its
+ * own batch stride.  c == 1: one wave per row; c > 1: triangular matrix product on f64 MFMA. */
+int dgpamd_mvn_paths(dgpamd_ctx *ctx, int64_t M, int c, int rep, int batch, const double *L, int64_t stride_l,
+                     const double *mean, int64_t stride_m, const double *E, int64_t stride_e, double *out,
+                     int64_t stride_o);
+
 /* ---- a12-a14  linked-GP prediction ------------------------------------------
  * functions.link_gp  functions.py:396-430 with IJ_sexp :432-451 / IJ_matern
  * :453-494 (Jd, Jd0 vecchia.py:915-988), trace_sum :496-506, quad vecchia.py:990:
