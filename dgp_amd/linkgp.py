@@ -1,12 +1,16 @@
 """Linked (D)GP emulation of a feed-forward system of emulators -- mirror of dgpsi.container / dgpsi.lgp
-(linkgp.py:12-608), mean/variance prediction.  Pure orchestration over kernel.gp_prediction /
+(linkgp.py:12-608), mean/variance prediction; joint sample paths of the system (lgp.sample_paths, over paths.py).  Pure orchestration over kernel.gp_prediction /
 linkgp_prediction / linkgp_prediction_full; aggregation over imputations as emulation.py:846-847."""
+import collections
 import contextlib
 import copy
+import hashlib
 
 import numpy as np
+import torch
 
 from .imputation import imputer
+from .kernel_class import peek
 
 
 class container:
@@ -77,9 +81,20 @@ def _ensure_stats(nd):
         nd.compute_stats()
 
 
+class _By:
+    """Indexable view: item i is f(i) (paths.draw_per_path reads its groups' statistics through it)."""
+
+    def __init__(self, f):
+        self.f = f
+
+    def __getitem__(self, i):
+        return self.f(i)
+
+
 class lgp:
     """all_layer: list of layers of containers; N imputations (1 if the system has GP emulators only)  (linkgp.py:140-165).
-    Joint sample paths (emulator.sample_paths / gp.sample_paths) are not offered for linked systems."""
+    `sample_paths` draws whole functions of the system (dense emulators): column s*sample_size + j is one joint draw over all
+    rows of x, the same path in every emulator and layer."""
 
     def __init__(self, all_layer, N=10):
         self.L = len(all_layer)
@@ -113,6 +128,8 @@ class lgp:
             for layer, ml in zip(system, mode):
                 for c, on in zip(layer, ml):
                     c.to_vecchia() if on else c.remove_vecchia()
+        for a in ('_paths_stats', '_per_cache', '_per_bytes'):   # sample_paths' statistics are rebuilt on next use
+            self.__dict__.pop(a, None)
 
     # -------------------------------------------------------------- single emulators
     @staticmethod
@@ -194,6 +211,32 @@ class lgp:
         return out
 
     # -------------------------------------------------------------- the system
+    def _global_inputs(self, x):
+        """x as the per-layer list of global inputs (predict's forms and checks)."""
+        if isinstance(x, list):
+            if len(x) != self.L:
+                raise Exception('When test input is given as a list, it must contain global inputs to the all layers '
+                                '(even with no global inputs to internal layers). Set None as the global input to the '
+                                'internal models if they have no global inputs.')
+            return x
+        if x.ndim == 1:
+            raise Exception('The testing input has to be a numpy 2d-array.')
+        return [x] + [[None] * k for k in self.num_model]
+
+    @staticmethod
+    def _feeding(model, l):
+        """local_input_idx of an emulator in layer l > 0 as a list over the layers before it (entries None or columns)."""
+        idx = model.local_input_idx
+        if l == 0:
+            if isinstance(idx, list):
+                raise Exception('When an emulator is in the first layer, local_input_idx must be a 1d-array.')
+            return idx
+        if not isinstance(idx, list):
+            return [None] * (l - 1) + [idx]
+        if len(idx) != l:
+            raise Exception('local_input_idx should be a list that has length of %i.' % l)
+        return idx
+
     def predict(self, x, method='mean_var', full_layer=False, sample_size=50, m=50):
         """Means and variances of the final-layer emulators' outputs (lists of (M x q) arrays), or of every
         layer if full_layer (linkgp.py:285-501); method='sampling': per emulator an array (q, M, N * sample_size) of
@@ -201,15 +244,7 @@ class lgp:
         if method not in ('mean_var', 'sampling'):
             raise Exception("method must be either 'mean_var' or 'sampling'.")
         sampling = method == 'sampling'
-        if isinstance(x, list):
-            if len(x) != self.L:
-                raise Exception('When test input is given as a list, it must contain global inputs to the all layers '
-                                '(even with no global inputs to internal layers). Set None as the global input to the '
-                                'internal models if they have no global inputs.')
-        else:
-            if x.ndim == 1:
-                raise Exception('The testing input has to be a numpy 2d-array.')
-            x = [x] + [[None] * k for k in self.num_model]
+        x = self._global_inputs(x)
         means, variances, draws = [], [], []
         for one in self.all_layer_set:
             feed_m, feed_v, lay_m, lay_v, lay_s = [], [], [], [], []
@@ -217,15 +252,10 @@ class lgp:
                 ms, vs, ss = [], [], []
                 for k, model in enumerate(layer):
                     if l == 0:
-                        if isinstance(model.local_input_idx, list):
-                            raise Exception('When an emulator is in the first layer, local_input_idx must be a 1d-array.')
+                        self._feeding(model, l)
                         mb, vb, mk, vk = self._emulate(model, x[0][:, model.local_input_idx], None, None, None, m, before=True)
                     else:
-                        idx = model.local_input_idx
-                        if not isinstance(idx, list):
-                            idx = [None] * (l - 1) + [idx]
-                        elif len(idx) != l:
-                            raise Exception('local_input_idx should be a list that has length of %i.' % l)
+                        idx = self._feeding(model, l)
                         m_in = np.concatenate([feed_m[i][:, j] for i, j in enumerate(idx) if j is not None], axis=1)
                         v_in = np.concatenate([feed_v[i][:, j] for i, j in enumerate(idx) if j is not None], axis=1)
                         mb, vb, mk, vk = self._emulate(model, None, m_in, v_in, x[l][k], m, before=True)
@@ -258,6 +288,194 @@ class lgp:
         out = [agg([means[s][k] for s in range(len(means))], [variances[s][k] for s in range(len(means))])
                for k in range(len(self.all_layer[-1]))]
         return [o[0] for o in out], [o[1] for o in out]
+
+    # -------------------------------------------------------------- joint sample paths
+    def sample_paths(self, x, sample_size=50, full_layer=False):
+        """Joint draws of the system's functions at the rows of x (dense emulators).  x as in predict.  Returns the layout of
+        predict(x, method='sampling'): per final-layer emulator a (q, M, N*sample_size) array, or with full_layer a list
+        over layers of such lists -- but column s*sample_size + j is ONE draw over all M rows: path j of system s
+        (all_layer_set[s]), the same path in every emulator and layer.  Each path walks the system layer by layer, emulator
+        by emulator, and within a DGP emulator layer by layer and node by node: a GP node is drawn jointly from its
+        posterior at the path's inputs -- the feeding emulators' draws of this path selected by local_input_idx, plus
+        x[l][k]; a DGP node with `connect` takes its global columns as predict does (the path's draws of the emulator's own
+        inputs, external ones from x[l][k]); likelihood nodes sample from the path's latents (nd.sampling, or the class
+        probabilities of a Categorical node).  Normals come from numpy's global generator: one
+        np.random.standard_normal((N, sample_size, M)) block per GP node in that walk order; likelihood nodes sample after
+        the GP nodes of their layer.  At most 8192 rows (ValueError); a Vecchia emulator raises NotImplementedError and a
+        training correlation matrix that is not positive definite numpy.linalg.LinAlgError, naming where."""
+        from . import paths
+        x = self._global_inputs(x)
+        idxs = [[self._feeding(c, l) for c in layer] for l, layer in enumerate(self.all_layer)]
+        for system in [self.all_layer] + list(self.all_layer_set):
+            for l, layer in enumerate(system):
+                for k, c in enumerate(layer):
+                    if c.vecch:
+                        raise NotImplementedError('sample_paths needs dense emulators: emulator %d of layer %d is in Vecchia '
+                                                  'mode (joint draws of a Vecchia emulator need a sparse algorithm of their '
+                                                  'own; use set_vecchia(False))' % (k + 1, l + 1))
+        paths.check_points(x[0])
+        sets = self.all_layer_set
+        e = next(c.structure.engine if c.type == 'gp' else c.structure[0][0].engine for c in sets[0][0])
+        M, S, J = len(x[0]), len(sets), int(sample_size)
+        feed, out = [], []
+        for l in range(self.L):
+            outs = []
+            for k in range(len(self.all_layer[l])):
+                models = [one[l][k] for one in sets]
+                z = None if l == 0 or x[l][k] is None else e.tensor(np.asarray(x[l][k], float))
+                if l == 0:   # the same inputs for every path
+                    m = e.tensor(np.ascontiguousarray(x[0][:, idxs[0][k]], dtype=float))
+                else:
+                    m = torch.cat([feed[i][:, :, torch.as_tensor(np.atleast_1d(j), device=e.device)]
+                                   for i, j in enumerate(idxs[l][k]) if j is not None], 2)
+                where = 'layer %d, emulator %d' % (l + 1, k + 1)
+                if models[0].type == 'gp':
+                    xin = m if z is None else torch.cat((m, z[None].expand(m.shape[0], M, z.shape[1])), 2)
+                    cur = self._paths_node(e, (l, k), [c.structure for c in models], xin.contiguous(), J,
+                                           where + ' (gp)')[:, :, None]
+                else:
+                    cur = self._paths_dgp(e, l, k, [c.structure for c in models], m, z, J)
+                outs.append(cur)
+            feed.append(torch.cat(outs, 2))
+            if full_layer or l == self.L - 1:
+                out.append([np.ascontiguousarray(c.cpu().numpy().transpose(2, 1, 0)) for c in outs])
+        return out if full_layer else out[-1]
+
+    def _paths_dgp(self, e, l, k, structs, m, z, J):
+        """Paths (S*J, M, q) of DGP emulator k of layer l: structs[s] is system s's structure; m its input, (M, D) shared
+        by every path (l == 0) or (S*J, M, D); z the external input x[l][k] (M, Dz) or None."""
+        S, L = len(structs), len(structs[0])
+        P, M = S * J, m.shape[-2]
+        internal, external = structs[0][0][0].input_dim, structs[0][0][0].connect
+
+        def per_path(t):
+            return t if t.dim() == 3 else t[None].expand(P, M, t.shape[1])
+
+        prev = None
+        for il, layer in enumerate(structs[0]):
+            if il == L - 1 and len(layer) == 1 and getattr(layer[0], 'name', None) == 'Categorical':
+                cat, lat = layer[0], prev.cpu().numpy()
+                return e.tensor(np.stack([structs[p // J][il][0].sampling(lat[p][:, cat.input_dim]) for p in range(P)])
+                                .reshape(P, M, -1))
+            cur = e.empty(P, M, len(layer))
+            for j, nd in enumerate(layer):
+                if nd.type != 'gp':
+                    continue
+                if il == 0:
+                    xin = m if z is None else torch.cat((per_path(m), per_path(z)), 2)
+                else:
+                    parts = [prev[:, :, torch.as_tensor(nd.input_dim, device=e.device)]]
+                    if nd.connect is not None and l == 0:
+                        parts.append(per_path(m[:, torch.as_tensor(nd.connect, device=e.device)]))
+                    elif nd.connect is not None:   # the global columns: as lgp.dgp_pred
+                        if il == L - 1:
+                            i1 = np.where(nd.connect[:, None] == internal[None, :])[1]
+                            i2 = np.array([], dtype=int) if external is None else \
+                                np.where(nd.connect[:, None] == external[None, :])[1]
+                        else:
+                            D = m.shape[-1]
+                            i1, i2 = nd.connect[nd.connect <= D - 1], nd.connect[nd.connect > D - 1] - D
+                        if i1.size:
+                            parts.append(per_path(m)[:, :, torch.as_tensor(i1, device=e.device)])
+                        if i2.size:
+                            parts.append(per_path(z[:, torch.as_tensor(i2, device=e.device)]))
+                    xin = torch.cat(parts, 2)
+                where = 'layer %d, emulator %d, node %d of its layer %d' % (l + 1, k + 1, j + 1, il + 1)
+                cur[:, :, j] = self._paths_node(e, (l, k, il, j), [st[il][j] for st in structs], xin.contiguous(), J, where)
+            if any(nd.type != 'gp' for nd in layer):   # likelihood nodes sample y from the path's latents
+                cur_np, lat = cur.cpu().numpy(), prev.cpu().numpy()
+                for j, nd in enumerate(layer):
+                    if nd.type != 'gp':
+                        for p in range(P):
+                            cur_np[p, :, j] = structs[p // J][il][j].sampling(lat[p][:, nd.input_dim])
+                cur = e.tensor(cur_np)
+            prev = cur
+        return prev
+
+    def _paths_node(self, e, pos, nodes, xin, J, where):
+        """Paths (S*J, M) of one GP node over all systems: nodes[s] is system s's node, xin its inputs, (M, D) shared by
+        every path or (S*J, M, D).  Draws this node's (S, J, M) block of normals.  Systems whose nodes share kernel and
+        hyper-parameters draw in one call: through paths.draw_shared (one Sigma per distinct L^-1, the systems' y as its
+        right-hand sides) for shared inputs, else through paths.draw_per_path with the system as each path's group."""
+        from . import paths
+        S, M = len(nodes), xin.shape[-2]
+        P = S * J
+        Z = np.random.standard_normal((S, J, M))
+        st = self._node_stats(e, pos, nodes, where)
+        calls = collections.defaultdict(list)
+        for s in range(S):
+            calls[st['call'][s]].append(s)
+        draws = []   # (systems, (len(systems)*J, M) paths)
+        for ss in calls.values():
+            nd = nodes[ss[0]]
+            hyper = (nd.length, nd.scale[0], nd.nugget[0])
+            if xin.dim() == 2:
+                by = collections.defaultdict(list)
+                for s in ss:
+                    by[st['cls'][s]].append(s)
+                for c, cs in by.items():
+                    ps = st['per'][c]
+                    Y = torch.stack([st['y'][s] for s in cs])
+                    E = e.tensor(np.ascontiguousarray(Z[cs].transpose(2, 0, 1).reshape(M, len(cs) * J)))
+                    draws.append((cs, paths.draw_shared(e, nd.name, xin, ps['W'], ps['Linv'], Y, *hyper, E, J).T))
+                continue
+            xs = xin if len(ss) == S else xin.view(S, J, M, -1)[torch.as_tensor(ss, device=e.device)].reshape(-1, M, xin.shape[2])
+            W = _By(lambda i, ss=ss: st['per'][st['cls'][ss[i]]]['W'])
+            Linv = _By(lambda i, ss=ss: st['per'][st['cls'][ss[i]]]['Linv'])
+            y = _By(lambda i, ss=ss: st['y'][ss[i]])
+            draws.append((ss, paths.draw_per_path(e, nd.name, xs.contiguous(), W, Linv, y, *hyper,
+                                                  e.tensor(Z[ss].reshape(len(ss) * J, M)), group=np.repeat(np.arange(len(ss)), J))))
+        if len(draws) == 1:
+            return draws[0][1].contiguous()
+        out = e.empty(S, J, M)
+        for ss, o in draws:
+            out[torch.as_tensor(ss, device=e.device)] = o.reshape(len(ss), J, M)
+        return out.reshape(P, M)
+
+    def _node_stats(self, e, pos, nodes, where):
+        """sample_paths' statistics of one GP node position over the systems, cached on the lgp (dropped by set_vecchia):
+        y per system; L^-1 (paths.factor_inverse) and W per distinct training set -- inputs, replicate weights, lengths and
+        nugget compared by content, so copies of one GP (lgp.__init__'s snapshots, or systems built by hand) and the
+        first-layer nodes of a DGP emulator share one.  One distinct set is kept; several (the deeper nodes of a DGP
+        emulator: one per system) are built when first asked for and kept under the emulator's byte budget (_LazyPer)."""
+        from . import paths
+        from .emulation import _LazyPer
+        cache = self.__dict__.setdefault('_paths_stats', {})
+        st = cache.get(pos)
+        if st is not None:
+            return st
+        self.__dict__.setdefault('_per_cache', collections.OrderedDict())
+        self.__dict__.setdefault('_per_bytes', 0)
+        cls, call, first, keys = [], [], [], {}
+        for s, nd in enumerate(nodes):
+            h = hashlib.sha1(nd.name.encode())
+            for a in (peek(nd, 'input'), peek(nd, 'global_input'), None if nd.rep is None else nd.W_diag, nd.length,
+                      nd.nugget):
+                h.update(b'-' if a is None else np.ascontiguousarray(a, dtype=float).tobytes() + str(np.shape(a)).encode())
+            c = keys.setdefault(h.digest(), len(keys))
+            if c == len(first):
+                first.append(s)
+            cls.append(c)
+            call.append((nd.name, np.asarray(nd.length, float).tobytes(), float(nd.scale[0]), float(nd.nugget[0]),
+                         np.shape(nd._X())))
+
+        def build(c):
+            nd, s = nodes[first[c]], first[c]
+            Xg = peek(nd, 'global_input')
+            Linv = paths.factor_inverse(e, nd.name, e.tensor(np.ascontiguousarray(peek(nd, 'input'), dtype=float)),
+                                        None if Xg is None else e.tensor(Xg), None if nd.rep is None else e.tensor(nd.W_diag),
+                                        nd.length, nd.nugget[0], '%s, system %d' % (where, s + 1))
+            return dict(Linv=Linv, W=e.tensor(np.ascontiguousarray(nd._X(), dtype=float)))
+
+        if len(first) == 1:
+            per = [build(0)]
+        else:
+            Np = e.padded_dim(len(nodes[0].output))
+            per = _LazyPer(self, ('paths',) + tuple(pos), build, Np * Np * 8)
+        st = dict(cls=cls, call=call, per=per,
+                  y=[e.tensor(np.asarray(nd.output, dtype=float).reshape(-1)) for nd in nodes])
+        cache[pos] = st
+        return st
 
     @contextlib.contextmanager
     def temp_all_layer(self):

@@ -516,16 +516,18 @@ class Engine:
     def joint_cov(self, kind, x, W, Linv, y, length, scale, nugget, group=None, A=None, mean=None):
         """Joint posterior covariance and mean of test points (dgpamd_joint_cov).  x: (batch, M, D) or (M, D); W: (G, n, D)
         or (n, D); Linv: (G, ld, ld) or (ld, ld) with L^-1 in its lower tiles; y: (G, r, n), (r, n) or None; group: host
-        ints (batch,) picking each item's W / Linv / y (None: all 0).  Returns (A, mean): A (batch, Mp, Mp) dgpamd_potrf
+        ints (batch,) picking each item's W / Linv / y (None: all 0).  A W, Linv or y with one group (2-d, or a leading
+        dimension of 1) is shared by all G groups (group stride 0).  Returns (A, mean): A (batch, Mp, Mp) dgpamd_potrf
         buffers holding scale (K** + nugget I - V^T V), Mp = padded_dim(M); mean (batch, M, r) or None."""
         xb = x if x.dim() == 3 else x[None]
         Wb = W if W.dim() == 3 else W[None]
         Lb = Linv if Linv.dim() == 3 else Linv[None]
         batch, M, D = xb.shape
-        G, n = Wb.shape[0], Wb.shape[1]
         r = 0 if y is None else y.shape[-2]
         yb = None if y is None else (y if y.dim() == 3 else y[None])
-        assert Wb.shape[2] == D and Lb.shape[0] == G and (yb is None or (yb.shape[0] == G and yb.shape[2] == n))
+        G, n = max(Wb.shape[0], Lb.shape[0], 1 if yb is None else yb.shape[0]), Wb.shape[1]
+        assert Wb.shape[2] == D and Wb.shape[0] in (1, G) and Lb.shape[0] in (1, G)
+        assert yb is None or (yb.shape[0] in (1, G) and yb.shape[2] == n)
         for t in (xb, Wb, Lb) + (() if yb is None else (yb,)):
             assert t.is_contiguous() and t.dtype == torch.float64
         length = _f64(length)
@@ -538,8 +540,10 @@ class Engine:
             mean = self.empty(batch, M, r)
         work = self.workspace(('joint',), lib.dgpamd_joint_workspace(n, M, r, batch))
         ldl = Lb.shape[-1]
+        sw, sl = (n * D if Wb.shape[0] > 1 else 0), (Lb.shape[-2] * ldl if Lb.shape[0] > 1 else 0)
+        sy = r * n if yb is not None and yb.shape[0] > 1 else 0
         self._chk(self._enter() or lib.dgpamd_joint_cov(self.h, KIND[kind], n, M, D, r, batch, _dp(xb), M * D, _hp(g), G, _dp(Wb),
-                                                         n * D, _dp(Lb), ldl, Lb.shape[-2] * ldl, _dp(yb), r * n, _hp(length),
+                                                         sw, _dp(Lb), ldl, sl, _dp(yb), sy, _hp(length),
                                                          len(length), float(scale), float(nugget), _dp(A), Mp * Mp, _dp(mean),
                                                          _dp(work)))
         return A, mean

@@ -105,24 +105,45 @@ def draw_shared(e, kind, x, W, Linv, Y, length, scale, nugget, Z, rep):
     return e.mvn_paths(A, mean, Z[None].contiguous(), rep=rep)[0]
 
 
-def draw_per_path(e, kind, xs, W, Linv, y, length, scale, nugget, Z):
-    """One node, one group (W, Linv, y (n,)), every path its own test inputs xs (P, M, D) and normals Z (P, M):
-    Sigma is formed and factored per path.  Returns (P, M)."""
+def _stack(ts):
+    """The groups' tensors stacked, or the one tensor they all are (shared by every group: joint_cov's group stride 0)."""
+    return ts[0] if all(t is ts[0] for t in ts) else torch.stack(ts)
+
+
+def draw_per_path(e, kind, xs, W, Linv, y, length, scale, nugget, Z, group=None):
+    """One node, every path its own test inputs xs (P, M, D) and normals Z (P, M): Sigma is formed and factored per path,
+    one joint_cov -> potrf -> mvn_paths chain per chunk of paths.  group None: one group, W (n, D), Linv (ld, ld), y (n,).
+    Else host ints (P,) picking each path's group, and W, Linv, y are indexable by group: read chunk by chunk, only for
+    the groups of the chunk (a tensor that several groups hold is passed once).  Returns (P, M)."""
     P, M, _ = xs.shape
-    n = W.shape[0]
+    if group is None:
+        W, Linv, y, group = [W], [Linv], [y], np.zeros(P, np.int64)
+    group = np.asarray(group)
+    n, ld = W[int(group[0])].shape[0], Linv[int(group[0])].shape[-1]
     out = e.empty(P, M)
-    Y = y.reshape(1, n)
     step = _chunk(e, n, M, 1, 1)
-    for p0 in range(0, P, step):
-        p1 = min(P, p0 + step)
+    gcap = max(1, torch.cuda.mem_get_info(e.device)[0] // 4 // (ld * ld * 8))   # groups' L^-1 stacked in one chunk
+    p0 = 0
+    while p0 < P:
+        p1, seen = min(P, p0 + step), set()
+        for i in range(p0, p1):
+            seen.add(int(group[i]))
+            if len(seen) > gcap:
+                p1 = i
+                break
+        gs = np.unique(group[p0:p1])
+        local = np.searchsorted(gs, group[p0:p1])
+        Wc, Lc, Yc = (_stack([t[int(g)] for g in gs]) for t in (W, Linv, y))
+        Yc = Yc.reshape(1, n) if Yc.dim() == 1 else Yc.reshape(len(gs), 1, n)
         xc = xs[p0:p1].contiguous()
 
-        def build(b, A, xc=xc):
-            xb = xc if b is None else xc[b:b + 1].contiguous()
-            e.joint_cov(kind, xb, W, Linv, Y, length, scale, nugget, A=A)
+        def build(b, A, xc=xc, Wc=Wc, Lc=Lc, Yc=Yc, local=local):
+            xb, gb = (xc, local) if b is None else (xc[b:b + 1].contiguous(), local[b:b + 1])
+            e.joint_cov(kind, xb, Wc, Lc, Yc, length, scale, nugget, group=gb, A=A)
 
         A = e.empty(p1 - p0, e.padded_dim(M), e.padded_dim(M))
-        _, mean = e.joint_cov(kind, xc, W, Linv, Y, length, scale, nugget, A=A)
+        _, mean = e.joint_cov(kind, xc, Wc, Lc, Yc, length, scale, nugget, group=local, A=A)
         _factor(e, M, A, scale, build)
         out[p0:p1] = e.mvn_paths(A, mean, Z[p0:p1].reshape(p1 - p0, M, 1).contiguous())[:, :, 0]
+        p0 = p1
     return out
