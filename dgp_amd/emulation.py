@@ -523,6 +523,74 @@ class emulator:
         out = [list(a.transpose(2, 1, 0)) for a in out]
         return out if full_layer else out[-1]
 
+    def sample_paths_vecchia(self, x, sample_size=50, full_layer=False, m=50):
+        """sample_paths by the Vecchia factorisation of each node's joint predictive distribution (vpaths, DESIGN I.11):
+        the same container and column layout, for dense and Vecchia emulators and any number of rows.  The rows of x are
+        drawn in one order, the emulator's sampling generator's permutation(M), taken first; every GP node then draws each
+        row given its m nearest training rows (the imputation's latents below layer 1) and earlier-drawn rows of the same
+        path, with one standard_normal((N, sample_size, M)) block per GP node as sample_paths.  With m >= n + M - 1 this is
+        sample_paths' dense joint.  A conditioning block that does not factor is retried with a jitter, then raises
+        numpy.linalg.LinAlgError naming its layer, node and imputation."""
+        from . import vpaths
+        if self.shard or getattr(self, 'shard_points', False):
+            raise NotImplementedError("sample_paths_vecchia with the imputations sharded over ranks would return partial "
+                                      "draws; use emulator(..., shard=False)")
+        vpaths.check_args(x, m)
+        e = self.engine
+        M, S, J = len(x), self.N, int(sample_size)
+        P = S * J
+        rng = self._sample_rng
+        order = rng.permutation(M)
+        xd = e.tensor(x)
+        cat = self._cat()
+        out, prev, prev_np = [], None, None
+        for l, layer in enumerate(self.all_layer):
+            if l == self.n_layer - 1 and cat is not None:
+                out.append(np.stack([cat.sampling(prev_np[j][:, cat.input_dim]) for j in range(P)]))
+                continue
+            cur = e.empty(P, M, len(layer))
+            for k, nd in enumerate(layer):
+                if nd.type != 'gp':
+                    continue
+                Z = e.tensor(rng.standard_normal((S, J, M)).reshape(P, M))
+                Xg = peek(nd, 'global_input')
+                omega = None if nd.rep is None else e.tensor(nd.W_diag)
+                z = None if nd.connect is None else xd[:, torch.as_tensor(nd.connect, device=xd.device)]
+
+                def ys(s, l=l, k=k, nd=nd):
+                    return self.latents[s][l][:, k] if l < self.n_layer - 1 else np.asarray(nd.output, float).reshape(-1)
+
+                if l == 0:
+                    xin = xd[:, torch.as_tensor(nd.input_dim, device=xd.device)]
+                    xin = (xin if z is None else torch.cat((xin, z), 1)).contiguous()
+                    cur[:, :, k] = vpaths.draw_shared(
+                        e, nd.name, e.tensor(nd._X()), e.tensor(np.stack([ys(s) for s in range(S)])), nd.length,
+                        nd.scale[0], nd.nugget[0], xin, m, order, Z, J, omega,
+                        'layer 1, node %d (shared by every imputation)' % (k + 1))
+                    continue
+                xs = prev[:, :, torch.as_tensor(nd.input_dim, device=xd.device)]
+                if z is not None:
+                    xs = torch.cat((xs, z[None].expand(P, M, z.shape[1])), 2)
+
+                def train_in(s, l=l, nd=nd, Xg=Xg):
+                    Xin = self.latents[s][l - 1][:, nd.input_dim]
+                    return e.tensor(np.ascontiguousarray(Xin if Xg is None else np.concatenate((Xin, Xg), 1)))
+
+                W, Y = vpaths.PerGroup(train_in), vpaths.PerGroup(lambda s, ys=ys: e.tensor(ys(s)))
+                cur[:, :, k] = vpaths.draw_per_path(
+                    e, nd.name, W, Y, nd.length, nd.scale[0], nd.nugget[0], xs.contiguous(), m, order, Z,
+                    group=np.repeat(np.arange(S), J), omega=omega,
+                    where=lambda p, l=l, k=k: 'layer %d, node %d, imputation %d' % (l + 1, k + 1, p // J + 1))
+            cur_np = cur.cpu().numpy()
+            for k, nd in enumerate(layer):
+                if nd.type != 'gp':
+                    for j in range(P):
+                        cur_np[j, :, k] = nd.sampling(prev_np[j][:, nd.input_dim])
+            out.append(cur_np)
+            prev, prev_np = cur, cur_np
+        out = [list(a.transpose(2, 1, 0)) for a in out]
+        return out if full_layer else out[-1]
+
     def _joint_stats(self, l, k):
         """sample_paths' statistics of GP node k of layer l, built when first asked for beside predict's: L^-1 of the
         training correlation matrix (not the Matern cell reordering of the linked predictor: a permuted L^-1 is not

@@ -699,6 +699,29 @@ class Engine:
                                                                    _dp(sched)))
         return out
 
+    def vpaths_nn(self, q, x, m, group=None):
+        """Conditioning sets of Vecchia sample paths (dgpamd_vpaths_nn): q (P, M, D) the paths' scaled test rows in their
+        order, x (G, n, D) scaled training sets, group None or int32 device (P,).  Returns (P, M, m) int64 combined indices."""
+        P, M, D = q.shape
+        n = x.shape[-2]
+        out = self.empty(P, M, m, dtype=torch.int64)
+        self._chk(self._enter() or lib.dgpamd_vpaths_nn(self.h, P, M, n, D, int(m), _dp(q), _dp(x), _dp(group), _dp(out)))
+        return out
+
+    def vpaths_rows(self, kind, q, x, NN, y, scale, nugget, omega=None, group=None, jitter=0.0):
+        """Rows of the Vecchia sample-path substitution (dgpamd_vpaths_rows): q (P, M, D), x (G, n, D) scaled as for
+        vpaths_nn, NN its result, y (G, nrhs, n) right-hand sides.  Returns Lrows (P, M, m+1), NNl (P, M, m+1), t (P, nrhs, M),
+        sd (P, M) and the device info word."""
+        P, M, D = q.shape
+        n, m, nrhs = x.shape[-2], NN.shape[2], y.shape[-2]
+        Lrows, t, sd = self.empty(P, M, m + 1), self.empty(P, nrhs, M), self.empty(P, M)
+        NNl = self.empty(P, M, m + 1, dtype=torch.int64)
+        info = self.empty(1, dtype=torch.int32)
+        self._chk(self._enter() or lib.dgpamd_vpaths_rows(self.h, KIND[kind], P, M, n, D, m, nrhs, _dp(q), _dp(x), _dp(group), _dp(NN),
+                                                          _dp(omega), _dp(y), float(scale), float(nugget), float(jitter), _dp(Lrows),
+                                                          _dp(NNl), _dp(t), _dp(sd), _dp(info)))
+        return Lrows, NNl, t, sd, info
+
     def vecchia_gp(self, kind, x, w, NN, y, scale, length, nugget, nugget_diag):
         M, D = x.shape
         length = _f64(length)

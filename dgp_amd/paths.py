@@ -3,8 +3,8 @@
 A node with training inputs W (global columns appended), outputs y and R = L L^T has at test inputs X* the joint posterior
     mu = K(X*,W) R^-1 y = V^T w,   Sigma = scale (K(X*,X*) + nugget I - V^T V),   V = L^-1 K(W,X*),  w = L^-1 y.
 The statistics are L^-1 (what dgpamd_potri leaves in the factored buffer); dgpamd_joint_cov forms V, Sigma and mu,
-dgpamd_potrf factors Sigma and dgpamd_mvn_paths draws mu + chol(Sigma) e.  Dense nodes only: a joint draw of a Vecchia
-node needs a sparse algorithm of its own.
+dgpamd_potrf factors Sigma and dgpamd_mvn_paths draws mu + chol(Sigma) e.  Dense nodes only: Vecchia nodes, and more
+than MAX_POINTS rows, are drawn by the sparse algorithm of vpaths.py (sample_paths_vecchia).
 """
 import warnings
 

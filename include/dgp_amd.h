@@ -504,6 +504,28 @@ int dgpamd_vecchia_linkgp(dgpamd_ctx *ctx, int kind, int64_t M, int64_t n, int D
                           const int64_t *NN, const double *y, double scale, const double *length_h, int nlen,
                           double nugget, const double *nugget_diag, double *mean, double *var);
 
+/* ---- Vecchia joint sample paths (DESIGN I.11) --------------------------------------
+ * One GP node, M test rows per path in one order pi.  Position i conditions on c(i): the min(m, n + i) nearest of the n
+ * training rows and the path's test rows at positions < i, squared-euclidean on coordinates already divided by the
+ * lengthscales, in (distance, combined index) order -- combined index j < n: training row j; n + i': test position i'.
+ * dgpamd_vpaths_nn: q (P x M x D) the paths' test rows in order pi; x (G x n x D) training sets; group (device int32, P,
+ * or NULL: all 0) picks each path's set.  NN (P x M x m): c(i) nearest first, -1 padded.  m <= 256.
+ * dgpamd_vpaths_rows: with A the correlation block over c(i) (diagonal 1 + jitter + nugget * omega_j on training members,
+ * omega NULL: 1; 1 + jitter + nugget on test members), a = k(c(i), u_i), b_i = A^-1 a, d_i = scale (1 + jitter + nugget -
+ * a^T b_i), the draw  v_i = sum_train b_ij y_j + sum_test b_ij v_j + sqrt(d_i) z_i  is emitted in dgpamd_vecchia_spsolve's
+ * layout (unit scale): Lrows / NNl (P x M x (m+1)) = [1/sqrt(d_i), -b_ij/sqrt(d_i) over c(i)'s TEST members in list order,
+ * 0..] / [i, their test positions, -1..]; t (P x nrhs x M) = sum over training members of b_ij y[group][r][j] for the nrhs
+ * right-hand sides y (G x nrhs x n); sd (P x M) = sqrt(d_i).  The substitution with b = z + t / sd (dgpamd_vecchia_levels,
+ * dgpamd_vecchia_spsolve_levels) then gives v.  info (device int32): 0, or 1 + some p*M + i whose block is not positive
+ * definite.  m <= 51 with D <= 16 runs register-resident; otherwise one wave per row with the block in LDS, and a block
+ * over a CU's 160 KiB returns DGPAMD_BAD_ARG before anything is launched.  DGPAMD_VECCHIA_LDS=1 forces the LDS kernel. */
+int dgpamd_vpaths_nn(dgpamd_ctx *ctx, int64_t P, int64_t M, int64_t n, int D, int m, const double *q, const double *x,
+                     const int32_t *group, int64_t *NN);
+int dgpamd_vpaths_rows(dgpamd_ctx *ctx, int kind, int64_t P, int64_t M, int64_t n, int D, int m, int nrhs, const double *q,
+                       const double *x, const int32_t *group, const int64_t *NN, const double *omega, const double *y,
+                       double scale, double nugget, double jitter, double *Lrows, int64_t *NNl, double *t, double *sd,
+                       int32_t *info);
+
 #ifdef __cplusplus
 }
 #endif
