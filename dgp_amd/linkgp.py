@@ -1,10 +1,10 @@
 """Linked (D)GP emulation of a feed-forward system of emulators -- mirror of dgpsi.container / dgpsi.lgp
-(linkgp.py:12-608), mean/variance prediction; joint sample paths of the system (lgp.sample_paths, over paths.py).  Pure orchestration over kernel.gp_prediction /
-linkgp_prediction / linkgp_prediction_full; aggregation over imputations as emulation.py:846-847."""
+(linkgp.py:12-608), mean/variance prediction; joint sample paths of the system (lgp.sample_paths over paths.py,
+lgp.sample_paths_vecchia over vpaths.py).  Pure orchestration over kernel.gp_prediction / linkgp_prediction /
+linkgp_prediction_full; aggregation over imputations as emulation.py:846-847."""
 import collections
 import contextlib
 import copy
-import hashlib
 
 import numpy as np
 import torch
@@ -93,8 +93,10 @@ class _By:
 
 class lgp:
     """all_layer: list of layers of containers; N imputations (1 if the system has GP emulators only)  (linkgp.py:140-165).
-    `sample_paths` draws whole functions of the system (dense emulators): column s*sample_size + j is one joint draw over all
-    rows of x, the same path in every emulator and layer."""
+    `sample_paths` draws whole functions of the system (dense emulators, at most 8192 rows): column s*sample_size + j is one
+    joint draw over all rows of x, the same path in every emulator and layer.  `sample_paths_vecchia` draws the same paths
+    from each GP node's m nearest training and earlier-drawn rows: dense and Vecchia-mode emulators in any mixture, any
+    number of rows, cost linear in the rows."""
 
     def __init__(self, all_layer, N=10):
         self.L = len(all_layer)
@@ -312,11 +314,48 @@ class lgp:
                     if c.vecch:
                         raise NotImplementedError('sample_paths needs dense emulators: emulator %d of layer %d is in Vecchia '
                                                   'mode (joint draws of a Vecchia emulator need a sparse algorithm of their '
-                                                  'own; use set_vecchia(False))' % (k + 1, l + 1))
+                                                  'own; use sample_paths_vecchia, or set_vecchia(False))' % (k + 1, l + 1))
         paths.check_points(x[0])
+        J = int(sample_size)
+
+        def draw(e, pos, nodes, xin, where):
+            return self._paths_node(e, pos, nodes, xin, J, where + (' (gp)' if len(pos) == 2 else ''))
+        return self._paths_walk(x, idxs, J, full_layer, draw)
+
+    def sample_paths_vecchia(self, x, sample_size=50, full_layer=False, m=50):
+        """sample_paths by the Vecchia factorisation of every GP node's joint predictive distribution (vpaths, DESIGN I.11):
+        the same walk, container and column layout, for any mixture of dense and Vecchia-mode emulators (the draw never
+        reads the n x n statistics) and any number of rows.  The rows of x are drawn in one order,
+        np.random.permutation(M), taken first and used by every emulator, layer, node and path; every GP node then draws
+        each row given the min(m, n + i) nearest of its n training rows (nd._X() and nd.output: a system's own latents
+        below the first layer of a DGP emulator) and of the same path's rows drawn before it, with one
+        np.random.standard_normal((N, sample_size, M)) block per GP node in walk order, indexed by the rows of x; likelihood
+        nodes sample after the GP nodes of their layer.  A system of one GP container returns gp.sample_paths_vecchia's
+        draws; with m >= n + M - 1 at every node the paths have sample_paths' distribution.  Nodes whose inputs every
+        path shares (layer 1 of the system) take one neighbour search for all paths (vpaths.draw_shared); every other
+        node draws all systems in one call per chunk of paths (vpaths.draw_per_path), split only where the systems' nodes
+        differ in kernel, hyper-parameters, training-set shape or replicate weights.  Nothing is kept across calls.
+        m < 1 raises ValueError; a conditioning block that does not factor is retried with a jitter, then raises
+        numpy.linalg.LinAlgError naming layer, emulator, node and system."""
+        from . import vpaths
+        x = self._global_inputs(x)
+        idxs = [[self._feeding(c, l) for c in layer] for l, layer in enumerate(self.all_layer)]
+        vpaths.check_args(x[0], m)
+        J = int(sample_size)
+        order = np.random.permutation(len(x[0]))
+
+        def draw(e, pos, nodes, xin, where):
+            return self._vpaths_node(e, nodes, xin, J, where, m, order)
+        return self._paths_walk(x, idxs, J, full_layer, draw)
+
+    def _paths_walk(self, x, idxs, J, full_layer, draw):
+        """The walk of sample_paths and sample_paths_vecchia: layer by layer and emulator by emulator, every path fed its
+        own draws of the emulators before it.  draw(e, pos, nodes, xin, where) -> (S*J, M) draws one GP node over all
+        systems (pos its place: (l, k) for a GP emulator, (l, k, il, j) inside a DGP emulator; nodes[s] system s's node; xin
+        (M, D) shared by every path or (S*J, M, D)) and takes the node's normals from numpy's global generator."""
         sets = self.all_layer_set
         e = next(c.structure.engine if c.type == 'gp' else c.structure[0][0].engine for c in sets[0][0])
-        M, S, J = len(x[0]), len(sets), int(sample_size)
+        M = len(x[0])
         feed, out = [], []
         for l in range(self.L):
             outs = []
@@ -331,19 +370,18 @@ class lgp:
                 where = 'layer %d, emulator %d' % (l + 1, k + 1)
                 if models[0].type == 'gp':
                     xin = m if z is None else torch.cat((m, z[None].expand(m.shape[0], M, z.shape[1])), 2)
-                    cur = self._paths_node(e, (l, k), [c.structure for c in models], xin.contiguous(), J,
-                                           where + ' (gp)')[:, :, None]
+                    cur = draw(e, (l, k), [c.structure for c in models], xin.contiguous(), where)[:, :, None]
                 else:
-                    cur = self._paths_dgp(e, l, k, [c.structure for c in models], m, z, J)
+                    cur = self._paths_dgp(e, l, k, [c.structure for c in models], m, z, J, draw)
                 outs.append(cur)
             feed.append(torch.cat(outs, 2))
             if full_layer or l == self.L - 1:
-                out.append([np.ascontiguousarray(c.cpu().numpy().transpose(2, 1, 0)) for c in outs])
+                out.append([c.permute(2, 1, 0).contiguous().cpu().numpy() for c in outs])
         return out if full_layer else out[-1]
 
-    def _paths_dgp(self, e, l, k, structs, m, z, J):
+    def _paths_dgp(self, e, l, k, structs, m, z, J, draw):
         """Paths (S*J, M, q) of DGP emulator k of layer l: structs[s] is system s's structure; m its input, (M, D) shared
-        by every path (l == 0) or (S*J, M, D); z the external input x[l][k] (M, Dz) or None."""
+        by every path (l == 0) or (S*J, M, D); z the external input x[l][k] (M, Dz) or None; draw as in _paths_walk."""
         S, L = len(structs), len(structs[0])
         P, M = S * J, m.shape[-2]
         internal, external = structs[0][0][0].input_dim, structs[0][0][0].connect
@@ -381,7 +419,7 @@ class lgp:
                             parts.append(per_path(z[:, torch.as_tensor(i2, device=e.device)]))
                     xin = torch.cat(parts, 2)
                 where = 'layer %d, emulator %d, node %d of its layer %d' % (l + 1, k + 1, j + 1, il + 1)
-                cur[:, :, j] = self._paths_node(e, (l, k, il, j), [st[il][j] for st in structs], xin.contiguous(), J, where)
+                cur[:, :, j] = draw(e, (l, k, il, j), [st[il][j] for st in structs], xin.contiguous(), where)
             if any(nd.type != 'gp' for nd in layer):   # likelihood nodes sample y from the path's latents
                 cur_np, lat = cur.cpu().numpy(), prev.cpu().numpy()
                 for j, nd in enumerate(layer):
@@ -432,6 +470,87 @@ class lgp:
             out[torch.as_tensor(ss, device=e.device)] = o.reshape(len(ss), J, M)
         return out.reshape(P, M)
 
+    @staticmethod
+    def _node_classes(nodes):
+        """One GP node position over the systems, compared by content: cls[s] the index of system s's training set among
+        the distinct ones (inputs, global inputs, replicate weights, lengths, nugget), first[c] the first system of set c,
+        call[s] what one device call holds fixed (kernel, lengths, scale, nugget, training-set shape)."""
+        cls, call, first, held, seen = [], [], [], [], {}
+        for s, nd in enumerate(nodes):
+            X, Xg = peek(nd, 'input'), peek(nd, 'global_input')
+            big = [None if a is None else np.asarray(a, dtype=float) for a in (X, Xg, None if nd.rep is None else nd.W_diag)]
+            length = np.asarray(nd.length, float).tobytes()
+            # (shapes and sums only pick the candidates; equality of every element decides)
+            key = (nd.name, length, np.asarray(nd.nugget, float).tobytes()) + \
+                tuple(None if a is None else (a.shape, float(a.sum())) for a in big)
+            for c in seen.setdefault(key, []):
+                if all(a is None or np.array_equal(a, b) for a, b in zip(big, held[c])):
+                    break
+            else:
+                c = len(first)
+                seen[key].append(c)
+                first.append(s)
+                held.append(big)
+            cls.append(c)
+            call.append((nd.name, length, float(nd.scale[0]), float(nd.nugget[0]),
+                         (np.shape(X)[0], np.shape(X)[1] + (0 if Xg is None else np.shape(Xg)[1]))))
+        return cls, call, first
+
+    def _vpaths_node(self, e, nodes, xin, J, where, m, order):
+        """_paths_node for sample_paths_vecchia: paths (S*J, M) of one GP node over all systems by vpaths, rows in the order
+        `order`, conditioning sets of size m.  Draws this node's (S, J, M) block of normals.  Systems that one device call
+        can hold (_node_classes' call, and equal replicate weights) draw together: shared inputs through
+        vpaths.draw_shared per distinct training set, the systems' outputs as the rows of Y; else through
+        vpaths.draw_per_path with the system as each path's group -- no group when the systems share training inputs and
+        outputs by content (the copies of a GP emulator); per-system tensors are made chunk by chunk (vpaths.PerGroup)."""
+        from . import vpaths
+        S, M = len(nodes), xin.shape[-2]
+        Z = np.random.standard_normal((S, J, M))
+        cls, call, _ = self._node_classes(nodes)
+        calls = collections.defaultdict(list)
+        for s, nd in enumerate(nodes):
+            calls[(call[s], None if nd.rep is None else np.asarray(nd.W_diag, float).tobytes())].append(s)
+
+        def train_in(s):
+            return e.tensor(np.ascontiguousarray(nodes[s]._X(), dtype=float))
+
+        def train_out(s):
+            return np.asarray(nodes[s].output, dtype=float).reshape(-1)
+
+        draws = []   # (systems, (len(systems)*J, M) paths)
+        for ss in calls.values():
+            nd = nodes[ss[0]]
+            hyper = (nd.length, nd.scale[0], nd.nugget[0])
+            omega = None if nd.rep is None else e.tensor(nd.W_diag)
+            Zs = e.tensor(Z[ss].reshape(len(ss) * J, M))
+            if xin.dim() == 2:
+                by = collections.defaultdict(list)
+                for s in ss:
+                    by[cls[s]].append(s)
+                for cs in by.values():   # (one set of rows serves the systems of cs: an error names the first of them)
+                    Y = e.tensor(np.stack([train_out(s) for s in cs]))
+                    Zc = Zs if len(cs) == len(ss) else e.tensor(Z[cs].reshape(len(cs) * J, M))
+                    draws.append((cs, vpaths.draw_shared(e, nd.name, train_in(cs[0]), Y, *hyper, xin, m, order, Zc, J, omega,
+                                                         '%s, system %d' % (where, cs[0] + 1))))
+                continue
+            xs = xin if len(ss) == S else xin.view(S, J, M, -1)[torch.as_tensor(ss, device=e.device)].reshape(-1, M, xin.shape[2])
+            W0 = train_in(ss[0]) if len({cls[s] for s in ss}) == 1 else None
+            if W0 is not None and all(np.array_equal(train_out(ss[0]), train_out(s)) for s in ss[1:]):
+                W, y, group = W0, e.tensor(train_out(ss[0])), None
+            else:
+                W = vpaths.PerGroup(lambda g, ss=ss, W0=W0: train_in(ss[g]) if W0 is None else W0)
+                y = vpaths.PerGroup(lambda g, ss=ss: e.tensor(train_out(ss[g])))
+                group = np.repeat(np.arange(len(ss)), J)
+            draws.append((ss, vpaths.draw_per_path(e, nd.name, W, y, *hyper, xs.contiguous(), m, order, Zs, group=group,
+                                                   omega=omega,
+                                                   where=lambda p, ss=ss: '%s, system %d' % (where, ss[p // J] + 1))))
+        if len(draws) == 1:
+            return draws[0][1].contiguous()
+        out = e.empty(S, J, M)
+        for ss, o in draws:
+            out[torch.as_tensor(ss, device=e.device)] = o.reshape(len(ss), J, M)
+        return out.reshape(S * J, M)
+
     def _node_stats(self, e, pos, nodes, where):
         """sample_paths' statistics of one GP node position over the systems, cached on the lgp (dropped by set_vecchia):
         y per system; L^-1 (paths.factor_inverse) and W per distinct training set -- inputs, replicate weights, lengths and
@@ -446,18 +565,7 @@ class lgp:
             return st
         self.__dict__.setdefault('_per_cache', collections.OrderedDict())
         self.__dict__.setdefault('_per_bytes', 0)
-        cls, call, first, keys = [], [], [], {}
-        for s, nd in enumerate(nodes):
-            h = hashlib.sha1(nd.name.encode())
-            for a in (peek(nd, 'input'), peek(nd, 'global_input'), None if nd.rep is None else nd.W_diag, nd.length,
-                      nd.nugget):
-                h.update(b'-' if a is None else np.ascontiguousarray(a, dtype=float).tobytes() + str(np.shape(a)).encode())
-            c = keys.setdefault(h.digest(), len(keys))
-            if c == len(first):
-                first.append(s)
-            cls.append(c)
-            call.append((nd.name, np.asarray(nd.length, float).tobytes(), float(nd.scale[0]), float(nd.nugget[0]),
-                         np.shape(nd._X())))
+        cls, call, first = self._node_classes(nodes)
 
         def build(c):
             nd, s = nodes[first[c]], first[c]
