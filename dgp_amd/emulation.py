@@ -172,7 +172,6 @@ class emulator:
         e = self.engine
         S = self.N
         stats = {}
-        Yall = np.asarray([np.asarray(nd.output, float).reshape(-1) for nd in self.all_layer[-1]])
         for l, layer in enumerate(self.all_layer):
             for k, nd in enumerate(layer):
                 if nd.type != 'gp':
@@ -182,9 +181,6 @@ class emulator:
                 cap = Np - n
                 Xg = None if peek(nd, 'global_input') is None else e.tensor(peek(nd, 'global_input'))
                 W = None if nd.rep is None else e.tensor(nd.W_diag)
-
-                def ys(s, l=l, k=k):   # (defaults: the closures below are called after this loop has moved on)
-                    return self.latents[s][l][:, k] if l < self.n_layer - 1 else Yall[k]
 
                 def factor(Xl, Y, nd=nd, n=n, Np=Np, Xg=Xg, W=W):
                     A = e.workspace(('emuA', n), Np * Np * 8)
@@ -205,14 +201,14 @@ class emulator:
                     Xl = e.tensor(peek(nd, 'input'))
                     rys, Rinv = [], None
                     for c0 in range(0, S, cap):   # all imputations' y as right-hand sides of ONE factorisation
-                        Y = e.tensor(np.stack([ys(s) for s in range(c0, min(S, c0 + cap))]))
+                        Y = e.tensor(np.stack([self._ys(s, l, k) for s in range(c0, min(S, c0 + cap))]))
                         Rinv, ry = factor(Xl, Y)
                         rys.append(ry)
                     stats[(l, k)] = dict(shared=True, Rinv=Rinv, ld=Np, ry=torch.cat(rys), n=n, Wall=e.tensor(nd._X()))
                 else:
-                    def build(s, l=l, nd=nd, factor=factor, ys=ys, Xg=Xg):
-                        Xin = self.latents[s][l - 1][:, nd.input_dim]
-                        Rinv, ry = factor(e.tensor(Xin), e.tensor(ys(s)[None, :]))
+                    def build(s, l=l, k=k, nd=nd, factor=factor, Xg=Xg):   # (defaults: called after this loop has moved on)
+                        Xin = self._train_in(s, l, nd)
+                        Rinv, ry = factor(e.tensor(Xin), e.tensor(self._ys(s, l, k)[None, :]))
                         cells = e.linkgp_cells(nd.name, Xin, Xg, Rinv, ry[0])   # (Matern: training points grouped by cells)
                         return cells if cells is not None else dict(Rinv=Rinv, ry=ry[0].contiguous(), W=e.tensor(Xin))
                     stats[(l, k)] = dict(shared=False, per=_LazyPer(self, (l, k), build, Np * Np * 8), ld=Np, n=n, Wg=Xg)
@@ -480,48 +476,20 @@ class emulator:
             raise NotImplementedError("sample_paths with the imputations sharded over ranks would return partial draws; use "
                                       "emulator(..., shard=False)")
         paths.check_points(x)
-        e = self.engine
+        e, rng, drawer = self.engine, self._sample_rng, paths.Dense()
         M, S, J = len(x), self.N, int(sample_size)
-        P = S * J
-        xd = e.tensor(x)
-        rng = self._sample_rng
-        cat = self._cat()
-        out, prev, prev_np = [], None, None
-        for l, layer in enumerate(self.all_layer):
-            if l == self.n_layer - 1 and cat is not None:   # class probabilities at the paths' latents (as _draw_samples)
-                out.append(np.stack([cat.sampling(prev_np[j][:, cat.input_dim]) for j in range(P)]))
-                continue
-            cur = e.empty(P, M, len(layer))
-            for k, nd in enumerate(layer):
-                if nd.type != 'gp':
-                    continue
-                Z = rng.standard_normal((S, J, M))
-                st = self._joint_stats(l, k)
-                z = None if nd.connect is None else xd[:, torch.as_tensor(nd.connect, device=xd.device)]
-                if l == 0:
-                    xin = xd[:, torch.as_tensor(nd.input_dim, device=xd.device)]
-                    xin = (xin if z is None else torch.cat((xin, z), 1)).contiguous()
-                    E = e.tensor(np.ascontiguousarray(Z.transpose(2, 0, 1).reshape(M, P)))
-                    cur[:, :, k] = paths.draw_shared(e, nd.name, xin, st['W'], st['Linv'], st['Y'], nd.length, nd.scale[0],
-                                                     nd.nugget[0], E, J).T
-                    continue
-                idx = torch.as_tensor(nd.input_dim, device=xd.device)
-                for s in range(S):
-                    ps = st['per'][s]
-                    xs = prev[s * J:(s + 1) * J][:, :, idx]
-                    if z is not None:
-                        xs = torch.cat((xs, z[None].expand(J, M, z.shape[1])), 2)
-                    cur[s * J:(s + 1) * J, :, k] = paths.draw_per_path(e, nd.name, xs.contiguous(), ps['W'], ps['Linv'], ps['y'],
-                                                                        nd.length, nd.scale[0], nd.nugget[0], e.tensor(Z[s]))
-            cur_np = cur.cpu().numpy()
-            for k, nd in enumerate(layer):
-                if nd.type != 'gp':   # likelihood nodes sample y from the path's latents (emulation.py:785-822)
-                    for j in range(P):
-                        cur_np[j, :, k] = nd.sampling(prev_np[j][:, nd.input_dim])
-            out.append(cur_np)
-            prev, prev_np = cur, cur_np
-        out = [list(a.transpose(2, 1, 0)) for a in out]
-        return out if full_layer else out[-1]
+
+        def draw(l, k, nd, xin):
+            Z = e.tensor(rng.standard_normal((S, J, M)).reshape(S * J, M))
+            st = self._joint_stats(l, k)
+            if l == 0:
+                return drawer.draw_shared(e, paths.hyper(nd), xin, (st['W'], st['Linv']), st['Y'], Z, J)
+            out = e.empty(S * J, M)
+            for s in range(S):   # (one call per imputation: its L^-1 is passed as it lies; a grouped call stacks copies)
+                ps, mine = st['per'][s], slice(s * J, (s + 1) * J)
+                out[mine] = drawer.draw_per_path(e, paths.hyper(nd), xin[mine], (ps['W'], ps['Linv']), ps['y'], Z[mine])
+            return out
+        return self._walk_paths(x, J, full_layer, draw)
 
     def sample_paths_vecchia(self, x, sample_size=50, full_layer=False, m=50):
         """sample_paths by the Vecchia factorisation of each node's joint predictive distribution (vpaths, DESIGN I.11):
@@ -531,65 +499,55 @@ class emulator:
         path, with one standard_normal((N, sample_size, M)) block per GP node as sample_paths.  With m >= n + M - 1 this is
         sample_paths' dense joint.  A conditioning block that does not factor is retried with a jitter, then raises
         numpy.linalg.LinAlgError naming its layer, node and imputation."""
-        from . import vpaths
+        from . import paths, vpaths
         if self.shard or getattr(self, 'shard_points', False):
             raise NotImplementedError("sample_paths_vecchia with the imputations sharded over ranks would return partial "
                                       "draws; use emulator(..., shard=False)")
         vpaths.check_args(x, m)
-        e = self.engine
+        e, rng = self.engine, self._sample_rng
         M, S, J = len(x), self.N, int(sample_size)
-        P = S * J
-        rng = self._sample_rng
-        order = rng.permutation(M)
+        drawer = vpaths.Vecchia(m, rng.permutation(M))
+
+        def draw(l, k, nd, xin):
+            Z = e.tensor(rng.standard_normal((S, J, M)).reshape(S * J, M))
+            omega = None if nd.rep is None else e.tensor(nd.W_diag)
+            if l == 0:
+                return drawer.draw_shared(e, paths.hyper(nd), xin, (e.tensor(nd._X()), omega),
+                                          e.tensor(np.stack([self._ys(s, l, k) for s in range(S)])), Z, J,
+                                          'layer 1, node %d (shared by every imputation)' % (k + 1))
+            train = paths.PerGroup(lambda s: (e.tensor(self._train_in(s, l, nd, True)), omega))
+            return drawer.draw_per_path(e, paths.hyper(nd), xin, train, paths.PerGroup(lambda s: e.tensor(self._ys(s, l, k))), Z,
+                                        np.repeat(np.arange(S), J),
+                                        lambda p: 'layer %d, node %d, imputation %d' % (l + 1, k + 1, p // J + 1))
+        return self._walk_paths(x, J, full_layer, draw)
+
+    def _walk_paths(self, x, J, full_layer, draw):
+        """sample_paths' and sample_paths_vecchia's walk (pathwalk.walk over all_layer, the same structure for every
+        imputation) and their container.  draw(l, k, nd, xin) -> (N*J, M) draws GP node k of layer l at xin, (M, D) in the
+        first layer and (N*J, M, D) below it, and takes the node's normals from the generator."""
+        from . import pathwalk
+        e = self.engine
         xd = e.tensor(x)
-        cat = self._cat()
-        out, prev, prev_np = [], None, None
-        for l, layer in enumerate(self.all_layer):
-            if l == self.n_layer - 1 and cat is not None:
-                out.append(np.stack([cat.sampling(prev_np[j][:, cat.input_dim]) for j in range(P)]))
-                continue
-            cur = e.empty(P, M, len(layer))
-            for k, nd in enumerate(layer):
-                if nd.type != 'gp':
-                    continue
-                Z = e.tensor(rng.standard_normal((S, J, M)).reshape(P, M))
-                Xg = peek(nd, 'global_input')
-                omega = None if nd.rep is None else e.tensor(nd.W_diag)
-                z = None if nd.connect is None else xd[:, torch.as_tensor(nd.connect, device=xd.device)]
 
-                def ys(s, l=l, k=k, nd=nd):
-                    return self.latents[s][l][:, k] if l < self.n_layer - 1 else np.asarray(nd.output, float).reshape(-1)
+        def first(nd):
+            xin = pathwalk.cols(xd, nd.input_dim)
+            return xin if nd.connect is None else torch.cat((xin, pathwalk.cols(xd, nd.connect)), 1)
 
-                if l == 0:
-                    xin = xd[:, torch.as_tensor(nd.input_dim, device=xd.device)]
-                    xin = (xin if z is None else torch.cat((xin, z), 1)).contiguous()
-                    cur[:, :, k] = vpaths.draw_shared(
-                        e, nd.name, e.tensor(nd._X()), e.tensor(np.stack([ys(s) for s in range(S)])), nd.length,
-                        nd.scale[0], nd.nugget[0], xin, m, order, Z, J, omega,
-                        'layer 1, node %d (shared by every imputation)' % (k + 1))
-                    continue
-                xs = prev[:, :, torch.as_tensor(nd.input_dim, device=xd.device)]
-                if z is not None:
-                    xs = torch.cat((xs, z[None].expand(P, M, z.shape[1])), 2)
-
-                def train_in(s, l=l, nd=nd, Xg=Xg):
-                    Xin = self.latents[s][l - 1][:, nd.input_dim]
-                    return e.tensor(np.ascontiguousarray(Xin if Xg is None else np.concatenate((Xin, Xg), 1)))
-
-                W, Y = vpaths.PerGroup(train_in), vpaths.PerGroup(lambda s, ys=ys: e.tensor(ys(s)))
-                cur[:, :, k] = vpaths.draw_per_path(
-                    e, nd.name, W, Y, nd.length, nd.scale[0], nd.nugget[0], xs.contiguous(), m, order, Z,
-                    group=np.repeat(np.arange(S), J), omega=omega,
-                    where=lambda p, l=l, k=k: 'layer %d, node %d, imputation %d' % (l + 1, k + 1, p // J + 1))
-            cur_np = cur.cpu().numpy()
-            for k, nd in enumerate(layer):
-                if nd.type != 'gp':
-                    for j in range(P):
-                        cur_np[j, :, k] = nd.sampling(prev_np[j][:, nd.input_dim])
-            out.append(cur_np)
-            prev, prev_np = cur, cur_np
+        out = [cur.cpu().numpy() for cur in pathwalk.walk(e, [self.all_layer] * self.N, J, xd, None, first,
+                                                           lambda l, k, nodes, xin: draw(l, k, nodes[0], xin))]
         out = [list(a.transpose(2, 1, 0)) for a in out]
         return out if full_layer else out[-1]
+
+    def _ys(self, s, l, k):
+        """The training outputs of node k of layer l in imputation s: its latents, or the node's output in the last layer."""
+        return self.latents[s][l][:, k] if l < self.n_layer - 1 else np.asarray(self.all_layer[l][k].output, float).reshape(-1)
+
+    def _train_in(self, s, l, nd, with_global=False):
+        """The training inputs of node nd of layer l > 0 in imputation s (host): its input_dim columns of the latents below,
+        with_global followed by the node's global columns."""
+        Xin = self.latents[s][l - 1][:, nd.input_dim]
+        Xg = peek(nd, 'global_input') if with_global else None
+        return Xin if Xg is None else np.concatenate((Xin, Xg), 1)
 
     def _joint_stats(self, l, k):
         """sample_paths' statistics of GP node k of layer l, built when first asked for beside predict's: L^-1 of the
@@ -605,24 +563,17 @@ class emulator:
             return st
         e = self.engine
         nd = self.all_layer[l][k]
-        Xg_h = peek(nd, 'global_input')
-        Xg = None if Xg_h is None else e.tensor(Xg_h)
+        Xg = None if peek(nd, 'global_input') is None else e.tensor(peek(nd, 'global_input'))
         W = None if nd.rep is None else e.tensor(nd.W_diag)
-
-        def ys(s):
-            return self.latents[s][l][:, k] if l < self.n_layer - 1 else np.asarray(nd.output, float).reshape(-1)
-
         if l == 0:
             Linv = paths.factor_inverse(e, nd.name, e.tensor(peek(nd, 'input')), Xg, W, nd.length, nd.nugget[0],
                                         'layer 1, node %d (shared by every imputation)' % (k + 1))
-            st = dict(Linv=Linv, W=e.tensor(nd._X()), Y=e.tensor(np.stack([ys(s) for s in range(self.N)])))
+            st = dict(Linv=Linv, W=e.tensor(nd._X()), Y=e.tensor(np.stack([self._ys(s, l, k) for s in range(self.N)])))
         else:
             def build(s):
-                Xin = self.latents[s][l - 1][:, nd.input_dim]
-                Linv = paths.factor_inverse(e, nd.name, e.tensor(Xin), Xg, W, nd.length, nd.nugget[0],
+                Linv = paths.factor_inverse(e, nd.name, e.tensor(self._train_in(s, l, nd)), Xg, W, nd.length, nd.nugget[0],
                                             'layer %d, node %d, imputation %d' % (l + 1, k + 1, s + 1))
-                Wall = Xin if Xg_h is None else np.concatenate((Xin, Xg_h), 1)
-                return dict(Linv=Linv, W=e.tensor(np.ascontiguousarray(Wall)), y=e.tensor(ys(s)))
+                return dict(Linv=Linv, W=e.tensor(self._train_in(s, l, nd, True)), y=e.tensor(self._ys(s, l, k)))
             Np = e.padded_dim(len(nd.output))
             st = dict(per=_LazyPer(self, key, build, Np * Np * 8))
         self._stats[key] = st

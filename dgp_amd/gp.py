@@ -198,9 +198,8 @@ class gp:
         xin = x[:, k.input_dim] if k.connect is None else np.concatenate((x[:, k.input_dim], x[:, k.connect]), 1)
         Z = np.random.standard_normal((sample_size, len(x)))
         y = e.tensor(np.asarray(k.output, float).reshape(1, -1))
-        out = paths.draw_shared(e, k.name, e.tensor(xin), st['Wall'], st['joint'], y, k.length, k.scale[0], k.nugget[0],
-                                e.tensor(np.ascontiguousarray(Z.T)), sample_size)
-        return out.cpu().numpy()
+        out = paths.Dense().draw_shared(e, paths.hyper(k), e.tensor(xin), (st['Wall'], st['joint']), y, e.tensor(Z), sample_size)
+        return out.T.cpu().numpy()
 
     def sample_paths_vecchia(self, x, sample_size=50, m=50):
         """Joint posterior draws of the GP at the rows of x by the Vecchia factorisation of the joint predictive distribution
@@ -208,17 +207,16 @@ class gp:
         order np.random.permutation(M), each conditioned on its m nearest training rows and earlier-drawn test rows; the
         normals are np.random.standard_normal((sample_size, M)), indexed by x's rows.  With m >= n + M - 1 this is the
         dense joint draw."""
-        from . import vpaths
+        from . import paths, vpaths
         vpaths.check_args(x, m)
         k = self.kernel
         e = k.engine
         M = len(x)
-        order = np.random.permutation(M)
+        drawer = vpaths.Vecchia(m, np.random.permutation(M))
         Z = np.random.standard_normal((sample_size, M))
         xin = x[:, k.input_dim] if k.connect is None else np.concatenate((x[:, k.input_dim], x[:, k.connect]), 1)
-        out = vpaths.draw_shared(e, k.name, e.tensor(k._X()), e.tensor(np.asarray(k.output, float).reshape(1, -1)), k.length,
-                                 k.scale[0], k.nugget[0], e.tensor(xin), m, order, e.tensor(Z), sample_size,
-                                 None if k.rep is None else e.tensor(k.W_diag), 'the gp model')
+        out = drawer.draw_shared(e, paths.hyper(k), e.tensor(xin), (e.tensor(k._X()), None if k.rep is None else e.tensor(k.W_diag)),
+                                 e.tensor(np.asarray(k.output, float).reshape(1, -1)), e.tensor(Z), sample_size, 'the gp model')
         return out.cpu().numpy().T
 
     def ppredict(self, x, method='mean_var', sample_size=50, m=50, chunk_num=None, core_num=None):

@@ -1,7 +1,8 @@
 """Linked (D)GP emulation of a feed-forward system of emulators -- mirror of dgpsi.container / dgpsi.lgp
-(linkgp.py:12-608), mean/variance prediction; joint sample paths of the system (lgp.sample_paths over paths.py,
-lgp.sample_paths_vecchia over vpaths.py).  Pure orchestration over kernel.gp_prediction / linkgp_prediction /
-linkgp_prediction_full; aggregation over imputations as emulation.py:846-847."""
+(linkgp.py:12-608), mean/variance prediction; joint sample paths of the system (lgp.sample_paths with the drawer
+paths.Dense, lgp.sample_paths_vecchia with vpaths.Vecchia; DGP emulators walked by pathwalk.walk).  Pure orchestration
+over kernel.gp_prediction / linkgp_prediction / linkgp_prediction_full; aggregation over imputations as
+emulation.py:846-847."""
 import collections
 import contextlib
 import copy
@@ -9,6 +10,7 @@ import copy
 import numpy as np
 import torch
 
+from . import paths, pathwalk
 from .imputation import imputer
 from .kernel_class import peek
 
@@ -81,14 +83,62 @@ def _ensure_stats(nd):
         nd.compute_stats()
 
 
-class _By:
-    """Indexable view: item i is f(i) (paths.draw_per_path reads its groups' statistics through it)."""
+class _DenseTrain:
+    """The training side of one GP node position for paths.Dense: lgp._node_stats' cached L^-1, W and y.  classes():
+    cls[s] system s's training set among the distinct ones, call[s] what one device call holds fixed; shared(cs): (train, Y)
+    of the systems cs, which share one training set; per_path(ss, J): (train, y, group) of the systems ss, J paths each."""
 
-    def __init__(self, f):
-        self.f = f
+    def __init__(self, sysm, e, pos, nodes, where):
+        self.stats = lambda: sysm._node_stats(e, pos, nodes, where)
 
-    def __getitem__(self, i):
-        return self.f(i)
+    def classes(self):
+        self.st = self.stats()
+        return self.st['cls'], self.st['call']
+
+    def _of(self, s):
+        ps = self.st['per'][self.st['cls'][s]]
+        return ps['W'], ps['Linv']
+
+    def shared(self, cs):
+        return self._of(cs[0]), torch.stack([self.st['y'][s] for s in cs])
+
+    def per_path(self, ss, J):
+        return (paths.PerGroup(lambda i: self._of(ss[i])), paths.PerGroup(lambda i: self.st['y'][ss[i]]),
+                np.repeat(np.arange(len(ss)), J))
+
+
+class _VecchiaTrain:
+    """The same for vpaths.Vecchia: nothing cached, tensors made when a chunk asks for them.  One call also holds one set of
+    replicate weights (omega); systems that share training inputs and outputs by content (the copies of a GP emulator)
+    need no group."""
+
+    def __init__(self, e, nodes):
+        self.e, self.nodes = e, nodes
+
+    def classes(self):
+        self.cls, call, _ = lgp._node_classes(self.nodes)
+        return self.cls, [(c, None if nd.rep is None else np.asarray(nd.W_diag, float).tobytes())
+                          for c, nd in zip(call, self.nodes)]
+
+    def _in(self, s):
+        return self.e.tensor(np.ascontiguousarray(self.nodes[s]._X(), dtype=float))
+
+    def _out(self, s):
+        return np.asarray(self.nodes[s].output, dtype=float).reshape(-1)
+
+    def _omega(self, s):
+        return None if self.nodes[s].rep is None else self.e.tensor(self.nodes[s].W_diag)
+
+    def shared(self, cs):
+        return (self._in(cs[0]), self._omega(cs[0])), self.e.tensor(np.stack([self._out(s) for s in cs]))
+
+    def per_path(self, ss, J):
+        omega = self._omega(ss[0])
+        W0 = self._in(ss[0]) if len({self.cls[s] for s in ss}) == 1 else None
+        if W0 is not None and all(np.array_equal(self._out(ss[0]), self._out(s)) for s in ss[1:]):
+            return (W0, omega), self.e.tensor(self._out(ss[0])), None
+        return (paths.PerGroup(lambda g: (self._in(ss[g]) if W0 is None else W0, omega)),
+                paths.PerGroup(lambda g: self.e.tensor(self._out(ss[g]))), np.repeat(np.arange(len(ss)), J))
 
 
 class lgp:
@@ -171,12 +221,7 @@ class lgp:
                     mo[:, k], vo[:, k] = nd.linkgp_prediction(m=mk, v=vk, z=x[:, nd.connect])
                 else:
                     # the node's global inputs are themselves uncertain (outputs of feeding emulators) and/or external
-                    if l == L - 1:
-                        i1 = np.where(nd.connect[:, None] == internal[None, :])[1]
-                        i2 = np.array([], dtype=int) if external is None else np.where(nd.connect[:, None] == external[None, :])[1]
-                    else:
-                        D = m.shape[1]
-                        i1, i2 = nd.connect[nd.connect <= D - 1], nd.connect[nd.connect > D - 1] - D
+                    i1, i2 = pathwalk.connect_split(nd.connect, l == L - 1, m.shape[1], internal, external)
                     if i1.size == 0:
                         mo[:, k], vo[:, k] = nd.linkgp_prediction(m=mk, v=vk, z=z[:, i2])
                     else:
@@ -305,7 +350,6 @@ class lgp:
         np.random.standard_normal((N, sample_size, M)) block per GP node in that walk order; likelihood nodes sample after
         the GP nodes of their layer.  At most 8192 rows (ValueError); a Vecchia emulator raises NotImplementedError and a
         training correlation matrix that is not positive definite numpy.linalg.LinAlgError, naming where."""
-        from . import paths
         x = self._global_inputs(x)
         idxs = [[self._feeding(c, l) for c in layer] for l, layer in enumerate(self.all_layer)]
         for system in [self.all_layer] + list(self.all_layer_set):
@@ -319,7 +363,8 @@ class lgp:
         J = int(sample_size)
 
         def draw(e, pos, nodes, xin, where):
-            return self._paths_node(e, pos, nodes, xin, J, where + (' (gp)' if len(pos) == 2 else ''))
+            where += ' (gp)' if len(pos) == 2 else ''
+            return self._paths_node(e, nodes, xin, J, paths.Dense(), _DenseTrain(self, e, pos, nodes, where), where)
         return self._paths_walk(x, idxs, J, full_layer, draw)
 
     def sample_paths_vecchia(self, x, sample_size=50, full_layer=False, m=50):
@@ -332,8 +377,8 @@ class lgp:
         np.random.standard_normal((N, sample_size, M)) block per GP node in walk order, indexed by the rows of x; likelihood
         nodes sample after the GP nodes of their layer.  A system of one GP container returns gp.sample_paths_vecchia's
         draws; with m >= n + M - 1 at every node the paths have sample_paths' distribution.  Nodes whose inputs every
-        path shares (layer 1 of the system) take one neighbour search for all paths (vpaths.draw_shared); every other
-        node draws all systems in one call per chunk of paths (vpaths.draw_per_path), split only where the systems' nodes
+        path shares (layer 1 of the system) take one neighbour search for all paths (Vecchia.draw_shared); every other
+        node draws all systems in one call per chunk of paths (Vecchia.draw_per_path), split only where the systems' nodes
         differ in kernel, hyper-parameters, training-set shape or replicate weights.  Nothing is kept across calls.
         m < 1 raises ValueError; a conditioning block that does not factor is retried with a jitter, then raises
         numpy.linalg.LinAlgError naming layer, emulator, node and system."""
@@ -342,10 +387,10 @@ class lgp:
         idxs = [[self._feeding(c, l) for c in layer] for l, layer in enumerate(self.all_layer)]
         vpaths.check_args(x[0], m)
         J = int(sample_size)
-        order = np.random.permutation(len(x[0]))
+        drawer = vpaths.Vecchia(m, np.random.permutation(len(x[0])))
 
         def draw(e, pos, nodes, xin, where):
-            return self._vpaths_node(e, nodes, xin, J, where, m, order)
+            return self._paths_node(e, nodes, xin, J, drawer, _VecchiaTrain(e, nodes), where)
         return self._paths_walk(x, idxs, J, full_layer, draw)
 
     def _paths_walk(self, x, idxs, J, full_layer, draw):
@@ -371,104 +416,51 @@ class lgp:
                 if models[0].type == 'gp':
                     xin = m if z is None else torch.cat((m, z[None].expand(m.shape[0], M, z.shape[1])), 2)
                     cur = draw(e, (l, k), [c.structure for c in models], xin.contiguous(), where)[:, :, None]
-                else:
-                    cur = self._paths_dgp(e, l, k, [c.structure for c in models], m, z, J, draw)
+                else:   # (its first layer takes every column of m and z)
+                    xin = m if z is None else torch.cat([pathwalk.per_path(t, len(sets) * J) for t in (m, z)], 2)
+                    for cur in pathwalk.walk(e, [c.structure for c in models], J, m, z, lambda nd: xin,
+                                             lambda il, j, nodes, xi: draw(e, (l, k, il, j), nodes, xi, '%s, node %d of its '
+                                                                           'layer %d' % (where, j + 1, il + 1))):
+                        pass   # (the last layer's paths are the emulator's)
                 outs.append(cur)
             feed.append(torch.cat(outs, 2))
             if full_layer or l == self.L - 1:
                 out.append([c.permute(2, 1, 0).contiguous().cpu().numpy() for c in outs])
         return out if full_layer else out[-1]
 
-    def _paths_dgp(self, e, l, k, structs, m, z, J, draw):
-        """Paths (S*J, M, q) of DGP emulator k of layer l: structs[s] is system s's structure; m its input, (M, D) shared
-        by every path (l == 0) or (S*J, M, D); z the external input x[l][k] (M, Dz) or None; draw as in _paths_walk."""
-        S, L = len(structs), len(structs[0])
-        P, M = S * J, m.shape[-2]
-        internal, external = structs[0][0][0].input_dim, structs[0][0][0].connect
-
-        def per_path(t):
-            return t if t.dim() == 3 else t[None].expand(P, M, t.shape[1])
-
-        prev = None
-        for il, layer in enumerate(structs[0]):
-            if il == L - 1 and len(layer) == 1 and getattr(layer[0], 'name', None) == 'Categorical':
-                cat, lat = layer[0], prev.cpu().numpy()
-                return e.tensor(np.stack([structs[p // J][il][0].sampling(lat[p][:, cat.input_dim]) for p in range(P)])
-                                .reshape(P, M, -1))
-            cur = e.empty(P, M, len(layer))
-            for j, nd in enumerate(layer):
-                if nd.type != 'gp':
-                    continue
-                if il == 0:
-                    xin = m if z is None else torch.cat((per_path(m), per_path(z)), 2)
-                else:
-                    parts = [prev[:, :, torch.as_tensor(nd.input_dim, device=e.device)]]
-                    if nd.connect is not None and l == 0:
-                        parts.append(per_path(m[:, torch.as_tensor(nd.connect, device=e.device)]))
-                    elif nd.connect is not None:   # the global columns: as lgp.dgp_pred
-                        if il == L - 1:
-                            i1 = np.where(nd.connect[:, None] == internal[None, :])[1]
-                            i2 = np.array([], dtype=int) if external is None else \
-                                np.where(nd.connect[:, None] == external[None, :])[1]
-                        else:
-                            D = m.shape[-1]
-                            i1, i2 = nd.connect[nd.connect <= D - 1], nd.connect[nd.connect > D - 1] - D
-                        if i1.size:
-                            parts.append(per_path(m)[:, :, torch.as_tensor(i1, device=e.device)])
-                        if i2.size:
-                            parts.append(per_path(z[:, torch.as_tensor(i2, device=e.device)]))
-                    xin = torch.cat(parts, 2)
-                where = 'layer %d, emulator %d, node %d of its layer %d' % (l + 1, k + 1, j + 1, il + 1)
-                cur[:, :, j] = draw(e, (l, k, il, j), [st[il][j] for st in structs], xin.contiguous(), where)
-            if any(nd.type != 'gp' for nd in layer):   # likelihood nodes sample y from the path's latents
-                cur_np, lat = cur.cpu().numpy(), prev.cpu().numpy()
-                for j, nd in enumerate(layer):
-                    if nd.type != 'gp':
-                        for p in range(P):
-                            cur_np[p, :, j] = structs[p // J][il][j].sampling(lat[p][:, nd.input_dim])
-                cur = e.tensor(cur_np)
-            prev = cur
-        return prev
-
-    def _paths_node(self, e, pos, nodes, xin, J, where):
+    def _paths_node(self, e, nodes, xin, J, drawer, train, where):
         """Paths (S*J, M) of one GP node over all systems: nodes[s] is system s's node, xin its inputs, (M, D) shared by
-        every path or (S*J, M, D).  Draws this node's (S, J, M) block of normals.  Systems whose nodes share kernel and
-        hyper-parameters draw in one call: through paths.draw_shared (one Sigma per distinct L^-1, the systems' y as its
-        right-hand sides) for shared inputs, else through paths.draw_per_path with the system as each path's group."""
-        from . import paths
+        every path or (S*J, M, D); drawer paths.Dense or vpaths.Vecchia, train its _DenseTrain / _VecchiaTrain.  Draws this
+        node's (S, J, M) block of normals.  Systems that one device call can hold (train.classes' call) draw together:
+        through drawer.draw_shared for shared inputs, once per distinct training set with the systems' outputs as the rows
+        of Y (an error names the first of them); else through drawer.draw_per_path with the system as each path's group."""
         S, M = len(nodes), xin.shape[-2]
-        P = S * J
         Z = np.random.standard_normal((S, J, M))
-        st = self._node_stats(e, pos, nodes, where)
+        cls, call = train.classes()
         calls = collections.defaultdict(list)
         for s in range(S):
-            calls[st['call'][s]].append(s)
+            calls[call[s]].append(s)
         draws = []   # (systems, (len(systems)*J, M) paths)
         for ss in calls.values():
-            nd = nodes[ss[0]]
-            hyper = (nd.length, nd.scale[0], nd.nugget[0])
+            hyper = paths.hyper(nodes[ss[0]])
             if xin.dim() == 2:
                 by = collections.defaultdict(list)
                 for s in ss:
-                    by[st['cls'][s]].append(s)
-                for c, cs in by.items():
-                    ps = st['per'][c]
-                    Y = torch.stack([st['y'][s] for s in cs])
-                    E = e.tensor(np.ascontiguousarray(Z[cs].transpose(2, 0, 1).reshape(M, len(cs) * J)))
-                    draws.append((cs, paths.draw_shared(e, nd.name, xin, ps['W'], ps['Linv'], Y, *hyper, E, J).T))
+                    by[cls[s]].append(s)
+                for cs in by.values():
+                    draws.append((cs, drawer.draw_shared(e, hyper, xin, *train.shared(cs), e.tensor(Z[cs].reshape(len(cs) * J, M)),
+                                                         J, '%s, system %d' % (where, cs[0] + 1))))
                 continue
             xs = xin if len(ss) == S else xin.view(S, J, M, -1)[torch.as_tensor(ss, device=e.device)].reshape(-1, M, xin.shape[2])
-            W = _By(lambda i, ss=ss: st['per'][st['cls'][ss[i]]]['W'])
-            Linv = _By(lambda i, ss=ss: st['per'][st['cls'][ss[i]]]['Linv'])
-            y = _By(lambda i, ss=ss: st['y'][ss[i]])
-            draws.append((ss, paths.draw_per_path(e, nd.name, xs.contiguous(), W, Linv, y, *hyper,
-                                                  e.tensor(Z[ss].reshape(len(ss) * J, M)), group=np.repeat(np.arange(len(ss)), J))))
+            tr, y, group = train.per_path(ss, J)
+            draws.append((ss, drawer.draw_per_path(e, hyper, xs.contiguous(), tr, y, e.tensor(Z[ss].reshape(len(ss) * J, M)), group,
+                                                   lambda p, ss=ss: '%s, system %d' % (where, ss[p // J] + 1))))
         if len(draws) == 1:
             return draws[0][1].contiguous()
         out = e.empty(S, J, M)
         for ss, o in draws:
             out[torch.as_tensor(ss, device=e.device)] = o.reshape(len(ss), J, M)
-        return out.reshape(P, M)
+        return out.reshape(S * J, M)
 
     @staticmethod
     def _node_classes(nodes):
@@ -496,68 +488,12 @@ class lgp:
                          (np.shape(X)[0], np.shape(X)[1] + (0 if Xg is None else np.shape(Xg)[1]))))
         return cls, call, first
 
-    def _vpaths_node(self, e, nodes, xin, J, where, m, order):
-        """_paths_node for sample_paths_vecchia: paths (S*J, M) of one GP node over all systems by vpaths, rows in the order
-        `order`, conditioning sets of size m.  Draws this node's (S, J, M) block of normals.  Systems that one device call
-        can hold (_node_classes' call, and equal replicate weights) draw together: shared inputs through
-        vpaths.draw_shared per distinct training set, the systems' outputs as the rows of Y; else through
-        vpaths.draw_per_path with the system as each path's group -- no group when the systems share training inputs and
-        outputs by content (the copies of a GP emulator); per-system tensors are made chunk by chunk (vpaths.PerGroup)."""
-        from . import vpaths
-        S, M = len(nodes), xin.shape[-2]
-        Z = np.random.standard_normal((S, J, M))
-        cls, call, _ = self._node_classes(nodes)
-        calls = collections.defaultdict(list)
-        for s, nd in enumerate(nodes):
-            calls[(call[s], None if nd.rep is None else np.asarray(nd.W_diag, float).tobytes())].append(s)
-
-        def train_in(s):
-            return e.tensor(np.ascontiguousarray(nodes[s]._X(), dtype=float))
-
-        def train_out(s):
-            return np.asarray(nodes[s].output, dtype=float).reshape(-1)
-
-        draws = []   # (systems, (len(systems)*J, M) paths)
-        for ss in calls.values():
-            nd = nodes[ss[0]]
-            hyper = (nd.length, nd.scale[0], nd.nugget[0])
-            omega = None if nd.rep is None else e.tensor(nd.W_diag)
-            Zs = e.tensor(Z[ss].reshape(len(ss) * J, M))
-            if xin.dim() == 2:
-                by = collections.defaultdict(list)
-                for s in ss:
-                    by[cls[s]].append(s)
-                for cs in by.values():   # (one set of rows serves the systems of cs: an error names the first of them)
-                    Y = e.tensor(np.stack([train_out(s) for s in cs]))
-                    Zc = Zs if len(cs) == len(ss) else e.tensor(Z[cs].reshape(len(cs) * J, M))
-                    draws.append((cs, vpaths.draw_shared(e, nd.name, train_in(cs[0]), Y, *hyper, xin, m, order, Zc, J, omega,
-                                                         '%s, system %d' % (where, cs[0] + 1))))
-                continue
-            xs = xin if len(ss) == S else xin.view(S, J, M, -1)[torch.as_tensor(ss, device=e.device)].reshape(-1, M, xin.shape[2])
-            W0 = train_in(ss[0]) if len({cls[s] for s in ss}) == 1 else None
-            if W0 is not None and all(np.array_equal(train_out(ss[0]), train_out(s)) for s in ss[1:]):
-                W, y, group = W0, e.tensor(train_out(ss[0])), None
-            else:
-                W = vpaths.PerGroup(lambda g, ss=ss, W0=W0: train_in(ss[g]) if W0 is None else W0)
-                y = vpaths.PerGroup(lambda g, ss=ss: e.tensor(train_out(ss[g])))
-                group = np.repeat(np.arange(len(ss)), J)
-            draws.append((ss, vpaths.draw_per_path(e, nd.name, W, y, *hyper, xs.contiguous(), m, order, Zs, group=group,
-                                                   omega=omega,
-                                                   where=lambda p, ss=ss: '%s, system %d' % (where, ss[p // J] + 1))))
-        if len(draws) == 1:
-            return draws[0][1].contiguous()
-        out = e.empty(S, J, M)
-        for ss, o in draws:
-            out[torch.as_tensor(ss, device=e.device)] = o.reshape(len(ss), J, M)
-        return out.reshape(S * J, M)
-
     def _node_stats(self, e, pos, nodes, where):
         """sample_paths' statistics of one GP node position over the systems, cached on the lgp (dropped by set_vecchia):
         y per system; L^-1 (paths.factor_inverse) and W per distinct training set -- inputs, replicate weights, lengths and
         nugget compared by content, so copies of one GP (lgp.__init__'s snapshots, or systems built by hand) and the
         first-layer nodes of a DGP emulator share one.  One distinct set is kept; several (the deeper nodes of a DGP
         emulator: one per system) are built when first asked for and kept under the emulator's byte budget (_LazyPer)."""
-        from . import paths
         from .emulation import _LazyPer
         cache = self.__dict__.setdefault('_paths_stats', {})
         st = cache.get(pos)

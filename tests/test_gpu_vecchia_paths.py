@@ -163,8 +163,8 @@ def test_full_conditioning_sets_give_the_dense_joint(eng, kind, n, M, m):
     omega = np.ones(n)
     order = rng.permutation(M)
     Z = np.concatenate((np.zeros((1, M)), np.eye(M)))
-    V = npy(vpaths.draw_shared(eng, kind, eng.tensor(W), eng.tensor(y[None]), length, scale, nugget, eng.tensor(X), m, order,
-                               eng.tensor(Z), M + 1))
+    V = npy(vpaths.Vecchia(m, order).draw_shared(eng, (kind, length, scale, nugget), eng.tensor(X), (eng.tensor(W), None),
+                                                 eng.tensor(y[None]), eng.tensor(Z), M + 1))
     mean, Sig = dense_joint(kind, W, y, omega, length, scale, nugget, X)
     np.testing.assert_allclose(V[0], mean, rtol=0, atol=1e-9 * max(1.0, np.abs(mean).max()))
     F = (V[1:] - V[0]).T
@@ -187,9 +187,9 @@ def test_first_row_agrees_with_vecchia_predict(eng):
         mu, s2 = mdl.predict(x, m=30)
         k = mdl.kernel
         order = rng.permutation(50)
-        V = npy(vpaths.draw_shared(eng, kind, eng.tensor(k._X()), eng.tensor(k.output.reshape(1, -1)), k.length, k.scale[0],
-                                   k.nugget[0], eng.tensor(x), 30, order, torch.zeros(1, 50, dtype=torch.float64,
-                                                                                     device=eng.device), 1))
+        V = npy(vpaths.Vecchia(30, order).draw_shared(eng, (kind, k.length, k.scale[0], k.nugget[0]), eng.tensor(x),
+                                                      (eng.tensor(k._X()), None), eng.tensor(k.output.reshape(1, -1)),
+                                                      torch.zeros(1, 50, dtype=torch.float64, device=eng.device), 1))
         r0 = order[0]
         assert abs(V[0, r0] - mu[r0, 0]) <= 1e-10 * max(1.0, abs(mu[r0, 0]))
         q = eng.tensor(x[order][None] / k.length)

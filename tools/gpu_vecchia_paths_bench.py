@@ -67,7 +67,7 @@ def main():
         print('sample_paths_vecchia (Vecchia emulator, M = %d, %d paths, m = %d): %-11s %9.1f ms' % (M, N * J, m, label, ms))
     if big_only:
         return
-    # the first-layer node's rows and schedule, as vpaths.draw_shared builds them
+    # the first-layer node's rows and schedule, as vpaths.Vecchia.draw_shared builds them
     nd = emu.all_layer[0][0]
     order = np.random.default_rng(7).permutation(M)
     ordt = torch.as_tensor(order, device=e.device)
