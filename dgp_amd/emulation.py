@@ -469,12 +469,7 @@ class emulator:
         node by node, one standard_normal((N, sample_size, M)) block per GP node.  At most 8192 rows of x; an imputation
         whose training correlation matrix is not positive definite raises numpy.linalg.LinAlgError."""
         from . import paths
-        if self.vecch:
-            raise NotImplementedError('sample_paths needs a dense emulator: joint draws of a Vecchia emulator need a sparse '
-                                      'algorithm of their own (use remove_vecchia())')
-        if self.shard or getattr(self, 'shard_points', False):
-            raise NotImplementedError("sample_paths with the imputations sharded over ranks would return partial draws; use "
-                                      "emulator(..., shard=False)")
+        self._need_dense_unsharded()
         paths.check_points(x)
         e, rng, drawer = self.engine, self._sample_rng, paths.Dense()
         M, S, J = len(x), self.N, int(sample_size)
@@ -490,6 +485,35 @@ class emulator:
                 out[mine] = drawer.draw_per_path(e, paths.hyper(nd), xin[mine], (ps['W'], ps['Linv']), ps['y'], Z[mine])
             return out
         return self._walk_paths(x, J, full_layer, draw)
+
+    def _need_dense_unsharded(self):
+        """What sample_paths and sample_functions refuse: both work on the dense statistics of all N imputations."""
+        if self.vecch:
+            raise NotImplementedError('sample_paths needs a dense emulator: joint draws of a Vecchia emulator need a sparse '
+                                      'algorithm of their own (use remove_vecchia())')
+        if self.shard or getattr(self, 'shard_points', False):
+            raise NotImplementedError("sample_paths with the imputations sharded over ranks would return partial draws; use "
+                                      "emulator(..., shard=False)")
+
+    def sample_functions(self, sample_size=50, n_features=2048):
+        """N * sample_size posterior draws of the emulated function as functions (pathwise conditioning, DESIGN I.12):
+        returns a pathfun.PathFunctions, paths(x, full_layer=False, noise=False), that evaluates every draw at the rows of
+        any x, any number of times, in sample_paths' container and column layout (column s * sample_size + j is path j of
+        imputation s).  Each GP node's prior is drawn through n_features random Fourier features shared by the node's paths
+        and conditioned on the training set -- the imputation's latents below layer 1 -- by Matheron's rule; the mean of
+        the draws is the posterior mean for every n_features, their covariance tends to sample_paths' as n_features
+        grows.  Creating the paths costs two triangular products per path; evaluating them (n + n_features) * M * D per
+        node and path, rows independent.  What is random in a path is drawn here, from the emulator's sampling generator,
+        per GP node in walk order (layer by layer, node by node): standard_normal((n_features, D)) for the frequencies;
+        for 'matern2.5' chisquare(5, (n_features, D)); uniform(0, 2 pi, n_features) for the phases;
+        standard_normal((N, sample_size, n_features)) for the feature weights; standard_normal((N, sample_size, n)) for the
+        nugget term.  Only the samples of likelihood nodes and of a Categorical top (the nodes' own sampling(), on numpy's
+        global generator) and the noise=True term (this generator) are drawn afresh on each evaluation (see PathFunctions).  Dense, unsharded emulators, as sample_paths; an imputation whose
+        training correlation matrix is not positive definite raises numpy.linalg.LinAlgError naming its layer, node and
+        imputation."""
+        from . import pathfun
+        self._need_dense_unsharded()
+        return pathfun.PathFunctions(self, sample_size, n_features)
 
     def sample_paths_vecchia(self, x, sample_size=50, full_layer=False, m=50):
         """sample_paths by the Vecchia factorisation of each node's joint predictive distribution (vpaths, DESIGN I.11):

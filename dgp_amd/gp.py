@@ -201,6 +201,22 @@ class gp:
         out = paths.Dense().draw_shared(e, paths.hyper(k), e.tensor(xin), (st['Wall'], st['joint']), y, e.tensor(Z), sample_size)
         return out.T.cpu().numpy()
 
+    def sample_functions(self, sample_size=50, n_features=2048):
+        """sample_size posterior draws of the GP as functions (pathwise conditioning on a random-Fourier-feature prior
+        draw, DESIGN I.12): returns a callable paths(x, noise=False) -> (M, sample_size) that evaluates the draws at the
+        rows of any x -- any number of rows, the same values at the same rows in every call, so a path can be optimised,
+        refined or integrated.  The mean of the draws is the posterior mean for every n_features; their covariance tends
+        to sample_paths' as n_features grows (noise=True adds the nugget term that sample_paths' draws carry, afresh on
+        every call).  Randomness comes from numpy's global generator, in the order np.random.standard_normal((n_features,
+        D)), for 'matern2.5' np.random.chisquare(5, (n_features, D)), np.random.uniform(0, 2 pi, n_features),
+        np.random.standard_normal((sample_size, n_features)), np.random.standard_normal((sample_size, n)).  Dense mode only;
+        a training correlation matrix that is not positive definite raises numpy.linalg.LinAlgError."""
+        from . import pathfun
+        if self.vecch:
+            raise NotImplementedError('sample_paths needs a dense GP: joint draws in Vecchia mode need a sparse algorithm '
+                                      'of their own (use remove_vecchia())')
+        return pathfun.GpPaths(self, sample_size, n_features)
+
     def sample_paths_vecchia(self, x, sample_size=50, m=50):
         """Joint posterior draws of the GP at the rows of x by the Vecchia factorisation of the joint predictive distribution
         (vpaths): (M, sample_size) as sample_paths, for dense and Vecchia-mode models and any M.  The rows are drawn in the

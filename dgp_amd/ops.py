@@ -298,14 +298,16 @@ class Engine:
                                     Np * Np, batch, _dp(ll), _dp(info), _dp(work)))
         return ll, info
 
-    def trmv_lower(self, n, L, scale, z, batch=1, out=None):
+    def trmv_lower(self, n, L, scale, z, batch=1, out=None, shared=False):
+        """out[b] = sqrt(scale[b]) L_b z[b]; shared: one factored buffer L for the whole batch (batch stride 0)."""
         Np = self.padded_dim(n)
         sc = _f64(scale)
         if len(sc) == 1 and batch > 1:
             sc = np.repeat(sc, batch)
         if out is None:
             out = self.empty(batch, n)
-        self._chk(self._enter() or lib.dgpamd_trmv_lower(self.h, n, _dp(L), Np * Np, _hp(sc), _dp(z), _dp(out), batch))
+        self._chk(self._enter() or lib.dgpamd_trmv_lower(self.h, n, _dp(L), 0 if shared else Np * Np, _hp(sc), _dp(z), _dp(out),
+                                                          batch))
         return out
 
     def ess_propose(self, F, NU, thetas, out=None):
@@ -560,6 +562,33 @@ class Engine:
         sm = 0 if mean is None else M * (c // rep)
         self._chk(self._enter() or lib.dgpamd_mvn_paths(self.h, M, c, rep, batch, _dp(L), Mp * Mp, _dp(mean), sm, _dp(E), M * c,
                                                          _dp(out), M * c))
+        return out
+
+    def pathfun_eval(self, kind, x, W, Omega, b, theta, v, length, scale, group=None, out=None):
+        """P function-valued draws of one GP node at M rows (dgpamd_pathfun_eval):
+            out[p, m] = sqrt(scale) (sqrt(2/F) sum_f theta[p, f] cos(Omega[f] . x[m] + b[f]) + sum_i v[p, i] c(x[m], W_g(p)[i])).
+        x: (M, D) shared by every path, or (P, M, D); W: (n, D), (G, n, D) or None (n = 0: the prior part alone); Omega
+        (F, D), b (F,), theta (P, F), v (P, n) or None; group: host ints (P,) picking each path's W (None: all 0; shared x
+        needs one group).  Returns out (P, M)."""
+        P, F = theta.shape
+        M, D = x.shape[-2:]
+        Wb = None if W is None else (W if W.dim() == 3 else W[None])
+        n = 0 if Wb is None else Wb.shape[1]
+        G = 1 if Wb is None else Wb.shape[0]
+        assert x.dim() == 2 or x.shape[0] == P
+        assert Omega.shape == (F, D) and b.shape == (F,) and (n == 0 or (v is not None and v.shape == (P, n) and Wb.shape[2] == D))
+        for t in (x, Wb, Omega, b, theta, v if n else None):
+            assert t is None or (t.is_contiguous() and t.dtype == torch.float64)
+        length = _f64(length)
+        g = None if group is None else np.ascontiguousarray(np.asarray(group, dtype=np.int32))
+        assert g is None or g.shape == (P,)
+        if out is None:
+            out = self.empty(P, M)
+        assert out.shape == (P, M) and out.is_contiguous()
+        self._chk(self._enter() or lib.dgpamd_pathfun_eval(self.h, KIND[kind], n, M, D, F, P, _dp(x), M * D if x.dim() == 3 else 0,
+                                                            None if g is None else _hp(g), G, _dp(Wb), n * D,
+                                                            _dp(Omega), _dp(b), _dp(theta), _dp(v) if n else None, _hp(length),
+                                                            len(length), float(scale), _dp(out)))
         return out
 
     def linkgp_predict(self, kind, m, v, z, Wtr, Wg, length, Rinv, ldr, ry, scale, nugget, mean=None, var=None,

@@ -1,0 +1,220 @@
+"""Function-valued posterior draws of GP nodes by pathwise conditioning (emulator.sample_functions, gp.sample_functions;
+DESIGN I.12).
+
+A node with training inputs W (n, D), outputs y, replicate weights omega, R = c(W, W) + nugget diag(omega) = L L^T has the
+prior draw  g(x) = phi(x)^T theta,  phi(x) = sqrt(2/F) cos(Omega x + b),  of F random Fourier features (features()), and
+Matheron's rule turns it into a posterior draw:
+    f(x) = sqrt(scale) (phi(x)^T theta + c(x, W) v),   v = L^-T L^-1 (y / sqrt(scale) - Phi(W) theta - sqrt(nugget omega) * eps),
+theta ~ N(0, I_F), eps ~ N(0, I_n).  Its mean over (theta, eps) is c(x, W) R^-1 y for every F; its covariance tends to the
+posterior's as F grows.  A path is held as (theta, v) and evaluated by dgpamd_pathfun_eval at any rows, any number of times,
+with the same values at the same rows.  NodePaths is the paths of one node; PathFunctions walks a DGP hierarchy with them
+(pathwalk.walk, beside the drawers paths.Dense and vpaths.Vecchia).
+"""
+import copy
+
+import numpy as np
+import torch
+
+from . import paths, pathwalk
+
+
+def features(rng, kind, length, D, F):
+    """(Omega (F, D), b (F,)) of a node's random Fourier features, drawn from rng (a numpy Generator, or the numpy.random
+    module) in the order: standard_normal((F, D)); for 'matern2.5' chisquare(5, (F, D)); uniform(0, 2 pi, F).
+    sexp: exp(-tau^2 / g^2) has spectral measure N(0, 2 / g^2): Omega = sqrt(2) z / g.  matern2.5 (the separable product):
+    every column a Student-t with 5 degrees of freedom over g, Omega = z / sqrt(chi2_5 / 5) / g, independent per (f, d).
+    One lengthscale is broadcast over the D columns."""
+    g = np.broadcast_to(np.asarray(length, dtype=np.float64).reshape(-1), (D,)) if np.size(length) == 1 else \
+        np.asarray(length, dtype=np.float64).reshape(D)
+    z = rng.standard_normal((F, D))
+    if kind == 'sexp':
+        Omega = np.sqrt(2.0) * z / g
+    elif kind == 'matern2.5':
+        Omega = z / np.sqrt(rng.chisquare(5, (F, D)) / 5.0) / g
+    else:
+        raise ValueError(kind)
+    b = rng.uniform(0.0, 2.0 * np.pi, F)
+    return Omega, b
+
+
+def _rows_per_call(e, P, width):
+    """Rows evaluated per call: `width` doubles per row and path within a quarter of the free device memory."""
+    free = torch.cuda.mem_get_info(e.device)[0]
+    return int(max(1, free // 4 // (8 * P * width)))
+
+
+def weights(e, hyper, W, Linv, Omega, b, theta, y, eps, omega):
+    """v (P, n) of P paths that share one training set: W (n, D), Linv = paths.factor_inverse's L^-1, theta (P, F), y (P, n)
+    or (n,), eps (P, n) device tensors, omega (n,) device tensor or None.  Phi(W) theta is the prior part of the paths at
+    x = W (dgpamd_pathfun_eval with n = 0); L^-1 is applied by dgpamd_trmv_lower to 64 paths at a time, L^-T by dgpamd_gemv
+    on the transposed triangle; one refinement step against R v follows."""
+    kind, length, scale, nugget = hyper
+    n = W.shape[0]
+    P = theta.shape[0]
+    LT = torch.tril(Linv[:n, :n]).T.contiguous()
+    diag = nugget if omega is None else nugget * omega
+
+    def solve(rhs):
+        u, out = e.empty(P, n), e.empty(P, n)
+        for p0 in range(0, P, 64):
+            p1 = min(P, p0 + 64)
+            e.trmv_lower(n, Linv, [1.0], rhs[p0:p1], batch=p1 - p0, out=u[p0:p1], shared=True)
+        for p in range(P):
+            e.gemv(LT, u[p], out=out[p])
+        return out
+
+    r = y / np.sqrt(scale) - e.pathfun_eval(kind, W, None, Omega, b, theta, None, length, 1.0)
+    r -= eps * (np.sqrt(nugget) if omega is None else torch.sqrt(nugget * omega))
+    r = r.contiguous()
+    v = solve(r)
+    # one step of iterative refinement: the explicit L^-1 leaves a residual of order cond(L) eps |R| |v|, and v is large where
+    # R is ill-conditioned (a small nugget); R v = c(W, W) v + nugget omega * v is the evaluation kernel itself at x = W
+    zero = e.zeros(1, W.shape[1])
+    Rv = e.pathfun_eval(kind, W, W, zero, e.zeros(1), e.zeros(P, 1), v, length, 1.0) + diag * v
+    return v + solve((r - Rv).contiguous())
+
+
+class NodePaths:
+    """P function-valued draws of one GP node: hyper = paths.hyper(node); Omega (F, D), b (F,) its features; theta (P, F);
+    W (n, D) one training set for every path, or (G, n, D) with group (host ints (P,)) picking each path's; v (P, n).
+    Everything is the object's own copy."""
+
+    def __init__(self, hyper, Omega, b, theta, W, v, group=None):
+        kind, length, scale, nugget = hyper
+        self.hyper = (kind, np.array(length, dtype=np.float64), float(scale), float(nugget))
+        self.Omega, self.b, self.theta, self.W, self.v = Omega, b, theta, W, v
+        self.group = None if group is None else np.asarray(group, dtype=np.int32).copy()
+
+    def __call__(self, e, x):
+        """The paths at x: (M, D) shared by every path, or (P, M, D).  Returns (P, M)."""
+        kind, length, scale, _ = self.hyper
+        if x.dim() == 3 and self.W.dim() == 2:
+            W, group = self.W[None], None
+        else:
+            W, group = self.W, (self.group if x.dim() == 3 else None)
+        return e.pathfun_eval(kind, x, W, self.Omega, self.b, self.theta, self.v, length, scale, group=group)
+
+    def noise_sd(self):
+        return np.sqrt(self.hyper[2] * self.hyper[3])
+
+
+class PathFunctions:
+    """emulator.sample_functions' result: N * sample_size posterior draws of the emulated function, each a closed-form
+    function of x.  paths(x, full_layer=False, noise=False) evaluates all of them at the rows of x and returns
+    sample_paths' container: a list over the final layer's nodes of (M, N * sample_size) arrays, or with full_layer a list
+    over layers of such lists; column s * sample_size + j is path j of imputation s.  Any number of rows (evaluated in
+    blocks that fit the free device memory); GP nodes give the same values at the same rows in every call.  Drawn afresh
+    on each call, block of rows by block of rows: the samples of likelihood nodes and of a Categorical top (from the path's
+    latents by the node's own sampling(), which draws from numpy's global generator, as in sample_paths), and with
+    noise=True an independent N(0, scale * nugget) term per row, path and GP node in walk order, from the emulator's
+    sampling generator (standard_normal((N * sample_size, rows)) each) -- the
+    nugget that sample_paths' joint covariance carries on its diagonal.  The object holds its own copies of the features,
+    weights and training inputs: it stays valid when the emulator changes."""
+
+    def __init__(self, emu, sample_size, n_features):
+        e, rng = emu.engine, emu._sample_rng
+        S, J, F = emu.N, int(sample_size), int(n_features)
+        if J < 1 or F < 1:
+            raise ValueError('sample_functions needs sample_size >= 1 and n_features >= 1')
+        self.engine, self.rng, self.N, self.sample_size, self.n_features = e, rng, S, J, F
+        self.layers = [[copy.copy(nd) for nd in layer] for layer in emu.all_layer]
+        self.nodes = {}
+        for l, layer in enumerate(emu.all_layer):
+            for k, nd in enumerate(layer):
+                if nd.type != 'gp':
+                    continue
+                hyper = paths.hyper(nd)
+                st = emu._joint_stats(l, k)
+                n = len(nd.output)
+                D = (st['W'] if l == 0 else st['per'][0]['W']).shape[1]
+                Om, b = features(rng, nd.name, nd.length, D, F)
+                Om, b = e.tensor(Om), e.tensor(b)
+                theta = e.tensor(rng.standard_normal((S, J, F)).reshape(S * J, F))
+                eps = e.tensor(rng.standard_normal((S, J, n)).reshape(S * J, n))
+                omega = None if nd.rep is None else e.tensor(nd.W_diag)
+                if l == 0:
+                    W = st['W'].clone()
+                    v = weights(e, hyper, W, st['Linv'], Om, b, theta, st['Y'].repeat_interleave(J, 0), eps, omega)
+                    self.nodes[l, k] = NodePaths(hyper, Om, b, theta, W, v)
+                else:
+                    Ws, vs = [], []
+                    for s in range(S):
+                        ps, mine = st['per'][s], slice(s * J, (s + 1) * J)
+                        Ws.append(ps['W'])
+                        vs.append(weights(e, hyper, ps['W'], ps['Linv'], Om, b, theta[mine], ps['y'], eps[mine], omega))
+                    self.nodes[l, k] = NodePaths(hyper, Om, b, theta, torch.stack(Ws), torch.cat(vs), np.repeat(np.arange(S), J))
+
+    def __call__(self, x, full_layer=False, noise=False):
+        paths.check_2d(x)
+        e, P = self.engine, self.N * self.sample_size
+        width = 4 * max(len(layer) for layer in self.layers) + 3 * max(nf.Omega.shape[1] for nf in self.nodes.values()) + 4
+        step, M = _rows_per_call(e, P, width), len(x)
+        if M == 0:
+            raise ValueError('sample_functions: x has no rows')
+        blocks = None
+        for m0 in range(0, M, step):
+            out = self._block(np.ascontiguousarray(x[m0:m0 + step]), noise)
+            blocks = [[a] for a in out] if blocks is None else [bl + [a] for bl, a in zip(blocks, out)]
+        out = [list(np.concatenate(bl, 1).transpose(2, 1, 0)) for bl in blocks]
+        return out if full_layer else out[-1]
+
+    def _block(self, x, noise):
+        e, P = self.engine, self.N * self.sample_size
+        xd = e.tensor(x)
+
+        def first(nd):
+            xin = pathwalk.cols(xd, nd.input_dim)
+            return xin if nd.connect is None else torch.cat((xin, pathwalk.cols(xd, nd.connect)), 1)
+
+        def draw(l, k, nodes, xin):
+            nf = self.nodes[l, k]
+            out = nf(e, xin)
+            if noise:
+                out += nf.noise_sd() * e.tensor(self.rng.standard_normal((P, len(x))))
+            return out
+        return [cur.cpu().numpy() for cur in pathwalk.walk(e, [self.layers] * self.N, self.sample_size, xd, None, first, draw)]
+
+
+class GpPaths:
+    """gp.sample_functions' result: paths(x, noise=False) -> (M, sample_size), column j the j-th posterior draw of the GP as
+    a function, evaluated at the rows of x: any number of rows, the same values at the same rows in every call.
+    noise=True adds an independent N(0, scale * nugget) term per row and path, np.random.standard_normal((sample_size, M))
+    drawn afresh on every call (the nugget that sample_paths' joint covariance carries on its diagonal)."""
+
+    def __init__(self, model, sample_size, n_features):
+        k = model.kernel
+        e = k.engine
+        J, F = int(sample_size), int(n_features)
+        if J < 1 or F < 1:
+            raise ValueError('sample_functions needs sample_size >= 1 and n_features >= 1')
+        if k._stats is None:
+            k.compute_stats()
+        st = k._stats
+        omega = None if k.rep is None else e.tensor(k.W_diag)
+        if 'joint' not in st:
+            st['joint'] = paths.factor_inverse(e, k.name, st['W'], st['Wg'], omega, k.length, k.nugget[0], 'the gp model')
+        W = st['Wall'].clone()
+        n, D = W.shape
+        hyper = paths.hyper(k)
+        Om, b = features(np.random, k.name, k.length, D, F)
+        Om, b = e.tensor(Om), e.tensor(b)
+        theta = e.tensor(np.random.standard_normal((J, F)))
+        eps = e.tensor(np.random.standard_normal((J, n)))
+        y = e.tensor(np.asarray(k.output, float).reshape(-1))
+        self.engine, self.sample_size = e, J
+        self.input_dim, self.connect = np.array(k.input_dim), None if k.connect is None else np.array(k.connect)
+        self.node = NodePaths(hyper, Om, b, theta, W, weights(e, hyper, W, st['joint'], Om, b, theta, y, eps, omega))
+
+    def __call__(self, x, noise=False):
+        paths.check_2d(x)
+        if len(x) == 0:
+            raise ValueError('sample_functions: x has no rows')
+        e, J = self.engine, self.sample_size
+        xin = x[:, self.input_dim] if self.connect is None else np.concatenate((x[:, self.input_dim], x[:, self.connect]), 1)
+        step, out = _rows_per_call(e, J, 2 + xin.shape[1]), []
+        for m0 in range(0, len(x), step):
+            out.append(self.node(e, e.tensor(np.ascontiguousarray(xin[m0:m0 + step]))).cpu().numpy().T)
+        out = np.concatenate(out, 0)
+        if noise:
+            out = out + self.node.noise_sd() * np.random.standard_normal((J, len(x))).T
+        return out

@@ -526,6 +526,22 @@ int dgpamd_vpaths_rows(dgpamd_ctx *ctx, int kind, int64_t P, int64_t M, int64_t 
                        double scale, double nugget, double jitter, double *Lrows, int64_t *NNl, double *t, double *sd,
                        int32_t *info);
 
+/* ---- function-valued posterior draws (pathwise conditioning, DESIGN I.12) ---------------------------------
+ * One GP node, P paths, M rows.  Path p is the closed-form function
+ *   out[p][m] = sqrt(scale) ( sqrt(2/F) sum_f theta[p][f] cos(Omega_f . x_m + b_f) + sum_i v[p][i] c(x_m, W_g(p)[i]) ):
+ * a random-Fourier-feature draw of the prior (Omega F x D, b F, theta P x F) plus the update that conditions it on the
+ * training set (v P x n; c the node's correlation function with lengthscales length_h, one or D of them).  x is shared by
+ * every path (M x D, stride_x == 0: the products run on f64 MFMA against tiles of features and correlations generated on
+ * the fly; every path then uses one training set, group_h NULL or constant) or one per path (P x M x D, stride_x >= M D:
+ * one lane per row).  group_h (host, P; NULL: all 0) < ngroups picks path p's training inputs W_g (n x D, stride_w between
+ * groups).  n == 0 (W, v may be NULL) evaluates the prior draw alone; evaluated at x = W that is the Phi(W) theta the
+ * weights v need.  D <= DGPAMD_MAXD, any P and M; neither Phi(x) nor c(x, W) is stored and no workspace is used.  Each
+ * out[p][m] is one fixed sequence of operations on row m alone: the same bits whichever rows share the call. */
+int dgpamd_pathfun_eval(dgpamd_ctx *ctx, int kind, int64_t n, int64_t M, int D, int64_t F, int P, const double *x,
+                        int64_t stride_x, const int32_t *group_h, int ngroups, const double *W, int64_t stride_w,
+                        const double *Omega, const double *b, const double *theta, const double *v,
+                        const double *length_h, int nlen, double scale, double *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,114 @@
+"""Function-valued posterior draws at the bench's model shape (profiles/pathfun_bench.txt; DESIGN I.12): n = 2000, d = 5
+Matern nodes -> one Matern node with `connect`, briefly trained; emulator(N=10); sample_size = 10 (100 paths).
+  1. per n_features F in (2048, 8192): the time to create the paths (sample_functions), then the time to evaluate them at
+     M = 1000 and M = 8192 rows, alternating with warm sample_paths and sample_paths_vecchia (m = 50) on the same emulator
+     and rows; at M = 100 000 alternating with sample_paths_vecchia alone (the dense draw stops at 8192 rows);
+  2. dgpamd_pathfun_eval alone by device events at M = 100 000, F = 2048: a first-layer node (shared rows, the MFMA kernel)
+     and the output node (per-path rows, the lane kernel), priced in executed f64 operations against the 78.6 TF/s peak.
+--big: only the M = 100 000 evaluation at F = 2048 and leg 2 (for a rocprofv3 --kernel-trace --stats run of its own, and
+for comparing builds of the library through DGPAMD_LIB)."""
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+PEAK = 78.6e12
+WIDTHS = (2, 4, 6, 8, 10, 16, 32, 64)   # the input widths pathfun.hip compiles (D is padded to the next)
+COS_FLOPS = 33    # cos_reduced: 14 fused multiply-adds and 5 additions / multiplications
+EXP_FLOPS = 32    # exp_negated: 15 fused multiply-adds and 2 additions / multiplications
+
+
+def entry_flops(kind, D):
+    """f64 operations (an fma is 2) of one generated entry: (feature, correlation)."""
+    DT = next(w for w in WIDTHS if w >= D)
+    feat = 2 * DT + COS_FLOPS
+    corr = (3 * DT + EXP_FLOPS) if kind == 'sexp' else (7 * DT + EXP_FLOPS + 2)
+    return feat, corr
+
+
+def executed_flops(kind, n, M, D, F, P, shared):
+    """What dgpamd_pathfun_eval executes, idle lanes and padding counted.  Lane kernel: 256 rows per workgroup, features and
+    training rows in tiles of 64, one multiply-add per entry on top.  MFMA kernel: 64 rows per workgroup, tiles of 32, every
+    entry generated once per block of 128 paths; the products on v_mfma_f64_16x16x4 over 64 or 128 path columns."""
+    up = lambda v, q: -(-v // q) * q
+    feat, corr = entry_flops(kind, D)
+    if not shared:
+        return P * up(M, 256) * (up(F, 64) * (feat + 2) + up(n, 64) * (corr + 2))
+    blocks, last = -(-P // 128), (64 if 0 < P % 128 <= 64 else 128)
+    gen = blocks * up(M, 64) * (up(F, 32) * feat + up(n, 32) * corr)
+    mfma = up(M, 64) * (up(F, 32) + up(n, 32)) * 2 * (128 * (blocks - 1) + last)
+    return gen + mfma
+
+
+def timed(f):
+    import torch
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = f()
+    torch.cuda.synchronize()
+    return out, 1e3 * (time.perf_counter() - t0)
+
+
+def main():
+    import bench
+    from dgp_amd import emulator
+    big_only = '--big' in sys.argv
+    n, d, N, J, m = 2000, 5, 10, 10, 50
+    model, X, _ = bench.build_model(n, d, 0, 0)
+    model.train(N=5, ess_burn=5, disable=True)
+    emu = emulator(model.estimate(), N=N, seed=1)
+    e = emu.engine
+    rng = np.random.default_rng(5)
+    xs = {M: rng.uniform(size=(M, d)) for M in (1000, 8192, 100000)}
+    emu.sample_paths(xs[1000], sample_size=J)   # (the lazily built statistics are shared by every method below)
+    pfs = {}
+    for F in ((2048,) if big_only else (2048, 8192)):
+        for label in ('first', 'second'):
+            pfs[F], ms = timed(lambda: emu.sample_functions(sample_size=J, n_features=F))
+            print('sample_functions(sample_size=%d, n_features=%d): creating %d paths, %-6s call %9.1f ms' % (J, F, N * J, label, ms))
+    if big_only:
+        for label in ('first call', 'second call'):
+            out, ms = timed(lambda: pfs[2048](xs[100000]))
+            print('paths(x), F = 2048, M = 100000: %-11s %9.1f ms' % (label, ms))
+    for M in (() if big_only else (1000, 8192, 100000)):
+        x = xs[M]
+        legs = [('paths(x), F = %d' % F, (lambda F=F: pfs[F](x))) for F in (2048, 8192)]
+        if M <= 8192:
+            legs.append(('sample_paths', lambda: emu.sample_paths(x, sample_size=J)))
+        legs.append(('sample_paths_vecchia, m = %d' % m, lambda: emu.sample_paths_vecchia(x, sample_size=J, m=m)))
+        for name, f in legs:   # warm every shape
+            out = f()
+            assert out[0].shape == (M, N * J) and np.all(np.isfinite(out[0]))
+        for rnd in range(2 if M == 100000 else 3):   # alternating: each round times every method once
+            for name, f in legs:
+                _, ms = timed(f)
+                print('M = %6d, %d paths, round %d: %-28s %10.1f ms' % (M, N * J, rnd + 1, name, ms))
+    # the evaluation kernels alone
+    M, F = 100000, 2048
+    pf, xd = pfs[F], e.tensor(xs[100000])
+    for (l, k), shared in (((0, 0), True), ((1, 0), False)):
+        nf = pf.nodes[l, k]
+        D = nf.Omega.shape[1]
+        xin = xd[:, :D].contiguous() if shared else e.tensor(rng.normal(size=(N * J, M, D)))
+        nf(e, xin)
+        reps = 3
+        ev0, ev1 = e.event(), e.event()
+        e.record(ev0)
+        for _ in range(reps):
+            nf(e, xin)
+        e.record(ev1)
+        ms = e.elapsed_ms(ev0, ev1) / reps
+        fx = executed_flops(nf.hyper[0], n, M, D, F, N * J, shared)
+        fa = N * J * M * (n + F) * D
+        print('dgpamd_pathfun_eval, %s rows, %s, %d paths, n = %d, F = %d, M = %d, D = %d: %.2f ms; executed %.3f TF -> %.2f TF/s '
+              '= %.3f of the f64 peak (work count (n + F) M D per path: %.3f T)'
+              % ('shared' if shared else 'per-path', nf.hyper[0], N * J, n, F, M, D, ms, fx / 1e12, fx / ms / 1e9,
+                 fx / ms / 1e9 / (PEAK / 1e12), fa / 1e12))
+
+
+if __name__ == '__main__':
+    main()
