@@ -564,12 +564,8 @@ class Engine:
                                                          _dp(out), M * c))
         return out
 
-    def pathfun_eval(self, kind, x, W, Omega, b, theta, v, length, scale, group=None, out=None):
-        """P function-valued draws of one GP node at M rows (dgpamd_pathfun_eval):
-            out[p, m] = sqrt(scale) (sqrt(2/F) sum_f theta[p, f] cos(Omega[f] . x[m] + b[f]) + sum_i v[p, i] c(x[m], W_g(p)[i])).
-        x: (M, D) shared by every path, or (P, M, D); W: (n, D), (G, n, D) or None (n = 0: the prior part alone); Omega
-        (F, D), b (F,), theta (P, F), v (P, n) or None; group: host ints (P,) picking each path's W (None: all 0; shared x
-        needs one group).  Returns out (P, M)."""
+    def _pathfun_call(self, fn, kind, x, W, Omega, b, theta, v, length, scale, group, outs):
+        """The checks and the argument list that dgpamd_pathfun_eval and dgpamd_pathfun_grad share; outs: the output tensors."""
         P, F = theta.shape
         M, D = x.shape[-2:]
         Wb = None if W is None else (W if W.dim() == 3 else W[None])
@@ -582,14 +578,27 @@ class Engine:
         length = _f64(length)
         g = None if group is None else np.ascontiguousarray(np.asarray(group, dtype=np.int32))
         assert g is None or g.shape == (P,)
-        if out is None:
-            out = self.empty(P, M)
-        assert out.shape == (P, M) and out.is_contiguous()
-        self._chk(self._enter() or lib.dgpamd_pathfun_eval(self.h, KIND[kind], n, M, D, F, P, _dp(x), M * D if x.dim() == 3 else 0,
-                                                            None if g is None else _hp(g), G, _dp(Wb), n * D,
-                                                            _dp(Omega), _dp(b), _dp(theta), _dp(v) if n else None, _hp(length),
-                                                            len(length), float(scale), _dp(out)))
-        return out
+        outs = [self.empty(*shape) if o is None else o for o, shape in zip(outs, ((P, M), (P, M, D)))]
+        for o, shape in zip(outs, ((P, M), (P, M, D))):
+            assert o.shape == shape and o.is_contiguous()
+        self._chk(self._enter() or fn(self.h, KIND[kind], n, M, D, F, P, _dp(x), M * D if x.dim() == 3 else 0,
+                                      None if g is None else _hp(g), G, _dp(Wb), n * D, _dp(Omega), _dp(b), _dp(theta),
+                                      _dp(v) if n else None, _hp(length), len(length), float(scale), *[_dp(o) for o in outs]))
+        return outs
+
+    def pathfun_eval(self, kind, x, W, Omega, b, theta, v, length, scale, group=None, out=None):
+        """P function-valued draws of one GP node at M rows (dgpamd_pathfun_eval):
+            out[p, m] = sqrt(scale) (sqrt(2/F) sum_f theta[p, f] cos(Omega[f] . x[m] + b[f]) + sum_i v[p, i] c(x[m], W_g(p)[i])).
+        x: (M, D) shared by every path, or (P, M, D); W: (n, D), (G, n, D) or None (n = 0: the prior part alone); Omega
+        (F, D), b (F,), theta (P, F), v (P, n) or None; group: host ints (P,) picking each path's W (None: all 0; shared x
+        needs one group).  Returns out (P, M)."""
+        return self._pathfun_call(lib.dgpamd_pathfun_eval, kind, x, W, Omega, b, theta, v, length, scale, group, [out])[0]
+
+    def pathfun_grad(self, kind, x, W, Omega, b, theta, v, length, scale, group=None, out=None, grad=None):
+        """pathfun_eval's draws and their input gradients in one pass (dgpamd_pathfun_grad): the arguments of pathfun_eval;
+        returns (out (P, M), grad (P, M, D)), out bit for bit pathfun_eval's and grad[p, m, d] = d out[p, m] / d x[m, d]
+        (x[p, m, d] for per-path x), in the node's own D input columns."""
+        return tuple(self._pathfun_call(lib.dgpamd_pathfun_grad, kind, x, W, Omega, b, theta, v, length, scale, group, [out, grad]))
 
     def linkgp_predict(self, kind, m, v, z, Wtr, Wg, length, Rinv, ldr, ry, scale, nugget, mean=None, var=None,
                        drop=None):

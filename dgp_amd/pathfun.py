@@ -9,6 +9,10 @@ theta ~ N(0, I_F), eps ~ N(0, I_n).  Its mean over (theta, eps) is c(x, W) R^-1 
 posterior's as F grows.  A path is held as (theta, v) and evaluated by dgpamd_pathfun_eval at any rows, any number of times,
 with the same values at the same rows.  NodePaths is the paths of one node; PathFunctions walks a DGP hierarchy with them
 (pathwalk.walk, beside the drawers paths.Dense and vpaths.Vecchia).
+
+The input gradient of a path is as closed-form as the path (DESIGN I.13): dgpamd_pathfun_grad returns a node's values and
+its (P, M, D) gradient from one pass, and PathFunctions.value_and_grad carries the Jacobian with respect to the emulator's
+input through the same walk by the chain rule, on the device.
 """
 import copy
 
@@ -94,8 +98,25 @@ class NodePaths:
             W, group = self.W, (self.group if x.dim() == 3 else None)
         return e.pathfun_eval(kind, x, W, self.Omega, self.b, self.theta, self.v, length, scale, group=group)
 
+    def value_and_grad(self, e, x):
+        """The paths and their input gradients at x ((M, D) shared, or (P, M, D)): (P, M), bit for bit what __call__
+        returns, and (P, M, D), d path p at row m / d column d of its own input."""
+        kind, length, scale, _ = self.hyper
+        if x.dim() == 3 and self.W.dim() == 2:
+            W, group = self.W[None], None
+        else:
+            W, group = self.W, (self.group if x.dim() == 3 else None)
+        return e.pathfun_grad(kind, x, W, self.Omega, self.b, self.theta, self.v, length, scale, group=group)
+
     def noise_sd(self):
         return np.sqrt(self.hyper[2] * self.hyper[3])
+
+
+def _scatter_add(J, g, columns):
+    """J[..., columns[i]] += g[..., i], column by column in the order given: a column named twice receives both terms, in a
+    fixed order."""
+    for i, c in enumerate(columns):
+        J[..., int(c)] += g[..., i]
 
 
 class PathFunctions:
@@ -109,7 +130,12 @@ class PathFunctions:
     noise=True an independent N(0, scale * nugget) term per row, path and GP node in walk order, from the emulator's
     sampling generator (standard_normal((N * sample_size, rows)) each) -- the
     nugget that sample_paths' joint covariance carries on its diagonal.  The object holds its own copies of the features,
-    weights and training inputs: it stays valid when the emulator changes."""
+    weights and training inputs: it stays valid when the emulator changes.
+    paths.value_and_grad(x, full_layer=False) -> (values, gradients) and paths.grad(x, full_layer=False) -> gradients
+    differentiate every draw with respect to the rows of x (emulators of GP nodes only): values is paths(x)'s container
+    with paths(x)'s bits; gradients is a list over the final layer's nodes of (M, Dx, N * sample_size) arrays, Dx =
+    x.shape[1], entry [m, d, s * sample_size + j] = d path / d x[m, d] (columns of x the model does not read: zero), or
+    with full_layer a list over layers of such lists."""
 
     def __init__(self, emu, sample_size, n_features):
         e, rng = emu.engine, emu._sample_rng
@@ -175,11 +201,92 @@ class PathFunctions:
         return [cur.cpu().numpy() for cur in pathwalk.walk(e, [self.layers] * self.N, self.sample_size, xd, None, first, draw)]
 
 
+    def _check_differentiable(self):
+        for layer in self.layers:
+            for nd in layer:
+                if nd.type != 'gp':
+                    raise ValueError('sample_functions: the draws of this emulator pass through a sampled node (a likelihood '
+                                     'node or a Categorical top), and a sampled node has no derivative with respect to x; '
+                                     'grad and value_and_grad need an emulator of GP nodes only (paths(x) still evaluates)')
+
+    def value_and_grad(self, x, full_layer=False):
+        """(values, gradients) at the rows of x (M, Dx).  values: paths(x, full_layer)'s container and bits.  gradients: a
+        list over the final layer's nodes of (M, Dx, N * sample_size) arrays, [m, d, s * sample_size + j] = d (path j of
+        imputation s at row m) / d x[m, d]; with full_layer a list over layers of such lists.  Columns of x that the model
+        does not read get zero.  Raises ValueError for an emulator with a likelihood node or a Categorical top."""
+        self._check_differentiable()
+        paths.check_2d(x)
+        e, P = self.engine, self.N * self.sample_size
+        M, Dx = x.shape
+        if M == 0:
+            raise ValueError('sample_functions: x has no rows')
+        K, D = max(len(layer) for layer in self.layers), max(nf.Omega.shape[1] for nf in self.nodes.values())
+        # paths(x)'s doubles per row and path, a node's gradient twice (the kernel's and the slice multiplied), and Dx per node
+        # for the Jacobians of two layers, one gathered operand and the node's own
+        width = 4 * K + 3 * D + 4 + 2 * D + (3 * K + 2) * Dx
+        step = _rows_per_call(e, P, width)
+        vals = grads = None
+        for m0 in range(0, M, step):
+            v, g = self._block_grad(np.ascontiguousarray(x[m0:m0 + step]), full_layer)
+            vals = [[a] for a in v] if vals is None else [bl + [a] for bl, a in zip(vals, v)]
+            grads = [[a] for a in g] if grads is None else [bl + [a] for bl, a in zip(grads, g)]
+        vals = [list(np.concatenate(bl, 1).transpose(2, 1, 0)) for bl in vals]
+        grads = [list(np.concatenate(bl, 1).transpose(2, 1, 3, 0)) for bl in grads]
+        return (vals, grads) if full_layer else (vals[-1], grads[-1])
+
+    def grad(self, x, full_layer=False):
+        """value_and_grad(x, full_layer)[1]."""
+        return self.value_and_grad(x, full_layer)[1]
+
+    def _block_grad(self, x, full_layer):
+        """The walk of _block with every node's (P, M, D_node) gradient folded into the Jacobian of its layer with respect to
+        x, (P, M, K_layer, Dx), on the device.  First layer: the gradient scattered into the node's input_dim and connect
+        columns of x.  Deeper: J[p, m, :] = sum_k g[p, m, k] J_below[p, m, input_dim[k], :] plus the connect part scattered
+        into x's columns -- one fused multiply-add per element and k, in the order of k, so that a row's Jacobian does not
+        depend on the rows that share its block (a library contraction may pick another summation order at another size).
+        Returns (values, Jacobians): per layer (P, M, K) and, for the last layer or with full_layer every layer,
+        (P, M, K, Dx) host arrays."""
+        e, P = self.engine, self.N * self.sample_size
+        xd = e.tensor(x)
+        M, Dx = x.shape
+        Js = {}
+
+        def first(nd):
+            xin = pathwalk.cols(xd, nd.input_dim)
+            return xin if nd.connect is None else torch.cat((xin, pathwalk.cols(xd, nd.connect)), 1)
+
+        def draw(l, k, nodes, xin):
+            nd = nodes[0]
+            out, g = self.nodes[l, k].value_and_grad(e, xin)
+            if l not in Js:
+                Js.pop(l - 2, None)
+                Js[l] = e.zeros(P, M, len(self.layers[l]), Dx)
+            J = Js[l][:, :, k]
+            connect = [] if nd.connect is None else list(nd.connect)
+            if l == 0:
+                _scatter_add(J, g, list(nd.input_dim) + connect)
+            else:
+                below, kd = Js[l - 1], len(nd.input_dim)
+                for i, kk in enumerate(nd.input_dim):
+                    J.addcmul_(g[:, :, i, None], below[:, :, int(kk)])
+                _scatter_add(J, g[:, :, kd:], connect)
+            return out
+
+        vals, jac, L = [], [], len(self.layers)
+        for l, cur in enumerate(pathwalk.walk(e, [self.layers] * self.N, self.sample_size, xd, None, first, draw)):
+            vals.append(cur.cpu().numpy())
+            if full_layer or l == L - 1:
+                jac.append(Js[l].cpu().numpy())
+        return vals, jac
+
+
 class GpPaths:
     """gp.sample_functions' result: paths(x, noise=False) -> (M, sample_size), column j the j-th posterior draw of the GP as
     a function, evaluated at the rows of x: any number of rows, the same values at the same rows in every call.
     noise=True adds an independent N(0, scale * nugget) term per row and path, np.random.standard_normal((sample_size, M))
-    drawn afresh on every call (the nugget that sample_paths' joint covariance carries on its diagonal)."""
+    drawn afresh on every call (the nugget that sample_paths' joint covariance carries on its diagonal).
+    paths.value_and_grad(x) -> ((M, sample_size), (M, Dx, sample_size)) and paths.grad(x) -> (M, Dx, sample_size), Dx =
+    x.shape[1]: entry [m, d, j] = d draw j at row m / d x[m, d], zero in the columns of x that the GP does not read."""
 
     def __init__(self, model, sample_size, n_features):
         k = model.kernel
@@ -218,3 +325,25 @@ class GpPaths:
         if noise:
             out = out + self.node.noise_sd() * np.random.standard_normal((J, len(x))).T
         return out
+
+    def value_and_grad(self, x):
+        """(values (M, sample_size), gradients (M, Dx, sample_size)) at the rows of x (M, Dx): values bit for bit paths(x)'s,
+        gradients[m, d, j] = d draw j at row m / d x[m, d]; the node's gradient is added into its input_dim and connect
+        columns of x, every other column is zero."""
+        paths.check_2d(x)
+        if len(x) == 0:
+            raise ValueError('sample_functions: x has no rows')
+        e, J = self.engine, self.sample_size
+        columns = list(self.input_dim) + ([] if self.connect is None else list(self.connect))
+        xin = x[:, columns]
+        M, Dx = x.shape
+        step, out, grad = _rows_per_call(e, J, 2 + 3 * xin.shape[1] + Dx), [], np.zeros((M, Dx, J))
+        for m0 in range(0, M, step):
+            f, g = self.node.value_and_grad(e, e.tensor(np.ascontiguousarray(xin[m0:m0 + step])))
+            out.append(f.cpu().numpy().T)
+            _scatter_add(grad[m0:m0 + step].transpose(0, 2, 1), g.cpu().numpy().transpose(1, 0, 2), columns)
+        return np.concatenate(out, 0), grad
+
+    def grad(self, x):
+        """value_and_grad(x)[1]."""
+        return self.value_and_grad(x)[1]

@@ -542,6 +542,21 @@ int dgpamd_pathfun_eval(dgpamd_ctx *ctx, int kind, int64_t n, int64_t M, int D, 
                         const double *Omega, const double *b, const double *theta, const double *v,
                         const double *length_h, int nlen, double scale, double *out);
 
+/* ---- input gradients of function-valued posterior draws (DESIGN I.13) --------------------------------------
+ * dgpamd_pathfun_eval's arguments and a second output: out (P x M) the values, bit for bit dgpamd_pathfun_eval's, and
+ *   out_g[p][m][d] = d out[p][m] / d x_md
+ *     = sqrt(scale) ( -sqrt(2/F) sum_f theta[p][f] Omega_fd sin(Omega_f . x_m + b_f) + sum_i v[p][i] c(x_m, W_i) q_d(x_m, W_i) ),
+ * q_d = d log c / d x_d (sexp: -2 t_d / g_d; matern2.5: -(5/3) t_d (1 + sqrt5 |t_d|) / (1 + sqrt5 |t_d| + (5/3) t_d^2) / g_d with
+ * t_d = (x_md - W_id) / g_d: zero and smooth at t_d = 0), in the node's own D input columns (P x M x D), from one pass: the sine
+ * comes from the cosine's argument reduction, the correlation and the coefficients are the value's.  Shared x with D <= 10 runs
+ * on f64 MFMA with D derivative tiles next to the generated tile; everything else one lane per row (shared x: a zero path
+ * stride, and the values from dgpamd_pathfun_eval's own kernel in a launch of its own, to keep its order of summation).  Checks and status codes as dgpamd_pathfun_eval; nothing but the two outputs is stored and no workspace is used.
+ * Each out_g[p][m][:] is one fixed sequence of operations on row m alone: the same bits whichever rows share the call. */
+int dgpamd_pathfun_grad(dgpamd_ctx *ctx, int kind, int64_t n, int64_t M, int D, int64_t F, int P, const double *x,
+                        int64_t stride_x, const int32_t *group_h, int ngroups, const double *W, int64_t stride_w,
+                        const double *Omega, const double *b, const double *theta, const double *v,
+                        const double *length_h, int nlen, double scale, double *out, double *out_g);
+
 #ifdef __cplusplus
 }
 #endif

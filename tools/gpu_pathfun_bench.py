@@ -6,7 +6,11 @@ Matern nodes -> one Matern node with `connect`, briefly trained; emulator(N=10);
   2. dgpamd_pathfun_eval alone by device events at M = 100 000, F = 2048: a first-layer node (shared rows, the MFMA kernel)
      and the output node (per-path rows, the lane kernel), priced in executed f64 operations against the 78.6 TF/s peak.
 --big: only the M = 100 000 evaluation at F = 2048 and leg 2 (for a rocprofv3 --kernel-trace --stats run of its own, and
-for comparing builds of the library through DGPAMD_LIB)."""
+for comparing builds of the library through DGPAMD_LIB).
+--grad: the input gradients alone (profiles/pathgrad_bench.txt; DESIGN I.13), F = 2048: at M = 1000, 8192 and 100 000 three
+alternating rounds of paths(x), paths.value_and_grad(x) and the forward-difference alternative (paths at x and at x + h e_d,
+d + 1 = 6 calls); then dgpamd_pathfun_grad against dgpamd_pathfun_eval by device events at M = 100 000 on a first-layer node
+(shared rows) and the output node (per-path rows)."""
 import os
 import sys
 import time
@@ -53,6 +57,47 @@ def timed(f):
     return out, 1e3 * (time.perf_counter() - t0)
 
 
+def grad_arm(emu, e, xs, N, J, n, rng):
+    P, F, d = N * J, 2048, 5
+    pf = emu.sample_functions(sample_size=J, n_features=F)
+    for M in (1000, 8192, 100000):
+        x = xs[M]
+        steps = [x] + [x + 1e-6 * np.eye(d)[k] for k in range(d)]
+        legs = [('paths(x)', lambda: pf(x)),
+                ('paths.value_and_grad(x)', lambda: pf.value_and_grad(x)),
+                ('%d x paths(x) (forward differences)' % (d + 1), lambda: [pf(xx) for xx in steps])]
+        out, (val, g) = legs[0][1](), legs[1][1]()   # warm every shape
+        legs[2][1]()
+        assert g[0].shape == (M, d, P) and np.all(np.isfinite(g[0])) and np.array_equal(out[0], val[0])
+        ms = np.zeros((3, 3))
+        for rnd in range(3):   # alternating: each round times every arm once
+            for a, (name, f) in enumerate(legs):
+                _, ms[rnd, a] = timed(f)
+                print('M = %6d, %d paths, round %d: %-36s %10.1f ms' % (M, P, rnd + 1, name, ms[rnd, a]))
+        best = ms.min(0)
+        print('M = %6d: value_and_grad / paths = %.2f, value_and_grad / %d x paths = %.3f (fastest round of each)'
+              % (M, best[1] / best[0], d + 1, best[1] / best[2]))
+    M = 100000
+    xd = e.tensor(xs[M])
+    for (l, k), shared in (((0, 0), True), ((1, 0), False)):
+        nf = pf.nodes[l, k]
+        D = nf.Omega.shape[1]
+        xin = xd[:, :D].contiguous() if shared else e.tensor(rng.normal(size=(P, M, D)))
+        times = []
+        for f in (lambda: nf(e, xin), lambda: nf.value_and_grad(e, xin)):
+            f()
+            reps = 3
+            ev0, ev1 = e.event(), e.event()
+            e.record(ev0)
+            for _ in range(reps):
+                f()
+            e.record(ev1)
+            times.append(e.elapsed_ms(ev0, ev1) / reps)
+        print('%s rows, %s, %d paths, n = %d, F = %d, M = %d, D = %d: dgpamd_pathfun_eval %.2f ms, dgpamd_pathfun_grad %.2f ms '
+              '(%.2f x, against %d evaluations for forward differences)'
+              % ('shared' if shared else 'per-path', nf.hyper[0], P, n, F, M, D, times[0], times[1], times[1] / times[0], D + 1))
+
+
 def main():
     import bench
     from dgp_amd import emulator
@@ -65,6 +110,8 @@ def main():
     rng = np.random.default_rng(5)
     xs = {M: rng.uniform(size=(M, d)) for M in (1000, 8192, 100000)}
     emu.sample_paths(xs[1000], sample_size=J)   # (the lazily built statistics are shared by every method below)
+    if '--grad' in sys.argv:
+        return grad_arm(emu, e, xs, N, J, n, rng)
     pfs = {}
     for F in ((2048,) if big_only else (2048, 8192)):
         for label in ('first', 'second'):
