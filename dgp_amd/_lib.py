@@ -58,6 +58,7 @@ SIGNATURES = {
     'dgpamd_post': (_i, [_p, _p, _z, _i]),
     'dgpamd_collect': (_i, [_p, _i, _p, _z]),
     'dgpamd_set_graphs': (_i, [_p, _i]),
+    'dgpamd_tuning_get': (_i, [_p, C.c_char_p, _p]),
     'dgpamd_set_linkgp_direct': (_i, [_p, _i]),
     'dgpamd_set_potrf_mode': (_i, [_p, _i]),
     'dgpamd_debug_trace': (_i, [_p, _p]),

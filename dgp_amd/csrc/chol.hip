@@ -591,7 +591,7 @@ struct MegaArgs {
     const int32_t *pred;     // null, or a device word: the launch does nothing when it is non-zero
     double *piv;             // [batch][ld]: the pivots (second chain form: their logarithms are summed at the end)
     int split;               // 1 (default): a visit whose newest panel has not arrived applies the older ones first (DGPAMD_MEGA_SPLIT=0: off)
-    int nowait;              // debug (DGPAMD_MEGA_NOWAIT=1, timing only, results invalid): the chain does not wait for the workers
+    int nowait;              // debug (timing only, results invalid; the host passes 0): the chain does not wait for the workers
     int ngroups;             // The matrices are dealt into this many groups (matrix b: group b % ngroups), the XCDs as well
                              // (XCD x: group x % ngroups; 1, 2, 4 or 8), and a worker takes the tasks of its own group's
                              // matrices first: every XCD has its own L2, so with one queue for all a panel tile was fetched
@@ -689,140 +689,8 @@ __device__ __forceinline__ int wg_wait_flags_opt(const int32_t *addr, int need, 
     return *bcw;
 }
 
-// acc (column-block layout) -= P P^T for the 32-column half of P staged MK in As
-__device__ __forceinline__ void mfma_cb_half(const double *As, d4 (&acc)[4], int wave, int lane) {
-    const vlds_double *Ap = (const vlds_double *)As;
-    const int m = lane & 15, kk = lane >> 4;
-#pragma unroll
-    for (int k0 = 0; k0 < KC; k0 += 4) {
-        const double bv = -Ap[(16 * wave + m) * LDM + k0 + kk];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const double av = Ap[(16 * t + m) * LDM + k0 + kk];
-            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[t], 0, 0, 0);
-        }
-    }
-}
-
-__device__ __forceinline__ void mega_chain(const MegaArgs &g, const int b, double *As, double *Bs, DiagShared &sh, double *scratch) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lm = lane & 15, lu = lane >> 4;
-    const int crow = 16 * wave + lu, ccol = lm;
-    const int64_t ld = g.ld;
-    double *A = g.buf[BUF_A] + (int64_t)b * g.stride_a;
-    int32_t *ver = g.ver + (int64_t)b * VER_PLANES * g.nbk * g.nbk;   // buffer A's versions first
-    int32_t *wflag = &g.sync->wflag[b].v;
-    long long *tr = (g.trace && b == 0 && tid == 0) ? g.trace : nullptr;
-    __builtin_amdgcn_s_setprio(3);
-    if (tid == 0) __hip_atomic_store(&g.sync->cukey[b], cu_key(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (tr) __hip_atomic_store(&g.trace[5999], wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    Tile64 D;
-    load_cb_lower(D.v, A, ld, wave, lane, scratch);
-    __syncthreads();   // (scratch and the factor's LDS share Bs)
-    double logdet = 0.0;
-    int info = 0;
-    for (int k = 0; k < g.nbk; ++k) {
-        if (tr) tr[16 * k + 0] = wall_clock64();
-        const int64_t rem = g.n - (int64_t)k * 64;
-        const int ncol = rem >= 64 ? 64 : (rem > 0 ? (int)rem : 0);
-        double *Wk = g.ws + (int64_t)b * g.stride_ws + (int64_t)k * 4096;
-        Tile64 winv;
-        // (whether the workers' tiles for the next block have arrived is asked during the factorisation: DiagPoll)
-        const int2 need = g.chain_need[k < g.nbk - 1 ? k : 0];
-        DiagPoll poll;
-        // A[k+1][k] (lane 0), A[k+1][k+1] (lane 1); no poll in the last block (a null word: the struct itself is always handed
-        // over -- a select between its address and null kept it in scratch memory)
-        poll.f = k + 1 < g.nbk ? ver + (k + 1) * g.nbk + k + (lane == 0 ? 0 : 1) : nullptr;
-        poll.need = lane == 0 ? need.x : need.y;
-        const int bad = diag_factor(D, winv, sh, ncol, (g.trace && b == 0) ? g.trace + 1024 + 16 * k : nullptr,
-                                    &poll);
-        const int ready = sh.ready == 3;   // (read before Bs, which holds the factor's LDS, is reused)
-        if (tr) tr[16 * k + 1] = wall_clock64();
-        diag_store_inverse<true>(winv, Wk);
-        wg_publish(wflag, k + 1, tid);   // the panel tasks of this block can run
-        if (tr) tr[16 * k + 2] = wall_clock64();
-        diag_store_factor(D, A + ((int64_t)k * 64) * ld + (int64_t)k * 64, ld, ncol);   // nobody's input
-        if (bad && !info) info = k * 64 + bad;
-        if (tid < 64) {
-            const double pv = sh.piv[tid];
-            double v = (tid < ncol && pv > 0.0) ? log(pv) : 0.0;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-            logdet += v;
-        }
-        if (k + 1 == g.nbk) break;
-        // ---- the next block's inputs from the workers: A[k+1][k] and A[k+1][k+1] with the panels <= k-1 applied ----
-        if (!ready) {
-            const int32_t *addr = nullptr;
-            int nd = 0;
-            if (tid == 0) { addr = ver + (k + 1) * g.nbk + k; nd = need.x; }
-            if (tid == 1) { addr = ver + (k + 1) * g.nbk + k + 1; nd = need.y; }
-            wg_wait_flags<true>(addr, nd, 100 + k, &g.sync->status, tid);
-            if (__hip_atomic_load(&g.sync->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) break;   // (a lost hand-off ends the launch)
-        }
-        if (tr) tr[16 * k + 3] = wall_clock64();
-        double *Pg = A + ((int64_t)(k + 1) * 64) * ld + (int64_t)k * 64;
-        const double *Cn = A + ((int64_t)(k + 1) * 64) * ld + (int64_t)(k + 1) * 64;
-        const HalfTile a0 = fetch_mk_sc1(Pg, ld, tid, 0), a1 = fetch_mk_sc1(Pg, ld, tid, 1);
-        // ---- P = A[k+1][k] W_k^T, W_k straight from the registers ----
-        d4 P[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) P[t] = (d4){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            __syncthreads();
-            commit_mk(h == 0 ? a0 : a1, As, tid);
-            if ((wave >> 1) == h) {
-#pragma unroll
-                for (int I = 0; I < 4; ++I)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) Bs[(16 * I + lu + 4 * r) * LDM + 16 * (wave & 1) + lm] = (I >= wave) ? winv.v[I][r] : 0.0;
-            }
-            __syncthreads();
-            // W_k = L_kk^-1 is LOWER triangular: column tile t of P = A W_k^T takes the 16-blocks kb <= t of the sum only
-            // (40 instead of 64 MFMAs per wave: the f64 MFMA runs at the vector rate on gfx950, so the skipped zeros are time)
-            {
-                const vlds_double *Ap = (const vlds_double *)As, *Bp = (const vlds_double *)Bs;
-                const int m_ = lane & 15, kk_ = lane >> 4;
-#pragma unroll
-                for (int k0 = 0; k0 < KC; k0 += 4) {
-                    const int kb = 2 * h + (k0 >> 4);
-                    const double av = Ap[(16 * wave + m_) * LDM + k0 + kk_];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t)
-                        if (t >= kb) P[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, Bp[(16 * t + m_) * LDM + k0 + kk_], P[t], 0, 0, 0);
-                }
-            }
-        }
-        if (tr) tr[16 * k + 4] = wall_clock64();
-        store_acc_sc1(P, Pg, ld, crow, ccol);
-        __syncthreads();   // (Bs, which holds the transposition scratch, is no longer read)
-        Tile64 Dn;         // loaded only now: the registers of W_k and of the panel tile's halves are free again
-        load_cb_lower<true>(Dn.v, Cn, ld, wave, lane, scratch);
-        // ---- D = A[k+1][k+1] - P P^T in the column-block layout; the panel tile is published between the halves ----
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            if (h == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // P's stores have drained by now
-            __syncthreads();
-            if (h == 1 && tid == 0)
-                __hip_atomic_store(ver + (k + 1) * g.nbk + k, VER_FINAL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) As[(crow + 4 * r) * LDM + 16 * t + ccol] = P[2 * h + t][r];
-            __syncthreads();
-            mfma_cb_half(As, Dn.v, wave, lane);
-        }
-        D = Dn;
-        if (tr) tr[16 * k + 5] = wall_clock64();
-    }
-    if (tid == 0) {
-        __hip_atomic_store(g.logdet + b, logdet, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(g.info + b, info, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// ---- the chain, second form (round 4) -------------------------------------------------------------------------------
-// The same arithmetic as mega_chain in the same order (bit-identical results), re-arranged around what bounded the block
+// ---- the chain ------------------------------------------------------------------------------------------------------------
+// The arithmetic of the chain of rounds 2-3 in the same order (bit-identical results), arranged around what bounded its block
 // step (profiles/r03_potrf_phase_trace.txt: 7.0 factor + 0.8 publish + 2.0 wait + 1.7 solve + 3.5 update):
 //   * the solve produces P^T in the accumulator layout, P^T = W_k Q^T (operands swapped: the same products in the same order).
 //     An accumulator tile is, register for register, an MFMA operand of the next product (the layout duality diagfac.hpp
@@ -882,22 +750,6 @@ __device__ __forceinline__ void store_pt_sc1(const d4 (&P)[4], double *Pg, int64
     // soffset is a register: the constants above 64 used to be materialised in SGPRs).  The registers of their own and the
     // wait states below stay; tests/test_isa_hazards.py reads the shipped code and fails when a data register of any 16-byte store
     // of the kernel is rewritten too early, or when a store's soffset is a register again.
-    // (-DMEGA_DIAG_OLD_STORE=1: round 4's first form -- one set of data registers, offsets in SGPRs -- for the one-fix-at-a-time
-    //  stress of profiles/r05_hazard_one_fix_at_a_time.txt; never in a shipped build)
-#if defined(MEGA_DIAG_OLD_STORE) && MEGA_DIAG_OLD_STORE
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int rp = 0; rp < 2; ++rp) {
-            const double x = P[t][2 * rp], y = P[t][2 * rp + 1];
-            const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)__double2loint(x), (unsigned)__double2loint(y), false, false);
-            const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)__double2hiint(x), (unsigned)__double2hiint(y), false, false);
-            u32x4 v1;
-            v1.x = lo[0]; v1.y = hi[0]; v1.z = lo[1]; v1.w = hi[1];
-            __builtin_amdgcn_raw_buffer_store_b128(v1, rs, base, (16 * t + 8 * rp) * 8, 16);
-        }
-    return;
-#endif
     u32x4 v[8];
 #pragma unroll
     for (int t = 0; t < 4; ++t)
@@ -1103,17 +955,10 @@ __device__ __forceinline__ void mega_chain2(const MegaArgs &g, const int b, doub
         if (ready != 3) {
             if (tid < 2 && !((ready >> tid) & 1)) {
                 const int got = __hip_atomic_load(ver + (k + 1) * g.nbk + k + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#if defined(MEGA_DIAG_OLD_LOOK) && MEGA_DIAG_OLD_LOOK   // (round 4's first form, for the one-fix-at-a-time stress only)
-                if (got >= (tid == 0 ? need.x : need.y)) atomicOr(&sh.ready, 1 << tid);
-            }
-            lds_barrier();
-            ready2 = g.nowait ? 3 : sh.ready;
-#else
                 if (got >= (tid == 0 ? need.x : need.y)) atomicOr(&sh.look, 1 << tid);
             }
             lds_barrier();
             ready2 = g.nowait ? 3 : (ready | sh.look);
-#endif
         }
         bool published = false;
         if (!(ready2 & 1)) {
@@ -1260,32 +1105,21 @@ __device__ __noinline__ int mega_pull(MegaSync *sync, int grp, int nbg, int nut,
     return -1;
 }
 
-#ifndef MEGA_V2
-#define MEGA_V2 1   // 0: the chain of rounds 2-3 (mega_chain), kept for same-box comparisons
-#endif
 __global__ __launch_bounds__(256, 2) void potrf_mega_kernel(MegaArgs g) {
     __shared__ double tiles[2 * 64 * LDM];   // As | Bs (workers); the chain's whole panel tile Q, then its register exchange
     __shared__ int32_t bc[4];
     double *As = tiles, *Bs = tiles + 64 * LDM;
-#if MEGA_V2
     // the chain keeps W_k and the factor's LDS beside the panel tile (79.8 KB per workgroup: two workgroups per CU still fit 160 KB)
     __shared__ double wtile[64 * LDQ];
     __shared__ DiagShared dsh;
     static_assert(64 * LDQ <= 2 * 64 * LDM, "the chain's panel tile must fit the workers' staging tiles");
     static_assert(2 * (sizeof(double) * (2 * 64 * LDM + 64 * LDQ) + sizeof(DiagShared) + 16) <= 160 * 1024, "two workgroups per CU");
-#else
-    DiagShared &sh = *reinterpret_cast<DiagShared *>(Bs);   // (idle while a chain workgroup factors)
-#endif
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int crow = 16 * wave + (lane >> 4), ccol = lane & 15;
     const int batch = g.batch;
     if (g.pred && *g.pred) return;   // (a speculative batch that an earlier one has made unnecessary: dgpamd_ess_queue)
     if ((int)blockIdx.x < batch) {
-#if MEGA_V2
         mega_chain2(g, blockIdx.x, tiles, wtile, dsh);
-#else
-        mega_chain(g, blockIdx.x, As, Bs, sh, &sh.u[0][0][0]);
-#endif
     } else {
         // a worker beside a chain leaves (bounded wait for the chains' keys: they are dispatched first)
         if (tid < 64) {
@@ -1897,8 +1731,8 @@ static int mega_wgs_per_cu();
 static int get_mega_tasks(dgpamd_ctx *ctx, int nbk, bool inv, int batch, MegaTable *&out) {
     // Panels per visit: 8 (trailing and K^-1 tiles), 10 from six matrices on; the cadence starts three columns to the right
     // of the chain (near = 2).  Measured at n = 2000 (tools/gpu_lazy_sweep.py, profiles/r02_mega_table_sweeps.txt).
-    // DGPAMD_MEGA_LAZY / _SLAZY / _NEAR / _LAG / _XCATCH / _STAIL override (tuning only).
-    const char *lz = getenv("DGPAMD_MEGA_LAZY"), *sz = getenv("DGPAMD_MEGA_SLAZY");
+    // DGPAMD_MEGA_LAZY / _SLAZY / _NEAR / _LOOK / _SLAG / _QUEUES / _NCRIT override (tuning only; ctx->tune).
+    const Tuning &tn = ctx->tune;
     const bool deep = batch >= 6;
     // (n = 5000, ten matrices with their inverses: 25.9 ms at 8 panels per visit, 25.3 at 12, 25.4 at 16 -- 49 TFLOP/s; one matrix is
     //  fastest at 8: the chain waits for deeper visits)
@@ -1908,31 +1742,24 @@ static int get_mega_tasks(dgpamd_ctx *ctx, int nbk, bool inv, int batch, MegaTab
     // the inverse nothing moved (near = 3 costs one matrix 0.06 ms).
     const int deep_lazy = (nbk >= 64 || inv) ? 12 : 10;
     const int shallow = inv ? 10 : MEGA_LAZY, sshallow = inv ? 10 : MEGA_SLAZY;
-    const int lazy = lz && atoi(lz) > 0 ? atoi(lz) : (deep ? deep_lazy : shallow), slazy = sz && atoi(sz) > 0 ? atoi(sz) : (deep ? deep_lazy : sshallow);
-    const char *en = getenv("DGPAMD_MEGA_NEAR"), *el = getenv("DGPAMD_MEGA_LAG"), *ex = getenv("DGPAMD_MEGA_XCATCH");
-    const char *es = getenv("DGPAMD_MEGA_STAIL");
+    const int lazy = tn.mega_lazy ? (int)tn.mega_lazy : (deep ? deep_lazy : shallow), slazy = tn.mega_slazy ? (int)tn.mega_slazy : (deep ? deep_lazy : sshallow);
     // (a task waits on 1 + 2 nkb version words, one per lane of ONE wave: the overrides are clamped so that the deepest visit --
     //  lazy + 1 + near + lag panels -- stays within 64 flags, and build_mega_tasks' output is checked below)
     // Round 5 (profiles/r05_mega_table_sweeps.txt): with the newest panel of a visit applied on its own (kernel, `split`) the solves can
     // leave more panels to themselves without lengthening the recursion along a row of tiles, and a column's last deep visit
     // then lies four block steps ahead of its solves: three columns' distance (near = 3) at every batch size.
-    const int near_raw = en ? atoi(en) : 3, lag_raw = el ? atoi(el) : 0;
-    const int near = near_raw < 0 ? 0 : (near_raw > 6 ? 6 : near_raw), lag = lag_raw < 0 ? 0 : (lag_raw > 2 ? 2 : lag_raw), xcatch = (ex ? atoi(ex) : 0) + 2 * (es ? atoi(es) : (inv && batch <= 3 ? 1 : 0));
-    const char *elk = getenv("DGPAMD_MEGA_LOOK");   // 0: the look-ahead as three tasks (rounds 2-3)
-    const int look = elk ? (atoi(elk) != 0) : 1;
-    const char *esl = getenv("DGPAMD_MEGA_SLAG");
-    const int slag = esl ? (atoi(esl) < 0 ? 0 : (atoi(esl) > 8 ? 8 : atoi(esl))) : 0;
+    const int near = (int)tn.mega_near, lag = 0, xcatch = 2 * (inv && batch <= 3 ? 1 : 0);   // (xcatch bit 1: the shrinking K^-1 threshold, `stail`)
+    const int look = (int)tn.mega_look;   // 0: the look-ahead as three tasks (rounds 2-3)
+    const int slag = (int)tn.mega_slag;
     // Two queues (critical lane + bulk) up to three matrices, one from four on.  (Re-measured after the synchronisation block's words got lines of their own,
     // profiles/r05_mega_table_sweeps.txt: most of what the critical queue had gained at four and more matrices was that ITS head did not share the line of the W
     // counters -- with every word on its own line one queue is 1-5 % faster there, the two still 1.5-3 % at one to three.)
-    const char *eq = getenv("DGPAMD_MEGA_QUEUES");   // 1: one queue per group of matrices (rounds 2-4); 2: critical + bulk
-    int queues = eq ? (atoi(eq) == 1 ? 1 : 2) : (batch <= 3 ? 2 : 1);
+    int queues = tn.mega_queues ? (int)tn.mega_queues : (batch <= 3 ? 2 : 1);   // 1: one queue per group of matrices (rounds 2-4); 2: critical + bulk
     {
         // The two-queue form needs workers of BOTH kinds: the kernel makes the first 8 x crit_per_xcd workers critical-first (crit_per_xcd =
         // ceil(ncrit x matrices / 8), at most 16) and everybody else bulk-first.  On a small or CU-masked device every worker would be critical-first,
         // run ahead into later block steps and wait there for bulk tiles that nobody pulls -- until the spin limit trips.  One queue then.
-        const int ncrit_env = getenv("DGPAMD_MEGA_NCRIT") ? atoi(getenv("DGPAMD_MEGA_NCRIT")) : 0;
-        const int ncrit = ncrit_env > 0 ? ncrit_env : (batch <= 4 ? 12 : 8);
+        const int ncrit = tn.mega_ncrit ? (int)tn.mega_ncrit : (batch <= 4 ? 12 : 8);
         int crit = (ncrit * batch + 7) / 8;
         if (crit > 16) crit = 16;
         const int64_t workers = (int64_t)mega_wgs_per_cu() * ctx->num_cu - batch;
@@ -2007,30 +1834,21 @@ static int potrf_mega_launch(dgpamd_ctx *ctx, int64_t n, double *A, double *T, d
     g.inv = T != nullptr;
     g.tasks = mt->dev; g.ntask = mt->ntask; g.chain_need = mt->need_dev;
     g.nut = mt->nut;
-    {
-        // (workers of the critical queue per matrix: one per task of a block step, and a few more while the engine has room)
-        static const int ncrit_env = getenv("DGPAMD_MEGA_NCRIT") ? atoi(getenv("DGPAMD_MEGA_NCRIT")) : 0;
-        g.ncrit = ncrit_env > 0 ? ncrit_env : (batch <= 4 ? 12 : 8);
-    }
+    // (workers of the critical queue per matrix: one per task of a block step, and a few more while the engine has room)
+    g.ncrit = ctx->tune.mega_ncrit ? (int)ctx->tune.mega_ncrit : (batch <= 4 ? 12 : 8);
     g.sync = reinterpret_cast<MegaSync *>(syncmem);
     g.ver = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(syncmem) + sizeof(MegaSync));
     g.logdet = logdet; g.info = info; g.trace = ctx->trace; g.pred = ctx->pred; g.piv = piv;
     g.tlog = (ctx->tlog && 64 + 8 * ((int64_t)batch * nbk + (int64_t)batch * mt->ntask) <= ctx->tlog_words) ? ctx->tlog : nullptr;
+    g.nowait = 0;
+    g.split = (int)ctx->tune.mega_split;
     {
-        static const int nowait = getenv("DGPAMD_MEGA_NOWAIT") ? atoi(getenv("DGPAMD_MEGA_NOWAIT")) : 0;
-        g.nowait = nowait;
-        static const int split = getenv("DGPAMD_MEGA_SPLIT") ? atoi(getenv("DGPAMD_MEGA_SPLIT")) : 1;
-        g.split = split;
-    }
-    {
-        const char *eg = getenv("DGPAMD_MEGA_GROUPS");
         // (measured at n = 2000, tools/gpu_lazy_sweep.py: uneven groups are fine -- an XCD whose own queue has run out takes
         // from the others -- so odd batches use two groups as well: potrf_inv -10 % at 3 matrices, -7 % at 6, -12 % at 12)
         // (round 5, same sweeps: three matrices with the inverse, and odd batches without it, are 3-5 % faster as ONE group -- two groups of 2 + 1 or 3 + 2
         //  matrices leave half the XCDs with the smaller share until their queue runs out)
         const bool one_group = (batch & 1) && (batch == 3 || !g.inv);
-        int G = eg ? atoi(eg) : (one_group ? 1 : batch % 8 == 0 ? 8 : batch % 4 == 0 ? 4 : batch >= 2 ? 2 : 1);
-        if (G != 1 && G != 2 && G != 4 && G != 8) G = 1;
+        int G = ctx->tune.mega_groups ? (int)ctx->tune.mega_groups : (one_group ? 1 : batch % 8 == 0 ? 8 : batch % 4 == 0 ? 4 : batch >= 2 ? 2 : 1);
         while (G > batch) G >>= 1;
         g.ngroups = G;
     }

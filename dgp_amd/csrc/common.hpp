@@ -18,8 +18,18 @@
 enum { PROF_NONE = 0, PROF_KMATRIX = 1, PROF_POTRF_DIAG = 2, PROF_TRSM = 3, PROF_SYRK = 4, PROF_TRTRI = 5,
        PROF_LAUUM = 6, PROF_GRAD = 7, PROF_LINKGP_J = 8, PROF_GP_QUAD = 9 };
 
+// The DGPAMD_* switches of the C library as dgpamd_create found them (context.hip holds the one table: names, defaults, accepted
+// values).  A context keeps the switches it was created under.  0 stands for "unset" where the default depends on the call.
+struct Tuning {
+    int64_t potrf_mode, fetch_spin, llik_args_copy;
+    int64_t mega_lazy, mega_slazy, mega_near, mega_look, mega_slag, mega_queues, mega_ncrit, mega_split, mega_groups;
+    int64_t jsep_tch, jsexp_tch, pair_chunk, sexp_form1, sexp_poly, jsep_pipe, jsep_log, jsep_noclass, jsep_diag;
+    int64_t nn_filter, nn_store_once, vecchia_lds, poison_lds;
+};
+
 struct dgpamd_ctx {
     int device;
+    Tuning tune;
     int num_cu;                                       // compute units of the device (workgroups i and i + num_cu share one)
     hipStream_t stream;
     bool own_stream;

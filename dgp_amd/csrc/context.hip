@@ -9,6 +9,66 @@ extern "C" const char *dgpamd_version(void) { return "dgp_amd 0.1 (gfx950)"; }
 
 extern "C" int64_t dgpamd_padded_dim(int64_t n) { return padded_dim(n); }
 
+// ---------------------------------------------------------------------------
+// The DGPAMD_* switches of the C library: ONE table, read by dgpamd_create and nowhere else.  Each row: the variable, the
+// field of Tuning it fills, the value when it is unset, and the rule that turns its text into the value (what is accepted, and
+// what an unaccepted value becomes).  INTEGRATION.md lists the same rows with what they are for.
+// ---------------------------------------------------------------------------
+static int64_t sw_present(const char *) { return 1; }                          // set at all, whatever the text
+static int64_t sw_unless0(const char *s) { return s[0] == '0' ? 0 : 1; }       // off only by a leading '0'
+static int64_t sw_nonzero(const char *s) { return atoll(s) != 0; }
+static int64_t sw_int(const char *s) { return atoll(s); }
+template <int64_t LO, int64_t HI>
+static int64_t sw_clamp(const char *s) { const int64_t v = atoll(s); return v < LO ? LO : (v > HI ? HI : v); }
+template <int64_t LO, int64_t HI, int64_t STEP, int64_t ELSE>                   // LO..HI in steps of STEP, anything else: ELSE
+static int64_t sw_range(const char *s) { const int64_t v = atoll(s); return v >= LO && v <= HI && v % STEP == 0 ? v : ELSE; }
+template <int64_t LO, int64_t HI, int64_t ELSE>                                 // a power of two in LO..HI, anything else: ELSE
+static int64_t sw_pow2(const char *s) { const int64_t v = atoll(s); return v >= LO && v <= HI && (v & (v - 1)) == 0 ? v : ELSE; }
+
+static const struct Switch {
+    const char *name;
+    int64_t Tuning::*field;
+    int64_t unset;
+    int64_t (*parse)(const char *);
+} SWITCHES[] = {
+    {"DGPAMD_POTRF_MODE", &Tuning::potrf_mode, 1, sw_unless0},                        // 0: per-block-step launches, e.g. on a shared device
+    {"DGPAMD_FETCH_SPIN", &Tuning::fetch_spin, 1, sw_unless0},                        // 0: dgpamd_fetch sleeps in hipStreamSynchronize
+    {"DGPAMD_LLIK_ARGS_COPY", &Tuning::llik_args_copy, 0, sw_nonzero},
+    {"DGPAMD_MEGA_LAZY", &Tuning::mega_lazy, 0, sw_range<1, INT32_MAX, 1, 0>},        // (unset: by batch / inv)
+    {"DGPAMD_MEGA_SLAZY", &Tuning::mega_slazy, 0, sw_range<1, INT32_MAX, 1, 0>},      // (unset: by batch / inv)
+    {"DGPAMD_MEGA_NEAR", &Tuning::mega_near, 3, sw_clamp<0, 6>},
+    {"DGPAMD_MEGA_LOOK", &Tuning::mega_look, 1, sw_nonzero},                          // 0: the look-ahead as three tasks (rounds 2-3)
+    {"DGPAMD_MEGA_SLAG", &Tuning::mega_slag, 0, sw_clamp<0, 8>},
+    {"DGPAMD_MEGA_QUEUES", &Tuning::mega_queues, 0, sw_range<1, 1, 1, 2>},            // 1: one queue per group of matrices; anything else: critical + bulk (unset: by batch)
+    {"DGPAMD_MEGA_NCRIT", &Tuning::mega_ncrit, 0, sw_range<1, INT32_MAX, 1, 0>},      // (unset: by batch)
+    {"DGPAMD_MEGA_SPLIT", &Tuning::mega_split, 1, sw_int},
+    {"DGPAMD_MEGA_GROUPS", &Tuning::mega_groups, 0, sw_pow2<1, 8, 1>},                // (unset: by batch / inv)
+    {"DGPAMD_JSEP_TCH", &Tuning::jsep_tch, 0, sw_range<8, 256, 8, 0>},                // (unset: the built-in points per workgroup)
+    {"DGPAMD_JSEXP_TCH", &Tuning::jsexp_tch, 0, sw_pow2<64, 256, 0>},                 // (unset: by the number of tiles)
+    {"DGPAMD_PAIR_CHUNK", &Tuning::pair_chunk, 0, sw_int},                            // (unset: as many points per launch as the records allow)
+    {"DGPAMD_SEXP_FORM1", &Tuning::sexp_form1, 0, sw_present},
+    {"DGPAMD_SEXP_POLY", &Tuning::sexp_poly, 0, sw_present},                          // (comparison run: the table-free exponential)
+    {"DGPAMD_JSEP_PIPE", &Tuning::jsep_pipe, 2, sw_int},
+    {"DGPAMD_JSEP_LOG", &Tuning::jsep_log, 0, sw_present},
+    {"DGPAMD_JSEP_NOCLASS", &Tuning::jsep_noclass, 0, sw_present},
+    {"DGPAMD_JSEP_DIAG", &Tuning::jsep_diag, 0, sw_int},
+    {"DGPAMD_NN_FILTER", &Tuning::nn_filter, 1, sw_unless0},                          // 0: the streaming top-k kernel at prediction sizes
+    {"DGPAMD_NN_STORE_ONCE", &Tuning::nn_store_once, 0, sw_int},                      // 1 / 2: force the store-once / the streaming kernels
+    {"DGPAMD_VECCHIA_LDS", &Tuning::vecchia_lds, 0, sw_nonzero},                      // 1: the LDS version of the row kernels for every size
+    {"DGPAMD_POISON_LDS", &Tuning::poison_lds, 0, sw_int},                            // non-zero: NaNs into every CU's LDS before each row launch (2: ops.py, before every call)
+};
+
+extern "C" int dgpamd_tuning_get(dgpamd_ctx *ctx, const char *name, int64_t *value) {
+    if (!ctx || !name || !value) return DGPAMD_BAD_ARG;
+    if (strncmp(name, "DGPAMD_", 7) == 0) name += 7;   // (with or without the prefix)
+    for (const Switch &sw : SWITCHES)
+        if (strcmp(name, sw.name + 7) == 0) {
+            *value = ctx->tune.*sw.field;
+            return DGPAMD_OK;
+        }
+    BAD_ARG(ctx, "no such switch");
+}
+
 extern "C" int dgpamd_create(int device, void *stream, dgpamd_ctx **out) {
     if (!out) return DGPAMD_BAD_ARG;
     *out = nullptr;
@@ -24,9 +84,12 @@ extern "C" int dgpamd_create(int device, void *stream, dgpamd_ctx **out) {
     ctx->prof_work = 0.0;
     ctx->use_graphs = 1;
     ctx->linkgp_direct = 0;
-    ctx->potrf_mode = 1;
+    for (const Switch &sw : SWITCHES) {
+        const char *text = getenv(sw.name);
+        ctx->tune.*sw.field = text ? sw.parse(text) : sw.unset;
+    }
+    ctx->potrf_mode = (int)ctx->tune.potrf_mode;
     ctx->pred = nullptr;
-    if (const char *pm = getenv("DGPAMD_POTRF_MODE")) ctx->potrf_mode = (pm[0] == '0') ? 0 : 1;   // (0: per-block-step launches, e.g. on a shared device)
     ctx->trace = nullptr;
     {
         int ncu = 0;
@@ -223,8 +286,7 @@ extern "C" int dgpamd_fetch(dgpamd_ctx *ctx, const void *device_src, void *host_
     if (!ctx) return DGPAMD_BAD_ARG;
     if (!device_src || !host_dst) BAD_ARG(ctx, "null pointer");
     if (bytes == 0) return DGPAMD_OK;
-    static const bool spin = !(getenv("DGPAMD_FETCH_SPIN") && getenv("DGPAMD_FETCH_SPIN")[0] == '0');
-    if (spin && bytes <= MAIL_KERNEL_MAX) {   // the few words a sampler / optimiser step returns: no sleep, no wake-up
+    if (ctx->tune.fetch_spin && bytes <= MAIL_KERNEL_MAX) {   // the few words a sampler / optimiser step returns: no sleep, no wake-up
         int rc = mail_post(ctx, ctx->mail[DGPAMD_MAILBOXES], device_src, bytes);
         if (rc) return rc;
         return mail_collect(ctx, ctx->mail[DGPAMD_MAILBOXES], host_dst, bytes);

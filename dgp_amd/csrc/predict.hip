@@ -7,17 +7,12 @@
 #include "common.hpp"
 #include "tile.hpp"
 #include "linkfun.hpp"
+#include "wave.hpp"
 
 #include <math.h>
 
 #define MC_MAX 2048   // test points per workspace chunk
 #define TCH 32        // test points per linked-GP workgroup
-
-__device__ __forceinline__ double wave_sum_p(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
 
 // ---------------------------------------------------------------------------
 // r[i][t] = k(W_i, x_t)   (K_vec_nb, vecchia.py:244-265)
@@ -269,7 +264,7 @@ __global__ __launch_bounds__(256) void linkgp_mean_kernel(LinkArgs a) {
         }
         acc = fma(I, ud ? a.ry[i] - cd * ud[i] : a.ry[i], acc);
     }
-    acc = wave_sum_p(acc);
+    acc = wave_sum(acc);
     if (lane == 0) part[wave] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -444,7 +439,7 @@ __global__ __launch_bounds__(256) void linkgp_J_kernel(LinkArgs a) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) acc = fma(Cr[p][q], exp(-e[p][q]), acc);
             }
-            acc = wave_sum_p(acc);
+            acc = wave_sum(acc);
             if (lane == 0) red[t * 4 + wave] = acc;
         }
     } else {
@@ -478,7 +473,7 @@ __global__ __launch_bounds__(256) void linkgp_J_kernel(LinkArgs a) {
                 if (Dz) prod *= pi_ * pj * exp(-SQRT5 * (si + sj));
                 acc = fma(cij, prod, acc);
             }
-            acc = wave_sum_p(acc);
+            acc = wave_sum(acc);
             if (lane == 0) red[t * 4 + wave] = acc;
         }
     }
@@ -625,7 +620,7 @@ __global__ __launch_bounds__(256, 3) void linkgp_Jsexp_kernel(LinkArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc = fma(Cr[tt][r], exp_negated(e[tt][r] + rr[r] + ss), acc);
         }
-        acc = wave_sum_p(acc);
+        acc = wave_sum(acc);
         if (lane == 0) red[t * 4 + wave] = acc;
     }
     __syncthreads();
@@ -823,7 +818,7 @@ __global__ __launch_bounds__(256, 2) void linkgp_Jsexp2_kernel(LinkArgs a) {
             }
             __builtin_amdgcn_sched_barrier(0);
         }
-        acc = wave_sum_p(acc);
+        acc = wave_sum(acc);
         if (lane == 0) red[t * 4 + wave] = acc;
     };
     if (nt > 0) {
@@ -1198,7 +1193,7 @@ __global__ __launch_bounds__(256, 2) void linkgp_Jsep_kernel(LinkArgs a) {
         for (int tt = 0; tt < 4; ++tt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc = fma(Cr[tt][r], prod[tt][r] * gr[r] * gc[tt], acc);
-        acc = wave_sum_p(acc);
+        acc = wave_sum(acc);
         if (lane == 0) red[t * 4 + wave] = acc;
     }
     // (the compiler's barrier waits for LDS and scalar traffic only -- s_waitcnt lgkmcnt(0); s_barrier; s_endpgm in the emitted code: the last step's redundant
@@ -1224,7 +1219,7 @@ __global__ __launch_bounds__(256) void linkgp_finalize_kernel(LinkArgs a, int nt
     if (tt >= a.Mc || t >= a.M) return;
     double s = 0.0;
     for (int b = lane; b < ntiles; b += 64) s += a.partial[(int64_t)b * a.Mc + tt];
-    s = wave_sum_p(s);
+    s = wave_sum(s);
     if (lane) return;
     if (KIND == DGPAMD_SEXP) {
         double c = 1.0;
@@ -1254,28 +1249,15 @@ static int64_t sexp_rec_doubles(int64_t nb, int Dw) { return (int64_t)(((Dw + 2 
 
 // Test points per workgroup of linkgp_Jsexp2_kernel: a workgroup's set-up (the tile's weights and base exponents) is amortised over them -- 256 where a launch of
 // MC_MAX points still has 32 rounds of workgroups (n = 5000: 28.5 -> 27.4 ms per 2048 points), 128 below (n = 2000: 256 would leave 8 rounds and cost 6 %).
-static int sexp_tch2(int64_t nb) {
-    if (getenv("DGPAMD_JSEXP_TCH")) {
-        const int c = atoi(getenv("DGPAMD_JSEXP_TCH"));
-        if (c == 64 || c == 128 || c == 256) return c;
-    }
-    return nb * (nb + 1) / 2 * (MC_MAX / 256) >= 32 * 512 ? 256 : TCH2;
-}
+static int sexp_tch2(int64_t nb) { return nb * (nb + 1) / 2 * (MC_MAX / 256) >= 32 * 512 ? 256 : TCH2; }
 
-static int jsep_tch() {   // test points per workgroup of linkgp_Jsep_kernel (DGPAMD_JSEP_TCH: comparison runs)
-    if (getenv("DGPAMD_JSEP_TCH")) {
-        const int c = atoi(getenv("DGPAMD_JSEP_TCH"));
-        if (c >= 8 && c <= 256 && c % 8 == 0) return c;
-    }
-    return TCHS;
-}
-
+// (no context, no switch: the built-in geometry.  linkgp_run never puts more points into a launch than this sizes records for.)
 extern "C" size_t dgpamd_linkgp_workspace(int64_t n, int64_t M, int Dw) {
     int64_t nb = (n + 63) / 64;
     int64_t Mc = ((M + TCH - 1) / TCH) * TCH;
     if (Mc > MC_MAX) Mc = MC_MAX;
     // (the records of one launch: the larger of the Matern and the SExp form's -- the call's kind is not known here)
-    int64_t recs = pair_chunk(nb, Mc, Dw, jsep_tch(), matern_rec_doubles(nb, Dw)) * matern_rec_doubles(nb, Dw);
+    int64_t recs = pair_chunk(nb, Mc, Dw, TCHS, matern_rec_doubles(nb, Dw)) * matern_rec_doubles(nb, Dw);
     {
         const int64_t r2 = pair_chunk(nb, Mc, Dw, sexp_tch2(nb), sexp_rec_doubles(nb, Dw)) * sexp_rec_doubles(nb, Dw);
         if (r2 > recs) recs = r2;
@@ -1303,7 +1285,8 @@ static int linkgp_run(dgpamd_ctx *ctx, int kind, int64_t n, int64_t M, int Dw, i
     a.drop = drop;
     a.no_order_classes = 0;
     a.dbg = nullptr;
-    a.tch = jsep_tch();
+    const Tuning &tn = ctx->tune;
+    a.tch = tn.jsep_tch ? (int)tn.jsep_tch : TCHS;   // test points per workgroup of linkgp_Jsep_kernel (DGPAMD_JSEP_TCH: comparison runs)
     int64_t Mc = ((M + TCH - 1) / TCH) * TCH;
     if (Mc > MC_MAX) Mc = MC_MAX;
     const int nb = (int)((n + 63) / 64), ntiles = nb * (nb + 1) / 2;
@@ -1312,13 +1295,21 @@ static int linkgp_run(dgpamd_ctx *ctx, int kind, int64_t n, int64_t M, int Dw, i
     a.recs = a.partial + (int64_t)ntiles * Mc;
     a.npad = (int64_t)nb * 64;
     const bool sx2 = (kind == DGPAMD_SEXP) && !direct && Dw + 2 <= 16;
-    if (sep) Mc = pair_chunk(nb, Mc, Dw, a.tch, matern_rec_doubles(nb, Dw));   // records of one chunk: Mc*Dw*npad*240 B (Matern), Mc*npad*(Dw+3..6)*8 B (SExp)
-    if (sx2) {
-        a.tch = sexp_tch2(nb);
-        Mc = pair_chunk(nb, Mc, Dw, a.tch, sexp_rec_doubles(nb, Dw));
+    // records of one chunk: Mc*Dw*npad*240 B (Matern), Mc*npad*(Dw+3..6)*8 B (SExp).  Under a DGPAMD_JSEP_TCH / _JSEXP_TCH override the chunk
+    // stays within what dgpamd_linkgp_workspace sized records for (the built-in points per workgroup).
+    if (sep) {
+        const int64_t sized = pair_chunk(nb, Mc, Dw, TCHS, matern_rec_doubles(nb, Dw));
+        Mc = pair_chunk(nb, Mc, Dw, a.tch, matern_rec_doubles(nb, Dw));
+        if (Mc > sized) Mc = sized;
     }
-    if (getenv("DGPAMD_PAIR_CHUNK") && (sep || sx2)) {   // (comparison runs: the fixed 256 points per launch of the earlier builds)
-        const int64_t c = atoll(getenv("DGPAMD_PAIR_CHUNK"));
+    if (sx2) {
+        const int64_t sized = pair_chunk(nb, Mc, Dw, sexp_tch2(nb), sexp_rec_doubles(nb, Dw));
+        a.tch = tn.jsexp_tch ? (int)tn.jsexp_tch : sexp_tch2(nb);
+        Mc = pair_chunk(nb, Mc, Dw, a.tch, sexp_rec_doubles(nb, Dw));
+        if (Mc > sized) Mc = sized;
+    }
+    if (sep || sx2) {   // (DGPAMD_PAIR_CHUNK, comparison runs: the fixed 256 points per launch of the earlier builds)
+        const int64_t c = tn.pair_chunk;
         if (c >= TCH && c < Mc) Mc = c / TCH * TCH;
     }
     a.Mc = Mc;
@@ -1338,7 +1329,7 @@ static int linkgp_run(dgpamd_ctx *ctx, int kind, int64_t n, int64_t M, int Dw, i
     if (tcj != TCH) shm = j_lds(tcj);
     // SExp: the second form up to Dw = 14; the first form (MFMA) above, while it fits in a CU's LDS (to Dw = 39..48, by Dz);
     // past that the direct kernel (99 KB at Dw = 64)
-    const bool sexp2 = sx2 && !getenv("DGPAMD_SEXP_FORM1");
+    const bool sexp2 = sx2 && !tn.sexp_form1;
     const int KP = (Dw + 3) & ~3, LDU = KP + 2;
     const size_t shm_s = ((size_t)2 * DT * 64 + (size_t)KP * LDK + (size_t)TCH * (2 * Dw + Dz) + TCH * 4 + 2 * 64 * LDU + 4 * 64 + Dz) * sizeof(double);
     const bool sexp1 = kind == DGPAMD_SEXP && !direct && !sexp2 && shm_s <= LDS_CU_BYTES;
@@ -1371,7 +1362,7 @@ static int linkgp_run(dgpamd_ctx *ctx, int kind, int64_t n, int64_t M, int Dw, i
             } else if (sexp2) {
                 const int KPA = (Dw + 2 + 3) & ~3;
                 const size_t shm2 = ((size_t)2 * Dw * 64 + a.tch * 4 + EXPN_TAB) * sizeof(double);
-                const bool poly = getenv("DGPAMD_SEXP_POLY") != nullptr;   // (comparison run: the table-free exponential)
+                const bool poly = tn.sexp_poly != 0;   // (comparison run: the table-free exponential)
                 const unsigned tb2 = (unsigned)((mc + a.tch - 1) / a.tch);
                 hipLaunchKernelGGL(sexp_records_kernel, dim3((unsigned)((a.npad + 255) / 256), (unsigned)mc), dim3(256), 0, ctx->stream, a, KPA);
                 PROF_BEGIN(ctx, PROF_LINKGP_J, (double)mc * (double)n * (double)(n + 1) * 0.5);   // pair evaluations (one exponential each)
@@ -1401,11 +1392,11 @@ static int linkgp_run(dgpamd_ctx *ctx, int kind, int64_t n, int64_t M, int Dw, i
             } else if (direct) {
                 hipLaunchKernelGGL((linkgp_J_kernel<DGPAMD_MATERN25, false>), dim3(ntiles, tb), dim3(256), shm, ctx->stream, a);
             } else {
-                const int pipe = getenv("DGPAMD_JSEP_PIPE") ? atoi(getenv("DGPAMD_JSEP_PIPE")) : 2;
+                const int pipe = (int)tn.jsep_pipe;
                 const size_t shm_sep = ((size_t)2 * DT * 64 + (size_t)a.tch * Dz + a.tch * 4 + 2 * 128 * PST) * sizeof(double) + (size_t)Dw * 4 * sizeof(int) +
-                                       (getenv("DGPAMD_JSEP_LOG") ? 16 + JSEP_LOG_STEPS * 8 * sizeof(long long) : 0);
-                a.no_order_classes = (getenv("DGPAMD_JSEP_NOCLASS") ? 1 : 0) | (getenv("DGPAMD_JSEP_SAMEBLK") ? 2 : 0) | (getenv("DGPAMD_JSEP_DIAG") ? atoi(getenv("DGPAMD_JSEP_DIAG")) : 0);
-                const bool plog = ctx->tlog != nullptr && getenv("DGPAMD_JSEP_LOG") != nullptr;
+                                       (tn.jsep_log ? 16 + JSEP_LOG_STEPS * 8 * sizeof(long long) : 0);
+                a.no_order_classes = (tn.jsep_noclass ? 1 : 0) | (int)tn.jsep_diag;
+                const bool plog = ctx->tlog != nullptr && tn.jsep_log;
                 auto jsep = plog ? linkgp_Jsep_kernel<2, true> : (pipe == 0 ? linkgp_Jsep_kernel<0, false> : linkgp_Jsep_kernel<2, false>);
                 a.dbg = (plog && ctx->tlog_words >= 64 + (long long)ntiles * ((mc + a.tch - 1) / a.tch) * JSEP_LOG_WORDS) ? ctx->tlog : nullptr;
                 int rc = set_lds(ctx, (const void *)jsep, shm_sep);

@@ -1,6 +1,7 @@
 // Training-path pipelines (SURVEY 8 a4,a5,a8): ESS proposals, the batched ESS
 // target log-likelihood, and the in-flight derivative reductions of the M-step.
 #include "common.hpp"
+#include "wave.hpp"
 
 #include <math.h>
 
@@ -108,12 +109,6 @@ struct GradArgs {
     double *partial;
     const double *alpha_col;   // null: -alpha is row n of Ainv; else -alpha_i = alpha_col[i * ld] (column n of L^-T, dgpamd_potrf_inv)
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
 
 template <int KIND>
 __device__ __forceinline__ double dcoef(double df) {
@@ -541,8 +536,7 @@ extern "C" int dgpamd_llik_batch_launch(dgpamd_ctx *ctx, int64_t n, int batch, c
     if (cleared)   // (its -alpha is read where it is, column n of L^-T: no copy into the inverse's row n)
         for (int b = 0; b < batch; ++b) ga[b].a.alpha_col = T + (int64_t)b * stride_a + n;
     // one to three nodes (most rounds of an M-step): the arguments ride in the launches themselves, no copy into device memory (DGPAMD_LLIK_ARGS_COPY=1: always copy)
-    static const bool always_copy = getenv("DGPAMD_LLIK_ARGS_COPY") != nullptr && atoi(getenv("DGPAMD_LLIK_ARGS_COPY")) != 0;
-    const bool by_value = batch <= 3 && !always_copy;
+    const bool by_value = batch <= 3 && !ctx->tune.llik_args_copy;
     const KmatArgs *kd = nullptr;
     const GradMulti *gd = nullptr;
     if (!by_value) {

@@ -8,18 +8,11 @@
 #include "common.hpp"
 #include "linkfun.hpp"
 #include "vecchia_pred.hpp"
+#include "wave.hpp"
 
 #include <math.h>
-#include <utility>
 
 #define VW 64   // threads per item (one wave)
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return __shfl(v, 0, 64);
-}
-
 
 static int fill_vparams(dgpamd_ctx *ctx, VParams &p, int kind, int D, const double *length_h, int nlen, double nugget) {
     if (kind != DGPAMD_SEXP && kind != DGPAMD_MATERN25) BAD_ARG(ctx, "kind must be 0 or 1");
@@ -98,11 +91,7 @@ __device__ void lds_backsolve_T(const double *L, int lda, int b, double *X, int 
 // ---------------------------------------------------------------------------
 // a17  neighbour search
 // ---------------------------------------------------------------------------
-// One 256-thread workgroup per query.  Pass p selects the p-th smallest (dist, index) pair.
-__device__ __forceinline__ bool pair_less(double d1, int64_t i1, double d2, int64_t i2) {
-    return d1 < d2 || (d1 == d2 && i1 < i2);
-}
-
+// One 256-thread workgroup per query.  Pass p selects the p-th smallest (dist, index) pair (pair_less).
 __global__ __launch_bounds__(256) void nn_select_kernel(int64_t nq, int64_t nx, int D, const double *q, const double *x,
                                                         int m_out, int ordered, int64_t *out) {
     extern __shared__ double lds[];
@@ -527,7 +516,6 @@ static int launch_nn_stream(dgpamd_ctx *ctx, int64_t nq, int64_t nx, int D, cons
         chunk = nq < 15000 ? 8192 : (nq < 40000 ? 16384 : 25024);
     else if (nx >= 45000)
         chunk = 16384;
-    if (const char *ce = getenv("DGPAMD_NN_CHUNK")) chunk = atoll(ce) > 0 ? (atoll(ce) + 63) / 64 * 64 : chunk;   // (tuning aid)
     const int nchunk = (int)((nx + chunk - 1) / chunk);
     const size_t items = (size_t)nblk * nchunk;
     void *both = nullptr;
@@ -788,7 +776,7 @@ template <int DMAX>
 static int launch_nn_stream_k(dgpamd_ctx *ctx, int64_t nq, int64_t nx, int D, const double *q, const double *x, int m_out,
                               int ordered, int64_t *out) {
     // the query form at prediction sizes: filter, then select (DGPAMD_NN_FILTER=0: the streaming kernel, for comparisons)
-    const bool filter_on = !(getenv("DGPAMD_NN_FILTER") && getenv("DGPAMD_NN_FILTER")[0] == '0');   // (read per call: the tests flip it)
+    const bool filter_on = ctx->tune.nn_filter != 0;
     NnfPlan plan;
     if (!ordered && filter_on && m_out > 26 && nnf_plan(nq, nx, m_out, plan)) {
         if (m_out <= 32) return launch_nn_filter<DMAX, 32>(ctx, nq, nx, D, q, x, m_out, out, plan);
@@ -814,8 +802,7 @@ static int launch_nn(dgpamd_ctx *ctx, int64_t nq, int64_t nx, int D, const doubl
     // n = 50 000) and the query form from ~6000 queries on (1.9x at 10 000, 2.6x at 20 000 queries against 50 000 points; their
     // floor is one cold-started chunk scan, ~4 ms).
     // DGPAMD_NN_STORE_ONCE = 1 / 2 forces the store-once / the streaming kernels (the tests compare the two).
-    const char *env = getenv("DGPAMD_NN_STORE_ONCE");
-    const int force = env ? atoi(env) : 0;
+    const int force = (int)ctx->tune.nn_store_once;
     const bool pays = ordered ? nx >= 12000 : (nq >= 6000 && nx >= 20000);
     if (D <= 16 && m_out <= 64 && nx < INT_MAX && force != 1 && (pays || force == 2))
         return D <= 8 ? launch_nn_stream_k<8>(ctx, nq, nx, D, q, x, m_out, ordered, out)
@@ -968,8 +955,8 @@ __global__ __launch_bounds__(VW) void vecchia_row_kernel(VRowArgs a) {
             tl = fma(2.0 * dk, u[r] * u[c], tl);
             s = fma(dk, al[r] * u[c] + al[c] * u[r], s);
         }
-        tl = wsum(tl);
-        s = wsum(s);
+        tl = wave_sum_all(tl);
+        s = wave_sum_all(s);
         if (lane == 0) {
             out[2 + k] = 2.0 * s * wl - tl * wl * wl;
             out[2 + P + k] = tl;
@@ -982,8 +969,8 @@ __global__ __launch_bounds__(VW) void vecchia_row_kernel(VRowArgs a) {
             tl = fma(dk, u[r] * u[r], tl);
             s = fma(dk, al[r] * u[r], s);
         }
-        tl = wsum(tl);
-        s = wsum(s);
+        tl = wave_sum_all(tl);
+        s = wave_sum_all(s);
         if (lane == 0) {
             out[2 + npl] = 2.0 * s * wl - tl * wl * wl;
             out[2 + P + npl] = tl;
@@ -1044,15 +1031,6 @@ __device__ __forceinline__ void rsqrt_sqrt(double d, double &inv, double &sd) {
     r = fma(0.5 * y, fma(-r, r, d), r);
     inv = y;
     sd = r;
-}
-
-template <int... Is, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, Is...>, F &&f) {
-    (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-    static_for_impl(std::make_integer_sequence<int, N>{}, f);
 }
 
 // value of lane C of the caller's 16-lane group.  s_nop 4: a DPP source written by the previous VALU needs two wait states
@@ -1235,7 +1213,7 @@ __device__ __forceinline__ void vrow4_body(const VRowArgs &a, double *lds, const
 
     double sd_last = 1.0, w_last = 0.0;
     VR4_STAMP(5);
-    static_for<BS>([&](auto J) {
+    static_for<0, BS>([&](auto J) {
         constexpr int j = J;
         double d = j < 16 ? group_bcast<(j & 15)>(ra[j & 15]) : group_bcast<(j & 15)>(rb[j < NBB ? j : 0]);
         if (!(d > 0.0)) d = 1.0;
@@ -1251,7 +1229,7 @@ __device__ __forceinline__ void vrow4_body(const VRowArgs &a, double *lds, const
         rb[j] = lb;
         nlb = -lb;
         asm volatile("s_nop 4" : "+v"(nla), "+v"(nlb));   // (DPP sources just written; see group_bcast)
-        static_for<BS>([&](auto Cc) {
+        static_for<0, BS>([&](auto Cc) {
             constexpr int c = Cc;
             if constexpr (c > j) {
                 if constexpr (c < 16) {
@@ -1292,7 +1270,7 @@ __device__ __forceinline__ void vrow4_body(const VRowArgs &a, double *lds, const
 #pragma unroll
         for (int c = 0; c < (MODE == V_NLLIK ? BS : 1); ++c) acca[c] = 0.0;
         double u0 = 0.0, u1 = 0.0, a0 = 0.0, a1 = 0.0;   // x of rows t and 16 + t
-        static_for<BS>([&](auto RR) {
+        static_for<0, BS>([&](auto RR) {
             constexpr int r = BS - 1 - RR, owner = r & 15;
             constexpr bool sb = r >= 16;
             double diag;
@@ -1311,7 +1289,7 @@ __device__ __forceinline__ void vrow4_body(const VRowArgs &a, double *lds, const
                 am = (t == owner) ? ar : 0.0;
                 if constexpr (sb) a1 += am; else a0 += am;
             }
-            static_for<r>([&](auto Cc) {
+            static_for<0, r>([&](auto Cc) {
                 constexpr int c = Cc;
                 double lrc;
                 if constexpr (sb) lrc = rb[c]; else lrc = ra[c & 15];
@@ -1413,19 +1391,16 @@ __global__ __launch_bounds__(64) void vecchia_row4_kernel(VRowArgs a) {
     }
 }
 
-#ifndef VR4_GRID
 #define VR4_GRID 2048   // row-block workgroups per input set (each walks n / 4 / 2048 row blocks)
-#endif
 template <int KIND, int MODE, int BS>
 static int launch_vrow4_nb(dgpamd_ctx *ctx, VRowArgs &a, int batch) {
     const size_t shm = vrow4_lds(BS, a.vp.D, MODE == V_NLLIK, MODE != V_LLIK);
     int rc = set_lds(ctx, (const void *)vecchia_row4_kernel<KIND, MODE, BS>, shm);
     if (rc) return rc;
     const int64_t nrb = (a.n + 3) / 4;
-    static const int64_t cap_env = getenv("DGPAMD_VR4_GRID") ? atoll(getenv("DGPAMD_VR4_GRID")) : -1;
     // the cap applies to the launches a device-side queue may predicate away (ctx->pred set); the others keep one
     // workgroup per row block, which the hardware balances better (llik x6 688 vs 721 us, nllik 333 vs 380 us at n = 50 000)
-    const int64_t cap = cap_env >= 0 ? (cap_env == 0 ? nrb : cap_env) : (a.pred ? VR4_GRID : nrb);
+    const int64_t cap = a.pred ? VR4_GRID : nrb;
     a.trace = ctx->trace;
     hipLaunchKernelGGL((vecchia_row4_kernel<KIND, MODE, BS>), dim3((unsigned)(nrb < cap ? nrb : cap), (unsigned)batch), dim3(64), shm,
                        ctx->stream, a);
@@ -1488,8 +1463,7 @@ __global__ __launch_bounds__(256) void lds_poison_kernel(double *sink) {
 }
 
 static int maybe_poison_lds(dgpamd_ctx *ctx, const double *any_device_ptr) {
-    const char *poison = getenv("DGPAMD_POISON_LDS");
-    if (poison && atoi(poison)) {
+    if (ctx->tune.poison_lds) {
         HIP_TRY(ctx, hipFuncSetAttribute((const void *)lds_poison_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
         hipLaunchKernelGGL(lds_poison_kernel, dim3(8 * ctx->num_cu), dim3(256), 65536, ctx->stream, (double *)any_device_ptr);
     }
@@ -1515,8 +1489,7 @@ static int launch_vrow(dgpamd_ctx *ctx, VRowArgs &a, int batch = 1) {
         int prc = maybe_poison_lds(ctx, a.X);
         if (prc) return prc;
     }
-    const char *env = getenv("DGPAMD_VECCHIA_LDS");   // (1: the LDS version for every size -- the tests compare the two)
-    if (a.m + 1 <= VR_MAXB && !(env && atoi(env)))   // register-resident factorisation, two rows per wave
+    if (a.m + 1 <= VR_MAXB && !ctx->tune.vecchia_lds)   // (DGPAMD_VECCHIA_LDS=1: the LDS version for every size -- the tests compare the two)   // register-resident factorisation, two rows per wave
         return a.vp.kind == DGPAMD_SEXP ? launch_vrow4<DGPAMD_SEXP, MODE>(ctx, a, batch) : launch_vrow4<DGPAMD_MATERN25, MODE>(ctx, a, batch);
     const size_t shm = vrow_lds(a.m, a.vp.D);
     const void *fn = a.vp.kind == DGPAMD_SEXP ? (const void *)vecchia_row_kernel<DGPAMD_SEXP, MODE>
@@ -2134,8 +2107,7 @@ extern "C" int dgpamd_vecchia_gp(dgpamd_ctx *ctx, int kind, int64_t M, int64_t n
     a.M = M; a.n = n; a.pm = pm; a.x = x; a.w = w; a.y = y; a.nugget_diag = nugget_diag; a.NN = NN; a.scale = scale;
     a.mean = mean; a.var = var;
     {
-        const char *env = getenv("DGPAMD_VECCHIA_LDS");   // (1: the LDS version for every size -- the tests compare the two)
-        if (pm <= VG_BC && D <= 16 && !(env && atoi(env))) {
+        if (pm <= VG_BC && D <= 16 && !ctx->tune.vecchia_lds) {   // (DGPAMD_VECCHIA_LDS=1: the LDS version for every size -- the tests compare the two)
             launch_vecchia_gp_reg(ctx, a);
             LAUNCH_CHECK(ctx);
             return DGPAMD_OK;
@@ -2313,8 +2285,8 @@ __global__ __launch_bounds__(VW) void vecchia_linkgp_kernel(VLinkArgs a) {
         for (int c = 0; c < b; ++c) s = fma(J[r * lda + c], Ry[c], s);
         qd = fma(Ry[r], s, qd);
     }
-    mu = wsum(mu);
-    qd = wsum(qd);
+    mu = wave_sum_all(mu);
+    qd = wave_sum_all(qd);
     __syncthreads();
     // tr(K^-1 J) = tr(L^-1 (L^-1 J)^T): two rounds of column-parallel forward substitutions
     for (int c = lane; c < b; c += VW)
@@ -2337,7 +2309,7 @@ __global__ __launch_bounds__(VW) void vecchia_linkgp_kernel(VLinkArgs a) {
         }
         tr += hc;
     }
-    tr = wsum(tr);
+    tr = wave_sum_all(tr);
     if (lane == 0) {
         a.mean[t] = mu;
         a.var[t] = fabs(qd - mu * mu + a.scale * (1.0 + a.nugget - tr));
@@ -2360,8 +2332,7 @@ extern "C" int dgpamd_vecchia_linkgp(dgpamd_ctx *ctx, int kind, int64_t M, int64
     a.y = y; a.nugget_diag = nugget_diag; a.NN = NN; a.scale = scale; a.nugget = nugget; a.mean = mean; a.var = var;
     for (int d = 0; d < Dw + Dz; ++d) a.len[d] = length_h[nlen == 1 ? 0 : d];
     {
-        const char *env = getenv("DGPAMD_VECCHIA_LDS");   // (1: the LDS version for every size -- the tests compare the two)
-        if (pm <= VL_BC && Dw <= 8 && Dz <= 8 && !(env && atoi(env))) {
+        if (pm <= VL_BC && Dw <= 8 && Dz <= 8 && !ctx->tune.vecchia_lds) {   // (DGPAMD_VECCHIA_LDS=1: the LDS version for every size -- the tests compare the two)
             if (kind == DGPAMD_SEXP)
                 launch_vecchia_linkgp_sexp_reg(ctx, a);
             else

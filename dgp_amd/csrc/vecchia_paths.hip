@@ -8,30 +8,14 @@
 // substitution is dgpamd_vecchia_levels + dgpamd_vecchia_spsolve_levels.
 #include "common.hpp"
 #include "vecchia_pred.hpp"
+#include "wave.hpp"
 
 #include <climits>
 #include <math.h>
-#include <utility>
 
 namespace {
 
-template <int I, int N, class F>
-__device__ __forceinline__ void vp_for(F &&f) {   // (every register index a compile-time constant: see vecchia_pred.hip)
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        vp_for<I + 1, N>(f);
-    }
-}
-__device__ __forceinline__ double vp_readlane(double v, int l) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-__device__ __forceinline__ double vp_wsum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return __shfl(v, 0, 64);
-}
-__device__ __forceinline__ bool vp_less(double d1, int i1, double d2, int i2) { return d1 < d2 || (d1 == d2 && i1 < i2); }
-
+// (the LDS kernels' corr_pts of vecchia.hip with exp_negated in place of the library's exp: other bits, not to be merged)
 template <int KIND>
 __device__ __forceinline__ double vp_corr(const double *xa, const double *xb, int D) {
     double s = 0.0, pr = 1.0;
@@ -92,22 +76,22 @@ __global__ __launch_bounds__(256) void vpaths_nn_kernel(VPNnArgs a) {
                 s = fma(df, df, s);
             }
         }
-        uint64_t mask = __ballot(j < nc && vp_less(s, (int)j, worst_d, worst_i));
+        uint64_t mask = __ballot(j < nc && pair_less(s, (int)j, worst_d, worst_i));
         while (mask) {
             const int l = __ffsll((unsigned long long)mask) - 1;
             mask &= mask - 1;
-            const double cd = vp_readlane(s, l);
+            const double cd = readlane_f64(s, l);
             const int ci = (int)(j0 + l);
-            if (!vp_less(cd, ci, worst_d, worst_i)) continue;   // (uniform: the list moved on since the ballot)
+            if (!pair_less(cd, ci, worst_d, worst_i)) continue;   // (uniform: the list moved on since the ballot)
             int pos = 0;
 #pragma unroll
-            for (int r = 0; r < R; ++r) pos += __popcll(__ballot(vp_less(bd[r], bi[r], cd, ci)));
+            for (int r = 0; r < R; ++r) pos += __popcll(__ballot(pair_less(bd[r], bi[r], cd, ci)));
 #pragma unroll
             for (int r = R - 1; r >= 0; --r) {
                 double ud = __shfl_up(bd[r], 1, 64);
                 int ui = __shfl_up(bi[r], 1, 64);
                 if (r > 0) {
-                    const double pd = vp_readlane(bd[r - 1], 63);
+                    const double pd = readlane_f64(bd[r - 1], 63);
                     const int pi = __builtin_amdgcn_readlane(bi[r - 1], 63);
                     if (lane == 0) {
                         ud = pd;
@@ -126,7 +110,7 @@ __global__ __launch_bounds__(256) void vpaths_nn_kernel(VPNnArgs a) {
 #pragma unroll
             for (int r = 0; r < R; ++r)
                 if (r == ws) {
-                    worst_d = vp_readlane(bd[r], wl);
+                    worst_d = readlane_f64(bd[r], wl);
                     worst_i = __builtin_amdgcn_readlane(bi[r], wl);
                 }
         }
@@ -185,7 +169,7 @@ __global__ __launch_bounds__(256) void vpaths_rows_reg_kernel(VPRowArgs a) {
         double s = 0.0, pr = 1.0;
 #pragma unroll
         for (int d = 0; d < DM; ++d) {
-            const double df = xr[d] - vp_readlane(xr[d], c);
+            const double df = xr[d] - readlane_f64(xr[d], c);
             if (KIND == DGPAMD_SEXP)
                 corr_accum_sexp(df, s);
             else
@@ -195,47 +179,47 @@ __global__ __launch_bounds__(256) void vpaths_rows_reg_kernel(VPRowArgs a) {
         return lane == c ? dg : v;
     };
     double reg[VG_BC];
-    vp_for<0, VG_BC>([&](auto ic) {
+    static_for<0, VG_BC>([&](auto ic) {
         constexpr int c = decltype(ic)::value;
         reg[c] = 0.0;
         if (c < b) reg[c] = column(c);
     });
     double last = column(b);
     bool bad = false;
-    vp_for<0, VG_BC>([&](auto ij) {
+    static_for<0, VG_BC>([&](auto ij) {
         constexpr int j = decltype(ij)::value;
         if (j < b) {
-            const double dj = vp_readlane(reg[j], j);
+            const double dj = readlane_f64(reg[j], j);
             bad = bad || !(dj > 0.0);
             const double rd = 1.0 / dj;
             const double mi = lane > j ? reg[j] * rd : 0.0;
-            vp_for<(j + 1) / 8, (VG_BC + 7) / 8>([&](auto ig) {
+            static_for<(j + 1) / 8, (VG_BC + 7) / 8>([&](auto ig) {
                 constexpr int c0 = 8 * decltype(ig)::value;
                 if (c0 < b) {
-                    vp_for<0, 8>([&](auto iq) {
+                    static_for<0, 8>([&](auto iq) {
                         constexpr int c = c0 + decltype(iq)::value;
-                        if constexpr (c > j && c < VG_BC) reg[c] = fma(-mi, vp_readlane(reg[c], j), reg[c]);
+                        if constexpr (c > j && c < VG_BC) reg[c] = fma(-mi, readlane_f64(reg[c], j), reg[c]);
                     });
                 }
             });
-            last = fma(-mi, vp_readlane(last, j), last);
+            last = fma(-mi, readlane_f64(last, j), last);
         }
     });
-    const double schur = vp_readlane(last, b);
+    const double schur = readlane_f64(last, b);
     bad = bad || !(schur > 0.0);
     // b_i = U^-1 (L^-1 a): back substitution, pivot j broadcast from lane j
     double coef = 0.0, res = lane < b ? last : 0.0;
-    vp_for<0, VG_BC>([&](auto ik) {
+    static_for<0, VG_BC>([&](auto ik) {
         constexpr int j = VG_BC - 1 - decltype(ik)::value;
         if (j < b) {
-            const double xj = vp_readlane(res, j) / vp_readlane(reg[j], j);
+            const double xj = readlane_f64(res, j) / readlane_f64(reg[j], j);
             coef = lane == j ? xj : coef;
             res = lane < j ? fma(-reg[j], xj, res) : res;
         }
     });
     const double sdv = sqrt(a.scale * schur);
     for (int r = 0; r < a.nrhs; ++r) {
-        const double tv = vp_wsum(tr ? coef * a.y[(g * a.nrhs + r) * n + nnv] : 0.0);
+        const double tv = wave_sum_all(tr ? coef * a.y[(g * a.nrhs + r) * n + nnv] : 0.0);
         if (lane == 0) a.t[(p * a.nrhs + r) * a.M + i] = tv;
     }
     const uint64_t tmask = __ballot(te);
@@ -338,7 +322,7 @@ __global__ __launch_bounds__(64) void vpaths_rows_lds_kernel(VPRowArgs a) {
         double s = 0.0;
         for (int c = lane; c < b; c += 64)
             if (idx[c] < n) s = fma(V[c], a.y[(g * a.nrhs + r) * n + idx[c]], s);
-        s = vp_wsum(s);
+        s = wave_sum_all(s);
         if (lane == 0) a.t[(p * a.nrhs + r) * a.M + i] = s;
     }
     if (lane == 0) {
@@ -393,7 +377,7 @@ extern "C" int dgpamd_vpaths_rows(dgpamd_ctx *ctx, int kind, int64_t P, int64_t 
     a.D = D; a.m = m; a.nrhs = nrhs; a.P = P; a.M = M; a.n = n; a.q = q; a.x = x; a.omega = omega; a.y = y; a.group = group;
     a.NN = NN; a.nugget = nugget; a.jitter = jitter; a.scale = scale; a.Lrows = Lrows; a.t = t; a.sd = sd; a.NNl = NNl;
     a.info = info;
-    const bool reg = m <= VG_BC && D <= 16 && !(getenv("DGPAMD_VECCHIA_LDS") && getenv("DGPAMD_VECCHIA_LDS")[0] == '1');
+    const bool reg = m <= VG_BC && D <= 16 && !ctx->tune.vecchia_lds;
     const size_t shm = vpaths_rows_lds_bytes(m, D);
     const void *fn = kind == DGPAMD_SEXP ? (const void *)vpaths_rows_lds_kernel<DGPAMD_SEXP>
                                          : (const void *)vpaths_rows_lds_kernel<DGPAMD_MATERN25>;

@@ -3,13 +3,7 @@
 // v_readlane; every register index is a compile-time constant (static_for), which is why this file takes minutes to compile.
 #include "vecchia_pred.hpp"
 #include "linkfun.hpp"
-#include <utility>
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return __shfl(v, 0, 64);
-}
+#include "wave.hpp"
 
 // The same prediction with the block in REGISTERS (pm <= VG_BC, D <= 16): one wave per test point, one ROW of the
 // (b + 2) x (b + 1) block [neighbours ; test point ; y] per lane -- lane r holds row r's b neighbour columns in reg[] and the
@@ -19,23 +13,6 @@ __device__ __forceinline__ double wsum(double v) {
 // no dependent LDS round trips; four test points per workgroup.  (LDL^T without square roots: the Schur complement of the test
 // point and the eliminated y row are the same numbers as with gp_vecch's Cholesky, vecchia.py:635-654.)  The LDS kernel above
 // ran one wave per point at 3-6 workgroups per CU on chains of dependent LDS reads: 8.3 ms per 100 000 points at pm = 50, D = 8.
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F &&f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-__device__ __forceinline__ double rcp_newton(double d) {
-    double x = __builtin_amdgcn_rcp(d);
-    double e = fma(-d, x, 1.0);
-    x = fma(x, e, x);
-    e = fma(-d, x, 1.0);
-    return fma(x, e, x);
-}
 template <int KIND, int DM>
 __global__ __launch_bounds__(256) void vecchia_gp_reg_kernel(VGpArgs a) {
     const int lane = threadIdx.x & 63;
@@ -155,12 +132,12 @@ __device__ __forceinline__ void linkgp_reg_finish(double (&reg)[VL_BC], double (
         constexpr int c = decltype(ic)::value;
         if (c < b) {
             const double nic = lane > c ? reg[c] : (lane == c ? 1.0 : 0.0);
-            const double tc = wsum(act ? nic * v : 0.0);
+            const double tc = wave_sum_all(act ? nic * v : 0.0);
             mt = fma(jm[c], tc, mt);
             trp = fma(jm[c], nic, trp);
         }
     });
-    const double mu = wsum(Iv * v), qd = wsum(v * mt), tr = wsum(trp * rdi);
+    const double mu = wave_sum_all(Iv * v), qd = wave_sum_all(v * mt), tr = wave_sum_all(trp * rdi);
     if (lane == 0) {
         a.mean[t] = mu;
         a.var[t] = fabs(qd - mu * mu + a.scale * (1.0 + a.nugget - tr));

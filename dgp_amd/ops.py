@@ -115,6 +115,13 @@ class Engine:
     def sync(self):
         self._chk(lib.dgpamd_sync(self.h))
 
+    def tuning(self, name):
+        """The value of one DGPAMD_* switch of the C library as this engine's context found it when it was created (a context keeps the
+        switches it was created under).  0 for an unset switch whose default depends on the call; an unknown name raises."""
+        v = C.c_int64()
+        self._chk(lib.dgpamd_tuning_get(self.h, name.encode(), C.byref(v)))
+        return v.value
+
     def set_linkgp_direct(self, enable):
         """Matern linked-GP J factor: reference's direct expression (True) or its separable form (default)."""
         self._chk(self._enter() or lib.dgpamd_set_linkgp_direct(self.h, 1 if enable else 0))

@@ -57,6 +57,11 @@ typedef struct dgpamd_ctx dgpamd_ctx;
  * NULL for the device's default (null) stream -- torch's default current stream. */
 int dgpamd_create(int device, void *stream, dgpamd_ctx **out);
 int dgpamd_destroy(dgpamd_ctx *ctx);
+/* The DGPAMD_* environment switches of the library (INTEGRATION.md lists them) are read once, by dgpamd_create: a context
+ * keeps the switches it was created under.  *value = what this context runs under for `name` (with or without the
+ * "DGPAMD_" prefix), as parsed and clamped; 0 where the switch was unset (or its value not accepted) and the default depends on the call.
+ * An unknown name: DGPAMD_BAD_ARG. */
+int dgpamd_tuning_get(dgpamd_ctx *ctx, const char *name, int64_t *value);
 const char *dgpamd_last_error(const dgpamd_ctx *ctx);
 int dgpamd_sync(dgpamd_ctx *ctx);
 /* Results to the host: copy `bytes` from device memory through the context's pinned staging buffer, ordered after

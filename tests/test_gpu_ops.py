@@ -5,6 +5,9 @@ Tolerances (f64): 1e-10 relative on kernel matrices and likelihood scalars;
 1e-8 where a Cholesky at n >= 1000 or the Jd-based Matern J is involved;
 variances that are differences of O(scale) terms carry an absolute tolerance
 of 1e-7*scale (cond(R) ~ 1e6 at nugget 1e-6); index arrays are bit-exact."""
+import contextlib
+import os
+
 import numpy as np
 import pytest
 
@@ -20,6 +23,64 @@ def eng():
         pytest.skip('no HIP device')
     from dgp_amd.ops import Engine
     return Engine(0)
+
+
+@contextlib.contextmanager
+def engine_under(**switches):
+    """A fresh Engine created with DGPAMD_<name> = value in the environment for every keyword (None: unset), closed afterwards.  A context keeps the
+    switches it was created under, so the environment is put back as soon as the engine exists; the engine must report every value it was given
+    (a misspelt name raises here instead of comparing a kernel with itself).  It shares the thread's stream with the module's `eng`: tensors of either
+    serve both."""
+    from dgp_amd.ops import Engine
+    names = {k: 'DGPAMD_' + k for k in switches}
+    before = {k: os.environ.get(names[k]) for k in switches}
+    try:
+        for k, v in switches.items():
+            os.environ.pop(names[k], None)
+            if v is not None:
+                os.environ[names[k]] = str(v)
+        e = Engine(0)
+    finally:
+        for k, v in before.items():
+            os.environ.pop(names[k], None)
+            if v is not None:
+                os.environ[names[k]] = v
+    try:
+        for k, v in switches.items():
+            assert v is None or e.tuning(k) == int(v), (k, v, e.tuning(k))
+        yield e
+        e.sync()
+    finally:
+        e.close()
+
+
+def test_a_context_keeps_the_switches_it_was_created_under(eng, monkeypatch):
+    """The C library reads its DGPAMD_* switches once, in dgpamd_create (csrc/context.hip: one table): an engine made before the environment
+    changes does not see the change, one made after it does and goes on doing so when the variables are gone again.  Values are reported as
+    parsed -- clamped (MEGA_NEAR 0..6), the default where a value is not accepted (JSEP_TCH: 8..256 in steps of 8) -- and an unknown name raises.
+    Nothing is launched."""
+    from dgp_amd.ops import Engine, DgpAmdError
+    names = ('VECCHIA_LDS', 'JSEP_TCH', 'MEGA_NEAR')
+    for k in names:
+        monkeypatch.delenv('DGPAMD_' + k, raising=False)
+    first = Engine(0)
+    for k, v in zip(names, ('1', '64', '9')):
+        monkeypatch.setenv('DGPAMD_' + k, v)
+    second = Engine(0)
+    monkeypatch.setenv('DGPAMD_JSEP_TCH', '7')
+    third = Engine(0)
+    for k in names:
+        monkeypatch.delenv('DGPAMD_' + k)
+    try:
+        assert [first.tuning(k) for k in names] == [0, 0, 3]
+        assert [second.tuning(k) for k in names] == [1, 64, 6]
+        assert third.tuning('JSEP_TCH') == 0 and third.tuning('DGPAMD_JSEP_TCH') == 0
+        assert second.tuning('DGPAMD_MEGA_NEAR') == 6   # (with or without the prefix)
+        with pytest.raises(DgpAmdError):
+            second.tuning('VECCHIA_LSD')
+    finally:
+        for e in (first, second, third):
+            e.close()
 
 
 def close(a, b, rtol=1e-10, atol=1e-13):
@@ -533,57 +594,57 @@ def test_vecchia_kernels_golden(eng, golden):
 
 
 @pytest.mark.parametrize('name', ['sexp', 'matern2.5'])
-def test_vecchia_row_kernels_register_and_lds_versions_agree(eng, name, monkeypatch):
+def test_vecchia_row_kernels_register_and_lds_versions_agree(eng, name):
     """Conditioning sets of up to 31 points take the register-resident two-rows-per-wave kernel, larger ones (and
     DGPAMD_VECCHIA_LDS=1) the LDS kernel the golden vectors were first pinned on: same sums, gradients and sparse-factor
     rows to rounding over ragged first rows, odd n, isotropic / ARD lengthscales, nugget weights, and a batch of inputs."""
     import torch
     rng = np.random.default_rng(31)
-    monkeypatch.setenv('DGPAMD_POISON_LDS', '1')   # NaNs in every CU's LDS before each row launch: nothing unwritten may be read
-    for n, D, m, ard, nugget_est in [(301, 3, 6, False, True), (777, 8, 25, False, False), (500, 5, 30, True, True), (64, 1, 12, False, True),
-                                     (40, 2, 30, True, False), (260, 2, 8, False, False), (130, 2, 3, False, True), (200, 12, 17, True, True),
-                                     (333, 4, 21, False, True), (150, 3, 27, False, False)]:
-        X = rng.uniform(size=(n, D))
-        y = np.sin(3 * X[:, 0]) + 0.1 * rng.normal(size=n)
-        ln = rng.uniform(0.4, 1.2, size=D) if ard else np.array([0.7])
-        w = rng.uniform(0.5, 2.0, size=n)
-        dX, dy, dw = eng.tensor(X), eng.tensor(y), eng.tensor(w)
-        NN = eng.nn_ordered(eng.tensor(X / ln), m)
-        XB = eng.tensor(np.stack([X, X + 0.01 * rng.normal(size=X.shape), rng.uniform(size=X.shape)]))
-        got = {}
-        for lds in ('0', '1'):
-            monkeypatch.setenv('DGPAMD_VECCHIA_LDS', lds)
-            o, P = eng.vecchia_nllik(name, dX, dy, NN, ln, 1e-3, dw, nugget_est)
-            got[lds] = (npy(eng.vecchia_llik(name, dX, dy, NN, ln, 1e-3, dw)), npy(o), npy(eng.vecchia_lmatrix(name, dX, NN, ln, 1e-3)),
-                        npy(eng.vecchia_llik_batch(name, XB, dy, NN, ln, 1e-3, dw)))
-        for a, b in zip(got['0'], got['1']):
-            close(a, b, rtol=1e-9, atol=1e-9 * np.abs(b).max())
-        monkeypatch.setenv('DGPAMD_VECCHIA_LDS', '0')
-        close(got['0'][3][0], got['0'][0], rtol=1e-14)       # batch member 0 is the single evaluation
-        for j in range(3):                                   # and every member equals its own single evaluation
-            close(got['0'][3][j], npy(eng.vecchia_llik(name, XB[j], dy, NN, ln, 1e-3, dw)), rtol=1e-14)
+    with contextlib.ExitStack() as stack:   # (POISON_LDS: NaNs in every CU's LDS before each row launch: nothing unwritten may be read)
+        engines = {lds: stack.enter_context(engine_under(POISON_LDS=1, VECCHIA_LDS=lds)) for lds in ('0', '1')}
+        for n, D, m, ard, nugget_est in [(301, 3, 6, False, True), (777, 8, 25, False, False), (500, 5, 30, True, True), (64, 1, 12, False, True),
+                                         (40, 2, 30, True, False), (260, 2, 8, False, False), (130, 2, 3, False, True), (200, 12, 17, True, True),
+                                         (333, 4, 21, False, True), (150, 3, 27, False, False)]:
+            X = rng.uniform(size=(n, D))
+            y = np.sin(3 * X[:, 0]) + 0.1 * rng.normal(size=n)
+            ln = rng.uniform(0.4, 1.2, size=D) if ard else np.array([0.7])
+            w = rng.uniform(0.5, 2.0, size=n)
+            dX, dy, dw = eng.tensor(X), eng.tensor(y), eng.tensor(w)
+            NN = eng.nn_ordered(eng.tensor(X / ln), m)
+            XB = eng.tensor(np.stack([X, X + 0.01 * rng.normal(size=X.shape), rng.uniform(size=X.shape)]))
+            got = {}
+            for lds, e in engines.items():
+                o, P = e.vecchia_nllik(name, dX, dy, NN, ln, 1e-3, dw, nugget_est)
+                got[lds] = (npy(e.vecchia_llik(name, dX, dy, NN, ln, 1e-3, dw)), npy(o), npy(e.vecchia_lmatrix(name, dX, NN, ln, 1e-3)),
+                            npy(e.vecchia_llik_batch(name, XB, dy, NN, ln, 1e-3, dw)))
+            for a, b in zip(got['0'], got['1']):
+                close(a, b, rtol=1e-9, atol=1e-9 * np.abs(b).max())
+            close(got['0'][3][0], got['0'][0], rtol=1e-14)       # batch member 0 is the single evaluation
+            for j in range(3):                                   # and every member equals its own single evaluation
+                close(got['0'][3][j], npy(engines['0'].vecchia_llik(name, XB[j], dy, NN, ln, 1e-3, dw)), rtol=1e-14)
 
 
-def test_nn_streaming_topk_equals_store_once_kernel(eng, monkeypatch):
+def test_nn_streaming_topk_equals_store_once_kernel(eng):
     """Candidate sets of 4096 points and more in up to 16 dimensions take the streaming top-k kernels (register-resident
     sorted lists, candidates staged once per 64 queries); DGPAMD_NN_STORE_ONCE=1 forces the store-once histogram kernel
     the bit-exact golden comparison was first made with (=2 the streaming ones).  Same neighbour arrays, element for element: ordered (vecchia.py:
     98-109) and query form (:20-37), ties between duplicated points broken by index, fewer candidates than neighbours in
     the first rows, query counts that do not fill the last block of 64."""
     rng = np.random.default_rng(17)
-    for n, D, m in [(4500, 3, 25), (6001, 8, 25), (5000, 1, 15), (4200, 12, 50), (9000, 2, 60), (4100, 5, 31)]:
-        x = rng.uniform(size=(n, D))
-        x[rng.integers(0, n, 300)] = x[rng.integers(0, n, 300)]       # duplicated points: equal distances
-        q = np.concatenate((rng.uniform(size=(333, D)), x[:40]))
-        dx, dq = eng.tensor(x), eng.tensor(q)
-        got = {}
-        for flag in ('2', '1'):   # (2: streaming at every size; by default it starts where it pays: n >= 12 000)
-            monkeypatch.setenv('DGPAMD_NN_STORE_ONCE', flag)
-            got[flag] = (npy(eng.nn_ordered(dx, m)), npy(eng.nn_query(dq, dx, m)))
-        np.testing.assert_array_equal(got['2'][0], got['1'][0])
-        np.testing.assert_array_equal(got['2'][1], got['1'][1])
-        a = got['2'][0]
-        assert a.shape == (n, m + 1) and np.array_equal(a[:, 0], np.arange(n)) and np.all(a[:5, 6:] == -1)
+    # (2: streaming at every size; by default it starts where it pays: n >= 12 000)
+    with engine_under(NN_STORE_ONCE=2) as e2, engine_under(NN_STORE_ONCE=1) as e1:
+        for n, D, m in [(4500, 3, 25), (6001, 8, 25), (5000, 1, 15), (4200, 12, 50), (9000, 2, 60), (4100, 5, 31)]:
+            x = rng.uniform(size=(n, D))
+            x[rng.integers(0, n, 300)] = x[rng.integers(0, n, 300)]       # duplicated points: equal distances
+            q = np.concatenate((rng.uniform(size=(333, D)), x[:40]))
+            dx, dq = eng.tensor(x), eng.tensor(q)
+            got = {}
+            for flag, e in (('2', e2), ('1', e1)):
+                got[flag] = (npy(e.nn_ordered(dx, m)), npy(e.nn_query(dq, dx, m)))
+            np.testing.assert_array_equal(got['2'][0], got['1'][0])
+            np.testing.assert_array_equal(got['2'][1], got['1'][1])
+            a = got['2'][0]
+            assert a.shape == (n, m + 1) and np.array_equal(a[:, 0], np.arange(n)) and np.all(a[:5, 6:] == -1)
 
 
 @pytest.mark.parametrize('B', [24, 32, 64])
@@ -615,7 +676,7 @@ def test_one_launch_factorisation_with_many_matrices(eng, B):
         assert torch.equal(a, b)
 
 
-def test_nn_query_filter_then_select_equals_streaming_topk(eng, monkeypatch):
+def test_nn_query_filter_then_select_equals_streaming_topk(eng):
     """From 30 000 queries against 20 000 points on the query search (vecchia.py:20-40) takes the filter-then-select kernels of round 5
     (a sampled upper bound of every query's K-th nearest distance, a register-light scan that notes the candidates at or below it, the
     K nearest of the notes; csrc/vecchia.hip nn_tau / nn_collect / nn_pick); DGPAMD_NN_FILTER=0 keeps the streaming top-k kernel.  Same
@@ -631,18 +692,16 @@ def test_nn_query_filter_then_select_equals_streaming_topk(eng, monkeypatch):
     g = np.stack(np.meshgrid(np.arange(150.), np.arange(140.)), -1).reshape(-1, 2)
     cases.append(('grid', g[rng.integers(0, len(g), 30100)], g, 31))
     cases.append(('equal', rng.uniform(size=(30000, 2)), np.ones((20000, 2)), 33))
-    for name, q, x, m in cases:
-        dq, dx = eng.tensor(q), eng.tensor(x)
-        got = {}
-        for flag in ('1', '0'):
-            monkeypatch.setenv('DGPAMD_NN_FILTER', flag)
-            got[flag] = npy(eng.nn_query(dq, dx, m))
-        np.testing.assert_array_equal(got['1'], got['0'], err_msg=name)
-        for i in rng.integers(0, len(q), 12):   # ... and both against brute force
-            dist = ((x - q[i]) ** 2).sum(1)
-            want = np.lexsort((np.arange(len(x)), dist))[:m]
-            # (numpy sums the squares in another order: compare the sets through their distances)
-            np.testing.assert_allclose(np.sort(dist[got['1'][i]]), np.sort(dist[want]), rtol=0, atol=1e-12 * max(1.0, dist.max()), err_msg=name)
+    with engine_under(NN_FILTER=1) as e1, engine_under(NN_FILTER=0) as e0:
+        for name, q, x, m in cases:
+            dq, dx = eng.tensor(q), eng.tensor(x)
+            got = {'1': npy(e1.nn_query(dq, dx, m)), '0': npy(e0.nn_query(dq, dx, m))}
+            np.testing.assert_array_equal(got['1'], got['0'], err_msg=name)
+            for i in rng.integers(0, len(q), 12):   # ... and both against brute force
+                dist = ((x - q[i]) ** 2).sum(1)
+                want = np.lexsort((np.arange(len(x)), dist))[:m]
+                # (numpy sums the squares in another order: compare the sets through their distances)
+                np.testing.assert_allclose(np.sort(dist[got['1'][i]]), np.sort(dist[want]), rtol=0, atol=1e-12 * max(1.0, dist.max()), err_msg=name)
 
 
 def test_vecchia_spsolve_long_chain(eng):
@@ -882,7 +941,7 @@ def test_linkgp_sexp_mfma_equals_direct_across_chunks(eng):
 
 
 @pytest.mark.parametrize('kind,n,M,Dw,Dz', [('matern2.5', 130, 4500, 3, 1), ('matern2.5', 700, 1100, 5, 0), ('sexp', 130, 4500, 3, 1)])
-def test_linkgp_launch_geometry_does_not_change_a_bit(eng, monkeypatch, kind, n, M, Dw, Dz):
+def test_linkgp_launch_geometry_does_not_change_a_bit(eng, kind, n, M, Dw, Dz):
     """Round 5: the record-based pair kernels take as many test points per launch as make >= 32 rounds of workgroups (csrc/predict.hip
     pair_chunk; 256 before), the Matern kernel's records of a step are requested between its column tiles instead of behind the
     step's barrier, with scalar addresses.  None of that touches a pair's arithmetic: the earlier geometry (DGPAMD_PAIR_CHUNK=256,
@@ -900,16 +959,14 @@ def test_linkgp_launch_geometry_does_not_change_a_bit(eng, monkeypatch, kind, n,
     z = rng.uniform(size=(M, Dz)) if Dz else None
     args = (eng.tensor(mm), eng.tensor(vv), eng.tensor(z) if Dz else None, eng.tensor(X[:, :Dw]), eng.tensor(X[:, Dw:]) if Dz else None, length,
             eng.tensor(st['Rinv']), n, eng.tensor(st['Rinv_y']), 1.4, 1e-3)
-    for v in ('DGPAMD_PAIR_CHUNK', 'DGPAMD_JSEP_PIPE', 'DGPAMD_JSEP_TCH', 'DGPAMD_JSEXP_TCH'):
-        monkeypatch.delenv(v, raising=False)
-    m0, v0 = (npy(t) for t in eng.linkgp_predict(kind, *args))
-    for env in ({'DGPAMD_PAIR_CHUNK': '256', 'DGPAMD_JSEP_PIPE': '0'}, {'DGPAMD_JSEP_TCH': '16'}, {'DGPAMD_JSEP_TCH': '64', 'DGPAMD_PAIR_CHUNK': '416'},
-                {'DGPAMD_PAIR_CHUNK': '96', 'DGPAMD_JSEP_PIPE': '0', 'DGPAMD_JSEP_TCH': '8'}, {'DGPAMD_JSEXP_TCH': '256'}, {'DGPAMD_JSEXP_TCH': '64', 'DGPAMD_PAIR_CHUNK': '160'}):
-        for k, val in env.items():
-            monkeypatch.setenv(k, val)
-        m1, v1 = (npy(t) for t in eng.linkgp_predict(kind, *args))
-        for k in env:
-            monkeypatch.delenv(k)
+    unset = dict(PAIR_CHUNK=None, JSEP_PIPE=None, JSEP_TCH=None, JSEXP_TCH=None)
+    with engine_under(**unset) as e:
+        assert [e.tuning(k) for k in ('PAIR_CHUNK', 'JSEP_PIPE', 'JSEP_TCH', 'JSEXP_TCH')] == [0, 2, 0, 0]   # (0: the built-in geometry)
+        m0, v0 = (npy(t) for t in e.linkgp_predict(kind, *args))
+    for env in ({'PAIR_CHUNK': '256', 'JSEP_PIPE': '0'}, {'JSEP_TCH': '16'}, {'JSEP_TCH': '64', 'PAIR_CHUNK': '416'},
+                {'PAIR_CHUNK': '96', 'JSEP_PIPE': '0', 'JSEP_TCH': '8'}, {'JSEXP_TCH': '256'}, {'JSEXP_TCH': '64', 'PAIR_CHUNK': '160'}):
+        with engine_under(**dict(unset, **env)) as e:
+            m1, v1 = (npy(t) for t in e.linkgp_predict(kind, *args))
         np.testing.assert_array_equal(m1, m0, err_msg=str(env))
         np.testing.assert_array_equal(v1, v0, err_msg=str(env))
     sl = slice(M - 12, M)
@@ -1093,7 +1150,6 @@ def test_linkgp_order_classes_equal_any_order(eng, n, M, Dw, Dz):
     predictions of the caller's order -- the same sums over all pairs, functions.py:453-494 -- to rounding, the class-free run
     (DGPAMD_JSEP_NOCLASS) and the direct formula included; inputs with zero variances, ties between coordinates (the
     class bounds are <= / >), sizes off the tile edge; the leave-one-out call takes `pos` as its drop list."""
-    import os
     import torch
     from oracle import dgp_oracle as O
     from dgp_amd.ops import cell_order
@@ -1120,12 +1176,9 @@ def test_linkgp_order_classes_equal_any_order(eng, n, M, Dw, Dz):
                                                  cells['ry'], 1.3, nug))
     close(m1, m0, rtol=1e-9, atol=1e-11)   # (sums of terms up to 1e3 times their total, taken in another order)
     close(v1, v0, rtol=1e-6, atol=1e-8)
-    os.environ['DGPAMD_JSEP_NOCLASS'] = '1'
-    try:
-        m2, v2 = (npy(t) for t in eng.linkgp_predict('matern2.5', dm, dv, dz, cells['W'], cells['Wg'], length, cells['Rinv'], n,
-                                                     cells['ry'], 1.3, nug))
-    finally:
-        del os.environ['DGPAMD_JSEP_NOCLASS']
+    with engine_under(JSEP_NOCLASS=1) as e:
+        m2, v2 = (npy(t) for t in e.linkgp_predict('matern2.5', dm, dv, dz, cells['W'], cells['Wg'], length, cells['Rinv'], n,
+                                                   cells['ry'], 1.3, nug))
     close(m2, m1, rtol=1e-13, atol=1e-14)   # (the mean does not pass through the pair kernel)
     close(v2, v1, rtol=1e-6, atol=1e-8)
     lmr, lvr = O.link_gp_predict(mm, vv, z, W, X[:, Dw:] if Dz else None, st['Rinv'], st['Rinv_y'], 1.3, length, nug, 'matern2.5')
@@ -1148,7 +1201,6 @@ def test_vecchia_gp_register_kernel_equals_lds_kernel(eng, name, D, pm):
     readlane broadcasts, no LDS) and through the one-wave-per-point LDS kernel it replaces (DGPAMD_VECCHIA_LDS=1): the same
     means and variances; conditioning sets shorter than pm (trailing -1 entries), a test-point count off the four-per-
     workgroup grid, replicate weights on the nugget, anisotropic lengthscales; a few points against the oracle."""
-    import os
     import torch
     from oracle import dgp_oracle as O
     rng = np.random.default_rng(5 + D)
@@ -1165,12 +1217,8 @@ def test_vecchia_gp_register_kernel_equals_lds_kernel(eng, name, D, pm):
         NN[t, max(1, pm - 1 - i % pm):] = -1
     args = (name, dq, dX, NN, eng.tensor(y), 1.7, length, 1e-3, eng.tensor(nd))
     m1, v1 = (npy(t) for t in eng.vecchia_gp(*args))
-    os.environ['DGPAMD_VECCHIA_LDS'] = '1'
-    os.environ['DGPAMD_POISON_LDS'] = '1'   # (every CU's LDS filled with NaNs before the LDS kernel's launch)
-    try:
-        m0, v0 = (npy(t) for t in eng.vecchia_gp(*args))
-    finally:
-        del os.environ['DGPAMD_VECCHIA_LDS'], os.environ['DGPAMD_POISON_LDS']
+    with engine_under(VECCHIA_LDS=1, POISON_LDS=1) as e:   # (every CU's LDS filled with NaNs before the LDS kernel's launch)
+        m0, v0 = (npy(t) for t in e.vecchia_gp(*args))
     assert np.all(np.isfinite(m1)) and np.all(v1 > 0)
     close(m1, m0, rtol=1e-9, atol=1e-11)
     close(v1, v0, rtol=1e-8, atol=1e-11)
@@ -1189,7 +1237,6 @@ def test_vecchia_linkgp_register_kernel_equals_lds_kernel(eng, Dw, Dz, pm, kind)
     per-lane separable records broadcast with v_readlane; no LDS) and through the LDS kernel they replace: the same means and
     variances, with and without deterministic global inputs, conditioning sets shorter than pm, zero input variances, ties
     between coordinates, a test-point count off the four-per-workgroup grid; a few points against the oracle."""
-    import os
     from oracle import dgp_oracle as O
     rng = np.random.default_rng(11 + Dw + Dz)
     n, M = 1200, 403
@@ -1213,12 +1260,8 @@ def test_vecchia_linkgp_register_kernel_equals_lds_kernel(eng, Dw, Dz, pm, kind)
     args = (kind, eng.tensor(mm), eng.tensor(vv), eng.tensor(z) if Dz else None, eng.tensor(W), eng.tensor(Wg) if Dz else None, NN,
             eng.tensor(y), 1.4, length, 1e-3, eng.tensor(nd))
     m1, v1 = (npy(t) for t in eng.vecchia_linkgp(*args))
-    os.environ['DGPAMD_VECCHIA_LDS'] = '1'
-    os.environ['DGPAMD_POISON_LDS'] = '1'   # (every CU's LDS filled with NaNs before the LDS kernel's launch)
-    try:
-        m0, v0 = (npy(t) for t in eng.vecchia_linkgp(*args))
-    finally:
-        del os.environ['DGPAMD_VECCHIA_LDS'], os.environ['DGPAMD_POISON_LDS']
+    with engine_under(VECCHIA_LDS=1, POISON_LDS=1) as e:   # (every CU's LDS filled with NaNs before the LDS kernel's launch)
+        m0, v0 = (npy(t) for t in e.vecchia_linkgp(*args))
     assert np.all(np.isfinite(m1)) and np.all(np.isfinite(v1))
     close(m1, m0, rtol=1e-9, atol=1e-11)
     close(v1, v0, rtol=1e-7, atol=1e-10)

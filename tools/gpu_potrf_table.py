@@ -13,7 +13,7 @@ e = Engine(0)
 rng = np.random.default_rng(0)
 Np = e.padded_dim(n)
 ev = (e.event(), e.event())
-print('lib %s  split_min %s  n=%d  median / min ms over %d' % (os.path.basename(os.environ.get('DGPAMD_LIB', 'libdgp_amd.so')), os.environ.get('DGPAMD_MEGA_SPLIT_MIN', '-'), n, reps))
+print('lib %s  n=%d  median / min ms over %d' % (os.path.basename(os.environ.get('DGPAMD_LIB', 'libdgp_amd.so')), n, reps))
 for B in batches:
     X, y = e.tensor(rng.uniform(size=(B, n, 5))), e.tensor(rng.normal(size=n))
     A, T, S = e.empty(B, Np, Np), e.empty(B, Np, Np), e.empty(B, Np, Np)
