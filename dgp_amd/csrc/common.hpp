@@ -214,8 +214,16 @@ __device__ __forceinline__ void corr_accum_matern(double d, double &prod, double
 // "1.5 * 2^52" addition (the integer then sits in the low word of the sum: no v_rndne / v_cvt), the scaling by 2^k a
 // multiplication by a double whose exponent field is written with integer arithmetic (no v_ldexp).  On gfx950 v_rndne_f64,
 // v_cvt_i32_f64 and v_ldexp_f64 issue at a quarter of v_fma_f64's rate: three of them cost as much as the twelve
-// multiply-adds of the polynomial (PMC: 31 VALU instructions per pair but 78 % of the issue cycles).  k is clamped at -1022:
-// arguments beyond ~708 give ~1e-308 instead of 0, which the weights multiply into nothing.
+// multiply-adds of the polynomial (PMC: 31 VALU instructions per pair but 78 % of the issue cycles).
+// Arguments beyond EXPN_XMAX give exactly 0 (exp(-707.5) = 5e-308 is the smallest value returned), up to +inf: past it k leaves the range of
+// the exponent field (k < -1022), from x = 2^31 ln 2 = 1.4886e9 on the low word of kf, and from ~2^52 on r is no remainder any more
+// -- the unguarded form returned -3e135, 6.7e307, inf there.  The guard is a compare and a select on the RESULT: a NaN argument
+// fails the compare and leaves through the arithmetic as NaN (a v_min_f64 against the bound would turn it into the bound).
+// Below the bound nothing changes: the same operations, the same bits.
+// NaN: the plain forms return NaN for every NaN (p is NaN and stays so through the product).  The table forms add e << 20 to the
+// high word of v, and e is cut from kf's mantissa, which carries a NaN's payload: they return NaN for the NaNs arithmetic produces
+// (the canonical one, payload bits 8..39 zero), while a NaN with a hand-made payload there can come out as a finite number.
+#define EXPN_XMAX 707.5   // (k >= -1021, and e >= -1021 in the table form: e = floor(k / 256) with k >= -261302)
 __device__ __forceinline__ double exp_negated(double x) {
     const double MAGIC = 6755399441055744.0;   // 1.5 * 2^52
     const double kf = fma(x, -1.44269504088896338700e+00, MAGIC);
@@ -235,9 +243,9 @@ __device__ __forceinline__ double exp_negated(double x) {
     p = fma(p, r, 0.5);
     p = fma(p, r, 1.0);
     p = fma(p, r, 1.0);
-    int ki = __double2loint(kf);               // k as a two's-complement integer
-    ki = ki < -1022 ? -1022 : ki;
-    return p * __hiloint2double((ki + 1023) << 20, 0);
+    const int ki = __double2loint(kf);         // k as a two's-complement integer (>= -1021 up to EXPN_XMAX)
+    const double v = p * __hiloint2double((int)(((unsigned)ki + 1023u) << 20), 0);   // (unsigned: beyond EXPN_XMAX the sum wraps, and the select drops it)
+    return x > EXPN_XMAX ? 0.0 : v;
 }
 
 // exp_negated with every Horner step pinned to ONE three-operand v_fma_f64 whose constant sits in an SGPR pair.  Left to itself the
@@ -264,9 +272,9 @@ __device__ __forceinline__ double exp_negated_v3(double x) {
     p = fma(p, r, 0.5);
     p = fma(p, r, 1.0);
     p = fma(p, r, 1.0);
-    int ki = __double2loint(kf);               // k as a two's-complement integer
-    ki = ki < -1022 ? -1022 : ki;
-    return p * __hiloint2double((ki + 1023) << 20, 0);
+    const int ki = __double2loint(kf);         // k as a two's-complement integer (>= -1021 up to EXPN_XMAX)
+    const double v = p * __hiloint2double((int)(((unsigned)ki + 1023u) << 20), 0);   // (unsigned: beyond EXPN_XMAX the sum wraps, and the select drops it)
+    return x > EXPN_XMAX ? 0.0 : v;
 }
 
 // The same with a table tab[j] = 2^(j/N) (in LDS): exp(-x) = 2^e tab[j] exp(r), k = round(-N x / ln 2) = N e + j,
@@ -293,11 +301,11 @@ __device__ __forceinline__ double exp_negated_tab(double x, const double *tab) {
     p = fma(p, r, 1.0);
     const int ki = __double2loint(kf);
     // k >> 8 from bits 8..39 of kf's mantissa (v_alignbit_b32: one instruction, as the 32-bit shift it replaces): the low word alone wraps
-    // from x = 2^31 ln 2 / 256 = 5.8e6 on and the clamp below was passed by; this form is right up to |k| < 2^39, x = 1.5e9
-    int e = (int)__builtin_amdgcn_alignbit((unsigned)__double2hiint(kf), (unsigned)ki, 8);
-    e = e < -1021 ? -1021 : e;
+    // from x = 2^31 ln 2 / 256 = 5.8e6 on; this form is right up to |k| < 2^39, x = 1.5e9, and needed up to EXPN_XMAX only
+    const int e = (int)__builtin_amdgcn_alignbit((unsigned)__double2hiint(kf), (unsigned)ki, 8);
     const double v = tab[ki & 255] * p;
-    return __hiloint2double(__double2hiint(v) + (e << 20), __double2loint(v));
+    const double w = __hiloint2double((int)((unsigned)__double2hiint(v) + ((unsigned)e << 20)), __double2loint(v));   // (unsigned: wraps beyond EXPN_XMAX, dropped by the select)
+    return x > EXPN_XMAX ? 0.0 : w;   // (see exp_negated)
 }
 
 // exp_negated_tab in two halves, for a caller that issues the table read well ahead of its use (the LDS round trip sat in front of every
@@ -315,19 +323,22 @@ __device__ __forceinline__ double exp_negated_tab_end(double x, double kf, doubl
     p = fma(p, r, 0.5);
     p = fma(p, r, 1.0);
     p = fma(p, r, 1.0);
-    int e = (int)__builtin_amdgcn_alignbit((unsigned)__double2hiint(kf), (unsigned)__double2loint(kf), 8);   // (k >> 8 for |k| < 2^39: see exp_negated_tab)
-    e = e < -1021 ? -1021 : e;
+    const int e = (int)__builtin_amdgcn_alignbit((unsigned)__double2hiint(kf), (unsigned)__double2loint(kf), 8);   // (k >> 8 for |k| < 2^39: see exp_negated_tab)
     const double v = t * p;
-    return __hiloint2double(__double2hiint(v) + (e << 20), __double2loint(v));
+    const double w = __hiloint2double((int)((unsigned)__double2hiint(v) + ((unsigned)e << 20)), __double2loint(v));   // (unsigned: wraps beyond EXPN_XMAX, dropped by the select)
+    return x > EXPN_XMAX ? 0.0 : w;
 }
 
-// lower-triangle tile index t -> (bi, bj), bi >= bj, t = bi(bi+1)/2 + bj
+// lower-triangle tile index t -> (bi, bj), bi >= bj, t = bi(bi+1)/2 + bj, for every 0 <= t < 2^31.  Unsigned, and only b (b + 1) is
+// ever formed: the estimate and the answer are at most 65535, so it stays below 2^32.  (With signed products of (b + 1)(b + 2) the
+// correction wrapped from bi = 46340 on, and from t = 65535 * 65536 / 2 on its first loop never ended.)
 __device__ __forceinline__ void tri_decode(int t, int &bi, int &bj) {
-    int b = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
-    while ((b + 1) * (b + 2) / 2 <= t) ++b;
-    while (b * (b + 1) / 2 > t) --b;
-    bi = b;
-    bj = t - b * (b + 1) / 2;
+    const unsigned tu = (unsigned)t;
+    unsigned b = (unsigned)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+    while (b * (b + 1) / 2 > tu) --b;
+    while (tu - b * (b + 1) / 2 > b) ++b;
+    bi = (int)b;
+    bj = (int)(tu - b * (b + 1) / 2);
 }
 
 // ---- cross-file internals -------------------------------------------------

@@ -43,6 +43,20 @@ __device__ __forceinline__ double rcp_f64(double d) {
     return fma(x, e, x);
 }
 
+// 1/sqrt(d) and sqrt(d): hardware estimate + two Newton rounds + one correction of the root (a few ulp)
+__device__ __forceinline__ void rsqrt_sqrt(double d, double &inv, double &sd) {
+    double y = __builtin_amdgcn_rsq(d);
+    const double h = 0.5 * d;
+    double e = fma(-h * y, y, 0.5);
+    y = fma(y, e, y);
+    e = fma(-h * y, y, 0.5);
+    y = fma(y, e, y);
+    double r = d * y;
+    r = fma(0.5 * y, fma(-r, r, d), r);
+    inv = y;
+    sd = r;
+}
+
 struct DiagShared {
     double f[16 * 17];      // the 16x16 diagonal tile, f[row * 17 + col]: in, then the elimination's result (upper part: the
                             // unscaled factor, below the diagonal of pivot columns: -pivot_col * (unit lower factor)^-1)

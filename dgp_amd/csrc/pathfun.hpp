@@ -68,6 +68,18 @@ __device__ __forceinline__ double cos_reduced_impl(double a, double *msin) {
 }
 __device__ __forceinline__ double cos_reduced(double a) { return cos_reduced_impl<false>(a, nullptr); }
 
+// q(t) = d log(factor) / dt of one dimension's factor of the correlation, t the scaled difference (pathfun_grad.hip)
+template <int KIND>
+__device__ __forceinline__ double dlog_factor(double t) {
+    if (KIND == DGPAMD_SEXP) return -2.0 * t;
+    const double r = fabs(t);
+    const double poly = fma(r, fma(r, 5.0 / 3.0, SQRT5), 1.0), lin = fma(r, SQRT5, 1.0);
+    double y = __builtin_amdgcn_rcp(poly);
+    y = fma(fma(-poly, y, 1.0), y, y);
+    y = fma(fma(-poly, y, 1.0), y, y);
+    return (-5.0 / 3.0 * t) * (lin * y);
+}
+
 // c(x, w) from the scaled rows xs (registers) and w (LDS, read by broadcast)
 template <int KIND, int DT>
 __device__ __forceinline__ double corr_row(const double (&xs)[DT], const double *__restrict__ w) {

@@ -6,6 +6,7 @@
 // forward solves cost nothing extra.  Neighbour search is exact brute force on
 // device (multi-pass selection in (distance, index) order -> deterministic).
 #include "common.hpp"
+#include "diagfac.hpp"   // (rsqrt_sqrt)
 #include "linkfun.hpp"
 #include "vecchia_pred.hpp"
 #include "wave.hpp"
@@ -1017,20 +1018,6 @@ __device__ __forceinline__ double row_allreduce_sum(double v) {
     ROR_ADD(0x128) ROR_ADD(0x124) ROR_ADD(0x122) ROR_ADD(0x121)
 #undef ROR_ADD
     return v;
-}
-
-// 1/sqrt(d) and sqrt(d): hardware estimate + two Newton rounds + one correction of the root (a few ulp)
-__device__ __forceinline__ void rsqrt_sqrt(double d, double &inv, double &sd) {
-    double y = __builtin_amdgcn_rsq(d);
-    const double h = 0.5 * d;
-    double e = fma(-h * y, y, 0.5);
-    y = fma(y, e, y);
-    e = fma(-h * y, y, 0.5);
-    y = fma(y, e, y);
-    double r = d * y;
-    r = fma(0.5 * y, fma(-r, r, d), r);
-    inv = y;
-    sd = r;
 }
 
 // value of lane C of the caller's 16-lane group.  s_nop 4: a DPP source written by the previous VALU needs two wait states

@@ -644,6 +644,19 @@ class Engine:
         self._chk(self._enter() or lib.dgpamd_nn_ordered(self.h, n, D, _dp(x), m, _dp(out)))
         return out
 
+    MATHFN = dict(exp_negated=0, exp_negated_v3=1, exp_negated_tab=2, exp_negated_tab2=3, cos_reduced=4, cos_sin_reduced=5,
+                  rsqrt=6, rsqrt_sqrt=7, rcp=8, dlog_matern25=9, dlog_sexp=10, exp_table=11, tri_decode=12)
+    _MATHFN_TWO = ('cos_sin_reduced', 'rsqrt_sqrt', 'tri_decode')
+
+    def debug_mathfn(self, fn, a):
+        """Testing aid (dgpamd_debug_mathfn): one of the library's own device math functions on every element of the float64 tensor
+        `a`, one lane per element.  fn: a key of Engine.MATHFN.  Returns one tensor, or two for the functions with two results."""
+        a = a.contiguous()
+        out0 = self.empty(a.numel())
+        out1 = self.empty(a.numel()) if fn in self._MATHFN_TWO else None
+        self._chk(self._enter() or lib.dgpamd_debug_mathfn(self.h, self.MATHFN[fn], a.numel(), _dp(a), _dp(out0), _dp(out1)))
+        return out0 if out1 is None else (out0, out1)
+
     def nn_query(self, q, x, m):
         M, D = q.shape
         n = x.shape[0]

@@ -446,6 +446,39 @@ int dgpamd_nn_query(dgpamd_ctx *ctx, int64_t M, int64_t n, int D, const double *
  * engine call this entry point before every library call. */
 int dgpamd_debug_poison_lds(dgpamd_ctx *ctx);
 
+/* Testing aid: the library's own device math functions, one lane per element (csrc/mathprobe.hip calls the functions the
+ * kernels inline, not copies).  a, out0, out1: `count` doubles each; out1 may be NULL where fn has one result.
+ *   fn                              out0                 out1
+ *   DGPAMD_FN_EXP_NEGATED           exp(-a)
+ *   DGPAMD_FN_EXP_NEGATED_V3        exp(-a)
+ *   DGPAMD_FN_EXP_NEGATED_TAB       exp(-a)
+ *   DGPAMD_FN_EXP_NEGATED_TAB2      exp(-a)                        (exp_negated_tab_begin + _end)
+ *   DGPAMD_FN_COS_REDUCED           cos(a)
+ *   DGPAMD_FN_COS_SIN_REDUCED       cos(a)               -sin(a)
+ *   DGPAMD_FN_RSQRT                 1/sqrt(a)                      (rsqrt_f64)
+ *   DGPAMD_FN_RSQRT_SQRT            1/sqrt(a)            sqrt(a)
+ *   DGPAMD_FN_RCP                   1/a                            (rcp_f64)
+ *   DGPAMD_FN_DLOG_MATERN25         dlog_factor<matern2.5>(a)
+ *   DGPAMD_FN_DLOG_SEXP             dlog_factor<sexp>(a)
+ *   DGPAMD_FN_EXP_TABLE             tab[(int)a], the table of exp_negated_tab as the kernels build it in LDS ((int)a taken mod 256)
+ *   DGPAMD_FN_TRI_DECODE            bi                   bj        of tri_decode((int)a)
+ * An unknown fn, count <= 0 or a null pointer (out1 where fn has two results included): DGPAMD_BAD_ARG. */
+#define DGPAMD_FN_EXP_NEGATED 0
+#define DGPAMD_FN_EXP_NEGATED_V3 1
+#define DGPAMD_FN_EXP_NEGATED_TAB 2
+#define DGPAMD_FN_EXP_NEGATED_TAB2 3
+#define DGPAMD_FN_COS_REDUCED 4
+#define DGPAMD_FN_COS_SIN_REDUCED 5
+#define DGPAMD_FN_RSQRT 6
+#define DGPAMD_FN_RSQRT_SQRT 7
+#define DGPAMD_FN_RCP 8
+#define DGPAMD_FN_DLOG_MATERN25 9
+#define DGPAMD_FN_DLOG_SEXP 10
+#define DGPAMD_FN_EXP_TABLE 11
+#define DGPAMD_FN_TRI_DECODE 12
+#define DGPAMD_FN_COUNT 13
+int dgpamd_debug_mathfn(dgpamd_ctx *ctx, int fn, int64_t count, const double *a, double *out0, double *out1);
+
 /* ---- a19-a21  Vecchia likelihoods and sampler ---------------------------------
  * vecchia_llik vecchia.py:164-180 ; vecchia_nllik :182-242 (raw sums; the host
  * finishes the scale_est / replicate branches) ; L_matrix :409-424 ;

@@ -76,3 +76,12 @@ def test_product_never_imports_the_oracle():
             if f.endswith('.py'):
                 txt = open(os.path.join(dirpath, f)).read()
                 assert 'oracle' not in txt.replace('the oracle', ''), f
+
+
+def test_mathfn_numbers_match_header():
+    """Engine.MATHFN (the keys of Engine.debug_mathfn) carries the DGPAMD_FN_* numbers of the header, all of them."""
+    from dgp_amd.ops import Engine
+    src = open(os.path.join(ROOT, 'include', 'dgp_amd.h')).read()
+    header = {k.lower(): int(v) for k, v in re.findall(r'#define\s+DGPAMD_FN_([A-Z0-9_]+)\s+(\d+)', src)}
+    count = header.pop('count')
+    assert header == Engine.MATHFN and sorted(header.values()) == list(range(count))

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import case
+from far_ref import FAR_LENGTH, FAR_NUGGET, FAR_SCALE, check_zeros, far_inputs
 
 pytestmark = pytest.mark.gpu
 
@@ -136,6 +137,66 @@ def test_kmatrix_at_the_maximum_dimension(eng, name, full):
         close(A[n, :n], y, rtol=0, atol=0)
 
 
+def close_or_zero(a, ref, rtol, atol):
+    """|a| <= 1e-300 where the reference is exactly 0 (far_ref.check_zeros); the sibling test's tolerance everywhere else."""
+    a, ref = np.asarray(a, float), np.asarray(ref, float)
+    nz = check_zeros(a, ref)
+    close(a[nz], ref[nz], rtol=rtol, atol=atol)
+
+
+@pytest.mark.parametrize('s', [1.0, 1e4])
+@pytest.mark.parametrize('name', ['sexp', 'matern2.5'])
+@pytest.mark.parametrize('full', [True, False])
+def test_kmatrix_beyond_the_exponent_range(eng, name, full, s):
+    """Exponents from 4.5e5 to beyond 2^63 (far_inputs): K is the oracle's (1 + nugget) I, n = 65 (two tiles)."""
+    from oracle import dgp_oracle as O
+    n = 65
+    X = far_inputs(n, s)
+    Kref = O.k_matrix(X, FAR_LENGTH, FAR_NUGGET, name)
+    assert np.count_nonzero(Kref) == n
+    if full:
+        K = npy(eng.kmatrix(name, eng.tensor(X), None, None, FAR_LENGTH, FAR_NUGGET))
+        close_or_zero(K, Kref, rtol=1e-12, atol=1e-15)
+    else:
+        y = np.random.default_rng(1).normal(size=n)
+        A = npy(eng.kmatrix(name, eng.tensor(X), None, None, FAR_LENGTH, FAR_NUGGET, full=False, Y=eng.tensor(y)))
+        K = A[:n, :n]
+        close_or_zero(np.tril(K), np.tril(Kref), rtol=1e-12, atol=1e-15)
+        close(A[n, :n], y, rtol=0, atol=0)
+    assert np.all(np.diag(K) == 1.0 + FAR_NUGGET)
+
+
+@pytest.mark.parametrize('name', ['sexp', 'matern2.5'])
+def test_kmatrix_keeps_a_nan_input_in_its_row_and_column(eng, name):
+    """A NaN in one input row: NaN in that row and column of K and nowhere else, as in the oracle (whose diagonal is set, not
+    computed) -- the exponentials' guard for huge arguments must not turn a NaN argument into a number."""
+    from oracle import dgp_oracle as O
+    n = 65
+    X = far_inputs(n, 1.0)
+    X[7, 1] = np.nan
+    with np.errstate(invalid='ignore'):
+        Kref = O.k_matrix(X, FAR_LENGTH, FAR_NUGGET, name)
+    K = npy(eng.kmatrix(name, eng.tensor(X), None, None, FAR_LENGTH, FAR_NUGGET))
+    assert np.isnan(Kref).sum() == 2 * (n - 1)
+    assert np.array_equal(np.isnan(K), np.isnan(Kref))
+    ok = ~np.isnan(Kref)
+    close_or_zero(K[ok], Kref[ok], rtol=1e-12, atol=1e-15)
+
+
+@pytest.mark.parametrize('s', [1.0, 1e4])
+@pytest.mark.parametrize('name', ['sexp', 'matern2.5'])
+def test_loglik_beyond_the_exponent_range(eng, name, s):
+    """log_likelihood on far_inputs (K = (1 + nugget) I in the oracle) at test_loglik_batched_vs_oracle's tolerance."""
+    from oracle import dgp_oracle as O
+    n = 65
+    X = far_inputs(n, s)
+    y = np.random.default_rng(2).normal(size=n)
+    ll, info = eng.loglik(name, eng.tensor(X), None, None, FAR_LENGTH, FAR_NUGGET, FAR_SCALE, eng.tensor(y))
+    eng.sync()
+    assert not npy(info).any()
+    close(npy(ll).reshape(-1)[0], O.log_likelihood(X, y, FAR_LENGTH, FAR_SCALE, FAR_NUGGET, name), rtol=1e-10)
+
+
 def test_kmatrix_rejects_views_it_would_write_wrongly(eng):
     """Engine.kmatrix takes the row stride of a caller's `out` (rows on 128-byte lines: bench.py); a transposed or too narrow
     view must be refused, not written in another layout."""
@@ -149,7 +210,7 @@ def test_kmatrix_rejects_views_it_would_write_wrongly(eng):
         eng.kmatrix('sexp', X, None, None, [1.0], 1e-6, out=eng.empty(70, 64))
 
 
-def test_sexp_link_gp_with_exponents_beyond_the_tables_old_range(eng):
+def test_sexp_link_gp_with_exponents_beyond_the_tables_old_range(eng, lengthscale=1e-3):
     """linkgp_Jsexp2_kernel's table exponential took k = round(-256 x / ln 2) from the low word of the magic-number sum: from
     x = 5.8e6 on the word wrapped and the underflow clamp was passed by.  Lengthscales of 1e-3 against inputs of
     order one put most pair exponents between 1e6 and 1e8: every such J entry is exactly zero in the reference's arithmetic
@@ -159,7 +220,7 @@ def test_sexp_link_gp_with_exponents_beyond_the_tables_old_range(eng):
     n, M, Dw = 200, 40, 3
     W = rng.normal(size=(n, Dw)) * 2.0
     y = rng.normal(size=n)
-    length, scale, nugget = np.array([1e-3]), 1.1, 1e-6
+    length, scale, nugget = np.array([lengthscale]), 1.1, 1e-6
     st = O.compute_stats(W, y, length, nugget, 'sexp', Dw)
     m, v = rng.normal(size=(M, Dw)) * 2.0, rng.uniform(1e-8, 1e-6, size=(M, Dw))
     m[:4] = W[:4] + 1e-4            # a few test points next to training points: non-trivial J_ii, everything else underflows
@@ -170,6 +231,12 @@ def test_sexp_link_gp_with_exponents_beyond_the_tables_old_range(eng):
     assert np.all(np.isfinite(lm)) and np.all(np.isfinite(lv))
     close(lm, mo, rtol=1e-9, atol=1e-12)
     close(lv, vo, rtol=1e-9, atol=1e-12)
+
+
+def test_sexp_link_gp_with_exponents_beyond_the_exponent_range(eng):
+    """The same at a lengthscale of 1e-5: pair exponents between 1e10 and 1e12, past 2^39 ln 2 / 256 = 1.4886e9 where the table
+    exponential's integer part leaves the 39 bits its exponent is cut from."""
+    test_sexp_link_gp_with_exponents_beyond_the_tables_old_range(eng, lengthscale=1e-5)
 
 
 def gpu_nll_grad(eng, d):
@@ -622,6 +689,72 @@ def test_vecchia_row_kernels_register_and_lds_versions_agree(eng, name):
             close(got['0'][3][0], got['0'][0], rtol=1e-14)       # batch member 0 is the single evaluation
             for j in range(3):                                   # and every member equals its own single evaluation
                 close(got['0'][3][j], npy(engines['0'].vecchia_llik(name, XB[j], dy, NN, ln, 1e-3, dw)), rtol=1e-14)
+
+
+@pytest.mark.parametrize('s', [1.0, 1e4])
+@pytest.mark.parametrize('name', ['sexp', 'matern2.5'])
+def test_vecchia_row_kernels_beyond_the_exponent_range(eng, name, s):
+    """vecchia_llik, vecchia_nllik and vecchia_lmatrix on far_inputs (n = 130, m = 10, neighbour arrays from the oracle): every
+    conditioning block is (1 + nugget) I in the oracle's arithmetic.  test_vecchia_kernels_golden's tolerances; sparse-factor
+    entries and gradient components that are exactly 0 there may be 1e-300 here at the most."""
+    import torch
+    from oracle import dgp_oracle as O
+    n, m = 130, 10
+    X = far_inputs(n, s)
+    y = np.random.default_rng(4).normal(size=n)
+    ones = np.ones(n)
+    NN = O.nn_ordered(X / FAR_LENGTH, m)
+    dX, dy, dNN, d1 = eng.tensor(X), eng.tensor(y), eng.tensor(NN, dtype=torch.int64), eng.tensor(ones)
+    out = npy(eng.vecchia_llik(name, dX, dy, dNN, FAR_LENGTH, FAR_NUGGET, d1))
+    close(-0.5 * (out[1] + out[0] / FAR_SCALE), O.vecchia_llik(X, y, NN, FAR_SCALE, FAR_LENGTH, FAR_NUGGET, ones, name), rtol=1e-9)
+    o, P = eng.vecchia_nllik(name, dX, dy, dNN, FAR_LENGTH, FAR_NUGGET, d1, True)
+    o = npy(o)
+    quad, logdet, dquad, dlogdet = o[0], o[1], o[2:2 + P], o[2 + P:]
+    nll, grad, _ = O.vecchia_nllik(X, y, NN, FAR_SCALE, FAR_LENGTH, FAR_NUGGET, ones, name, False, True, n, 0.0)
+    close(0.5 * (logdet + quad / FAR_SCALE), nll, rtol=1e-9)
+    assert grad[0] == 0.0 and grad[1] != 0.0
+    close_or_zero(0.5 * (dlogdet - dquad / FAR_SCALE), grad, rtol=1e-7, atol=1e-8)
+    Lref = O.L_matrix(X, NN, FAR_LENGTH, FAR_NUGGET, name)
+    assert np.count_nonzero(Lref) == n
+    close_or_zero(npy(eng.vecchia_lmatrix(name, dX, dNN, FAR_LENGTH, FAR_NUGGET)), Lref, rtol=1e-8, atol=1e-8 * np.abs(Lref).max())
+
+
+@pytest.mark.parametrize('s', [1.0, 1e4])
+@pytest.mark.parametrize('name', ['sexp', 'matern2.5'])
+def test_vecchia_predictions_beyond_the_exponent_range(eng, name, s):
+    """vecchia_gp and (sexp: the Matern linked factors follow the reference's expression, which is not finite here) vecchia_linkgp
+    on far_inputs, register and LDS kernels: M = 8 test points, four ON training points (mean y_i up to the nugget) and four
+    between them (prior mean 0, variance scale (1 + nugget)), n = 130, 10 neighbours from the oracle.
+    test_vecchia_kernels_golden's tolerances; means that are exactly 0 in the oracle may be 1e-300 here at the most."""
+    import torch
+    from oracle import dgp_oracle as O
+    n, pm = 130, 10
+    X = far_inputs(n, s)
+    y = np.random.default_rng(6).normal(size=n)
+    ones = np.ones(n)
+    xq = np.concatenate((X[[0, 5, 64, 129]], far_inputs(4, s) + 0.25 * s))
+    vq = np.full(xq.shape, 1e-12)
+    pNN = O.pred_nn(xq / FAR_LENGTH, X / FAR_LENGTH, pm)
+    gm, gv = O.gp_vecch(xq, X, pNN, y, FAR_SCALE, FAR_LENGTH, FAR_NUGGET, ones, name)
+    assert np.count_nonzero(gm) == 4
+    with np.errstate(all='ignore'):
+        lm, lv = O.link_gp_vecch(xq, vq, None, X, None, pNN, y, FAR_SCALE, FAR_LENGTH, FAR_NUGGET, ones, name)
+    if name == 'sexp':
+        assert np.count_nonzero(lm) == 4
+    else:   # (why vecchia_linkgp is not compared for the Matern kind: the reference itself is not finite on these inputs)
+        assert not (np.all(np.isfinite(lm)) and np.all(np.isfinite(lv))), (lm, lv)
+    with contextlib.ExitStack() as stack:
+        for lds in ('0', '1'):
+            e = stack.enter_context(engine_under(POISON_LDS=1, VECCHIA_LDS=lds))
+            t = e.tensor
+            dNN = t(pNN, dtype=torch.int64)
+            m_, v_ = e.vecchia_gp(name, t(xq), t(X), dNN, t(y), FAR_SCALE, FAR_LENGTH, FAR_NUGGET, t(ones))
+            close_or_zero(npy(m_), gm, rtol=1e-8, atol=1e-10)
+            close(npy(v_), gv, rtol=1e-7, atol=1e-10)
+            if name == 'sexp':
+                m_, v_ = e.vecchia_linkgp(name, t(xq), t(vq), None, t(X), None, dNN, t(y), FAR_SCALE, FAR_LENGTH, FAR_NUGGET, t(ones))
+                close_or_zero(npy(m_), lm, rtol=1e-7, atol=1e-9)
+                close(npy(v_), lv, rtol=1e-6, atol=1e-8)
 
 
 def test_nn_streaming_topk_equals_store_once_kernel(eng):

@@ -9,6 +9,8 @@ import copy
 import numpy as np
 import pytest
 
+from far_ref import check_zeros, far_inputs
+
 pytestmark = pytest.mark.gpu
 
 
@@ -109,6 +111,43 @@ def test_eval_at_64_inputs_and_without_training_rows(eng, kind):
         a = slice(p, p + 1)
         within(out[a], R.evaluate(xs[p], None, Omega, b, theta[a], None, kind, length, scale),
                R.tolerance(xs[p], None, Omega, b, theta[a], None, kind, length, scale), 'per-path n=0 %s path %d' % (kind, p))
+
+
+def within_or_zero(out, ref, tol, what):
+    """|out| <= 1e-300 where the reference is exactly 0 (far_ref.check_zeros), the forward-error bound everywhere else."""
+    out = np.asarray(out)
+    nz = check_zeros(out, ref, what)
+    print('%s: %d exact zeros' % (what, (~nz).sum()))
+    if nz.any():
+        within(out[nz], ref[nz], tol[nz], what)
+
+
+@pytest.mark.parametrize('s', [1.0, 1e4])
+@pytest.mark.parametrize('kind', ['sexp', 'matern2.5'])
+def test_eval_beyond_the_exponent_range(eng, kind, s):
+    """n = 65 training rows and M = 70 rows of far_inputs (the first 65 rows ARE training rows: c = 1 there and 0 everywhere else),
+    shared and per-path x, with random theta (the bound of every evaluation) and with theta = 0 (the correlation part alone: v[p, m]
+    sqrt(scale) on the training rows, exactly 0 on the others)."""
+    import pathfun_ref as R
+    rng = np.random.default_rng(5)
+    n, M, D, F, P, scale = 65, 70, 2, 64, 3, 1.1
+    length = np.array([1e-5])
+    W, x = far_inputs(n, s), far_inputs(M, s)
+    xs = np.stack([x, x[::-1].copy(), np.roll(x, 3, axis=0)])
+    Omega, b = features_for(kind, length, D, F, 1)
+    v = rng.normal(size=(P, n))
+    t = eng.tensor
+    for theta in (rng.normal(size=(P, F)), np.zeros((P, F))):
+        what = '%s s=%g theta %s' % (kind, s, 'random' if theta.any() else '0')
+        out = npy(eng.pathfun_eval(kind, t(x), t(W), t(Omega), t(b), t(theta), t(v), length, scale))
+        ref = R.evaluate(x, W, Omega, b, theta, v, kind, length, scale)
+        assert theta.any() or np.count_nonzero(ref) == P * n
+        within_or_zero(out, ref, R.tolerance(x, W, Omega, b, theta, v, kind, length, scale), 'shared ' + what)
+        out = npy(eng.pathfun_eval(kind, t(xs), t(W), t(Omega), t(b), t(theta), t(v), length, scale))
+        for p in range(P):
+            a = slice(p, p + 1)
+            within_or_zero(out[a], R.evaluate(xs[p], W, Omega, b, theta[a], v[a], kind, length, scale),
+                           R.tolerance(xs[p], W, Omega, b, theta[a], v[a], kind, length, scale), 'per-path %s path %d' % (what, p))
 
 
 @pytest.mark.parametrize('P', [1, 64, 65, 129, 300])

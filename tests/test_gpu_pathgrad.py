@@ -7,6 +7,8 @@ dgpamd_pathfun_eval's bit for bit.  Every comparison prints the largest error / 
 import numpy as np
 import pytest
 
+from far_ref import FAR_SCALE, far_inputs
+
 pytestmark = pytest.mark.gpu
 
 
@@ -35,13 +37,12 @@ def features_for(kind, length, D, F, seed):
     return pathfun.features(np.random.default_rng(seed), kind, length, D, F)
 
 
-def check_operator(eng, kind, length, n, D, F, P, M, shape, seed, groups=1, x=None, W=None, what=''):
+def check_operator(eng, kind, length, n, D, F, P, M, shape, seed, groups=1, x=None, W=None, what='', scale=1.7):
     """One call of pathfun_grad against the restatement, and its values against pathfun_eval's bits.  shape 'shared': x
     (M, D) and one training set; 'per-path': x (P, M, D) and `groups` training sets in mixed order."""
     import torch
     import pathgrad_ref as G
     rng = np.random.default_rng(seed)
-    scale = 1.7
     Omega, b = features_for(kind, length, D, F, seed + 1)
     if W is None:
         W = rng.uniform(size=(groups, n, D))
@@ -127,6 +128,41 @@ def test_grad_on_training_rows_and_with_large_arguments(eng, kind):
     assert np.abs(x @ Omega.T + b).max() > 300.0
     for shape in ('shared', 'per-path'):
         check_operator(eng, kind, short, n, D, 64, P, 70, shape, 8, what=kind + ' length 0.002')
+
+
+@pytest.mark.parametrize('s', [1.0, 1e4])
+@pytest.mark.parametrize('kind', ['sexp', 'matern2.5'])
+def test_grad_beyond_the_exponent_range(eng, kind, s):
+    """n = 65 training rows and M = 70 rows of far_inputs (the first 65 ARE training rows: c = 1 and q = 0 there, c = 0 on every
+    other pair), shared and per-path x.  With random theta: check_operator's bound (and pathfun_eval's bits).  With theta = 0 only
+    the correlation part is left and the restatement's gradient is exactly 0 everywhere: here it may be 1e-300 at the most, and
+    the values are v[p, m] sqrt(scale) on the training rows within pathfun_ref's bound and at most 1e-300 on the others."""
+    import pathfun_ref as R
+    import pathgrad_ref as G
+    n, M, D, F, P, scale = 65, 70, 2, 64, 3, FAR_SCALE
+    length = np.array([1e-5])
+    W, x = far_inputs(n, s)[None], far_inputs(M, s)
+    xs = np.stack([x, x[::-1].copy(), np.roll(x, 3, axis=0)])
+    what = '%s s=%g' % (kind, s)
+    check_operator(eng, kind, length, n, D, F, P, M, 'shared', 11, x=x, W=W, what=what, scale=scale)
+    check_operator(eng, kind, length, n, D, F, P, M, 'per-path', 12, x=xs, W=W, what=what, scale=scale)
+    Omega, b = features_for(kind, length, D, F, 13)
+    theta, v = np.zeros((P, F)), np.random.default_rng(14).normal(size=(P, n))
+    t = eng.tensor
+    for shape, xx in (('shared', x), ('per-path', xs)):
+        out, grad = eng.pathfun_grad(kind, t(xx), t(W[0]), t(Omega), t(b), t(theta), t(v), length, scale)
+        out, grad = npy(out), npy(grad)
+        for p in range(P):
+            a, xp = slice(p, p + 1), (xx if shape == 'shared' else xx[p])
+            with np.errstate(invalid='ignore'):
+                gref = G.grad(xp, W[0], Omega, b, theta[a], v[a], kind, length, scale)
+            assert not gref.any()
+            assert np.all(np.abs(grad[a]) <= 1e-300), (what, shape, p, np.abs(grad[a]).max())
+            ref = R.evaluate(xp, W[0], Omega, b, theta[a], v[a], kind, length, scale)
+            z = ref == 0.0
+            assert z.sum() == M - n and np.all(np.abs(out[a][z]) <= 1e-300), (what, shape, p)
+            tol = R.tolerance(xp, W[0], Omega, b, theta[a], v[a], kind, length, scale)
+            within(out[a][~z], ref[~z], tol[~z], '%s %s theta 0 path %d' % (what, shape, p))
 
 
 @pytest.mark.parametrize('shape', ['shared', 'per-path'])

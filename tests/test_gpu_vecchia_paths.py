@@ -9,6 +9,8 @@ import warnings
 import numpy as np
 import pytest
 
+from far_ref import check_zeros, far_inputs
+
 pytestmark = pytest.mark.gpu
 
 
@@ -130,6 +132,49 @@ def test_rows_equal_numpy(eng, kind, extra, form):
             np.testing.assert_array_equal(NNl[p, i, 1:1 + k], mem[te] - n)
             np.testing.assert_allclose(-Lr[p, i, 1:1 + k] * sd[p, i], b[te], rtol=0, atol=tol)
             assert np.all(NNl[p, i, 1 + k:] == -1) and np.all(Lr[p, i, 1 + k:] == 0)
+
+
+@pytest.mark.parametrize('s', [1.0, 1e4])
+@pytest.mark.parametrize('kind', ['sexp', 'matern2.5'])
+def test_rows_beyond_the_exponent_range(eng, kind, s):
+    """Training rows i s (1, 1) against a lengthscale of 1e-5 (squared-exponential exponents 2e10 i^2 and beyond 2^63, Matern ones
+    sqrt5 2e5 i and sqrt5 2e9 i: far beyond 2^31 ln 2 = 1.4886e9, where exp_negated's integer part leaves 32 bits), P = 2 paths of
+    M = 16 test rows -- path 0 half on training rows and half between them, path 1 all between --, n = 64, m = 8.  Every correlation
+    between different points is exactly 0 in numpy: the b_i are e_j / (1 + nugget) or 0.  test_rows_equal_numpy's tolerances; what
+    is exactly 0 in the restatement may be 1e-300 here at the most."""
+    import torch
+    rng = np.random.default_rng(16)
+    n, M, P, m, nugget, scale, length = 64, 16, 2, 8, 1e-6, 1.1, 1e-5
+    X = (far_inputs(n, s) / length)[None]
+    pos = np.stack([np.concatenate((rng.permutation(n)[:8], rng.permutation(n)[:8] + 0.25)), rng.permutation(n)[:M] + 0.5])
+    Q = pos[:, :, None] * s * np.ones((1, 1, 2)) / length
+    omega = np.ones(n)
+    Y = np.concatenate((np.eye(n)[None], rng.normal(size=(1, 1, n))), 1)   # (1, n + 1, n)
+    NN = eng.vpaths_nn(eng.tensor(Q), eng.tensor(X), m, None)
+    Lr, NNl, t, sd, info = eng.vpaths_rows(kind, eng.tensor(Q), eng.tensor(X), NN, eng.tensor(Y), scale, nugget)
+    assert int(npy(info)[0]) == 0
+    Lr, NNl, t, sd, NN = npy(Lr), npy(NNl), npy(t), npy(sd), npy(NN)
+
+    def close_or_zero(a, ref, atol):
+        nz = check_zeros(a, ref)
+        np.testing.assert_allclose(a[nz], ref[nz], rtol=0, atol=atol)
+
+    hits = 0
+    for p in range(P):
+        for i in range(M):
+            mem, b, sch = row_ref(kind, Q[p], X[0], NN[p, i], i, nugget, omega)
+            hits += np.count_nonzero(b)
+            tol = 1e-10 * max(1.0, np.abs(b).max())
+            assert abs(sd[p, i] - np.sqrt(scale * sch)) <= 1e-10 * np.sqrt(scale * sch)
+            tr, te = mem < n, mem >= n
+            close_or_zero(t[p, mem[tr], i], b[tr], tol)
+            np.testing.assert_allclose(t[p, n, i], Y[0, n, mem[tr]] @ b[tr], rtol=0, atol=tol * np.abs(Y).max() * n)
+            k = te.sum()
+            assert Lr[p, i, 0] == pytest.approx(1 / sd[p, i], rel=1e-14) and NNl[p, i, 0] == i
+            np.testing.assert_array_equal(NNl[p, i, 1:1 + k], mem[te] - n)
+            close_or_zero(-Lr[p, i, 1:1 + k] * sd[p, i], b[te], tol)
+            assert np.all(NNl[p, i, 1 + k:] == -1) and np.all(Lr[p, i, 1 + k:] == 0)
+    assert hits == 8
 
 
 def test_rows_refuse_a_block_over_the_lds(eng):

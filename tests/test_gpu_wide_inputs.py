@@ -13,6 +13,8 @@ the tolerances measure the kernels, not cond(K)."""
 import numpy as np
 import pytest
 
+from far_ref import far_inputs
+
 pytestmark = pytest.mark.gpu
 
 SQ5 = np.sqrt(np.longdouble(5))
@@ -145,6 +147,41 @@ def test_grad_reduce_vs_extended_precision(eng, name, D, n):
                 for got, terms, what in ((out[p], T[p], 'trace'), (out[P + p], Q[p], 'quad')):
                     ref, mag = terms.sum(), np.abs(terms).sum()
                     assert abs(np.longdouble(got) - ref) <= 1e-12 * mag, (what, p, got, float(ref), float(mag), len(length), nugget_est, W is not None)
+
+
+@pytest.mark.parametrize('s', [1.0, 1e4])
+@pytest.mark.parametrize('name', ['sexp', 'matern2.5'])
+def test_grad_reduce_beyond_the_exponent_range(eng, name, s):
+    """The same reduction where every off-diagonal correlation underflows: inputs i s (1, 1) for row i against a lengthscale of
+    1e-5 (squared-exponential exponents 2e10 i^2 and beyond 2^63, Matern ones sqrt5 2e5 i and sqrt5 2e9 i: far beyond 2^31 ln 2 =
+    1.4886e9, where the table exponential's integer part leaves the bits its exponent is cut from), n = 65, shared and per-column
+    lengthscales.  K^-1 is GIVEN as a dense symmetric matrix and alpha as a dense vector, so that every entry of dK carries
+    weight.  In extended precision every lengthscale term is exactly 0: the sums may be 1e-300 here at the most; the nugget's
+    sums keep the sibling's 1e-12 of their absolute sum."""
+    rng = np.random.default_rng(65)
+    n, nugget = 65, 1e-6
+    X = far_inputs(n, s)
+    Kinv = rng.normal(size=(n, n))
+    Kinv = 0.5 * (Kinv + Kinv.T)
+    alpha = rng.normal(size=n)
+    Np = eng.padded_dim(n)
+    buf = np.zeros((Np, Np))
+    buf[:n, :n] = Kinv
+    buf[n, :n] = -alpha
+    KiL, aL = Kinv.astype(np.longdouble), alpha.astype(np.longdouble)
+    off = ~np.eye(n, dtype=bool)
+    for length in (np.array([1e-5, 1e-5]), np.array([1e-5])):
+        K, C = corr_terms(X, length, name)
+        if len(length) == 1:
+            C = C.sum(0, keepdims=True)
+        out, P = eng.grad_reduce(name, eng.tensor(X), None, None, length, nugget, True, eng.tensor(buf))
+        out = npy(out)
+        assert P == len(C) + 1
+        for p in range(len(C)):
+            assert not (KiL * C[p] * K)[off].any() and not (np.outer(aL, aL) * C[p] * K)[off].any()
+            assert abs(out[p]) <= 1e-300 and abs(out[P + p]) <= 1e-300, (p, out[p], out[P + p], len(length))
+        for got, terms in ((out[P - 1], nugget * np.diag(KiL)), (out[2 * P - 1], nugget * aL * aL)):
+            assert abs(np.longdouble(got) - terms.sum()) <= 1e-12 * np.abs(terms).sum(), (got, float(terms.sum()), len(length))
 
 
 # ------------------------------------------------------------------ B. dgpamd_llik_batch against the oracle
