@@ -115,45 +115,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DT <= 16 ? 
 }
 
 template <int KIND, int DT>
-static int launch_pathfun(dgpamd_ctx *ctx, PathfunArgs &a, bool shared, const int32_t *group, int P) {
-    if (shared) {
-        a.P = P;
-        const size_t shm = (size_t)(KC * DT + KC + (1 + MFMA_PT) * 64 * LDM) * sizeof(double);   // (67.3 KB at DT = 64)
-        const int rc = set_lds(ctx, (const void *)pathfun_mfma_kernel<KIND, DT>, shm);
-        if (rc) return rc;
-        dim3 grid((unsigned)((a.M + 63) / 64), (unsigned)((P + 64 * MFMA_PT - 1) / (64 * MFMA_PT)));
-        hipLaunchKernelGGL((pathfun_mfma_kernel<KIND, DT>), grid, dim3(256), shm, ctx->stream, a);
-        return DGPAMD_OK;
-    }
-    const double *x = a.x, *theta = a.theta, *v = a.v;
-    double *out = a.out;
-    for (int q0 = 0; q0 < P; q0 += DGPAMD_MAXB) {   // (the groups travel by value: DGPAMD_MAXB paths per launch)
-        const int pc = P - q0 < DGPAMD_MAXB ? P - q0 : DGPAMD_MAXB;
-        a.P = pc;
-        a.x = x + (int64_t)q0 * a.stride_x;
-        a.theta = theta + (int64_t)q0 * a.F;
-        a.v = v ? v + (int64_t)q0 * a.n : nullptr;
-        a.out = out + (int64_t)q0 * a.M;
-        for (int q = 0; q < pc; ++q) a.group[q] = group ? group[q0 + q] : 0;
-        hipLaunchKernelGGL((pathfun_lane_kernel<KIND, DT>), dim3((unsigned)((a.M + 255) / 256), (unsigned)pc), dim3(256), 0,
-                           ctx->stream, a);
-    }
+static int launch_pathfun_mfma(dgpamd_ctx *ctx, PathfunArgs &a, int P) {
+    a.P = P;
+    const size_t shm = (size_t)(KC * DT + KC + (1 + MFMA_PT) * 64 * LDM) * sizeof(double);   // (67.3 KB at DT = 64)
+    const int rc = set_lds(ctx, (const void *)pathfun_mfma_kernel<KIND, DT>, shm);
+    if (rc) return rc;
+    dim3 grid((unsigned)((a.M + 63) / 64), (unsigned)((P + 64 * MFMA_PT - 1) / (64 * MFMA_PT)));
+    hipLaunchKernelGGL((pathfun_mfma_kernel<KIND, DT>), grid, dim3(256), shm, ctx->stream, a);
     return DGPAMD_OK;
 }
 
 template <int KIND>
 static int dispatch_pathfun(dgpamd_ctx *ctx, PathfunArgs &a, bool shared, const int32_t *group, int P) {
-    // The rows are padded with zero columns to the next width compiled (a zero column changes neither sum; the work grows with the
-    // padded width).  Powers of two, plus 6 and 10: the bench model's first layer has 5 inputs and its output node 5 + 5, and a DGP
-    // node behind layer 1 sees (nodes below) + (connected inputs) columns, typically in this range.
-    if (a.D <= 2) return launch_pathfun<KIND, 2>(ctx, a, shared, group, P);
-    else if (a.D <= 4) return launch_pathfun<KIND, 4>(ctx, a, shared, group, P);
-    else if (a.D <= 6) return launch_pathfun<KIND, 6>(ctx, a, shared, group, P);
-    else if (a.D <= 8) return launch_pathfun<KIND, 8>(ctx, a, shared, group, P);
-    else if (a.D <= 10) return launch_pathfun<KIND, 10>(ctx, a, shared, group, P);
-    else if (a.D <= 16) return launch_pathfun<KIND, 16>(ctx, a, shared, group, P);
-    else if (a.D <= 32) return launch_pathfun<KIND, 32>(ctx, a, shared, group, P);
-    return launch_pathfun<KIND, 64>(ctx, a, shared, group, P);
+    return pathfun_width(a.D, [&](auto dt) -> int {
+        constexpr int DT = decltype(dt)::value;
+        if (shared) return launch_pathfun_mfma<KIND, DT>(ctx, a, P);
+        launch_lane(ctx, pathfun_lane_kernel<KIND, DT>, a, group, P);
+        return DGPAMD_OK;
+    });
 }
 
 int pathfun_launch_values(dgpamd_ctx *ctx, int kind, PathfunArgs a, bool shared, const int32_t *group, int P) {
@@ -165,11 +144,10 @@ extern "C" int dgpamd_pathfun_eval(dgpamd_ctx *ctx, int kind, int64_t n, int64_t
                                    int64_t stride_x, const int32_t *group_h, int ngroups, const double *W, int64_t stride_w,
                                    const double *Omega, const double *b, const double *theta, const double *v,
                                    const double *length_h, int nlen, double scale, double *out) {
-    if (!ctx) return DGPAMD_BAD_ARG;
     PathfunArgs a;
     bool shared;
     const int bad = pathfun_args(ctx, __func__, a, shared, kind, n, M, D, F, P, x, stride_x, group_h, ngroups, W, stride_w, Omega, b,
-                                 theta, v, length_h, nlen, scale, out);
+                                 theta, v, length_h, nlen, scale, out, nullptr);
     if (bad) return bad;
     const int rc = pathfun_launch_values(ctx, kind, a, shared, group_h, P);
     if (rc) return rc;

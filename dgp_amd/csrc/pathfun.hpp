@@ -1,12 +1,14 @@
 // Generation code shared by the values of function-valued posterior draws (pathfun.hip, DESIGN I.12) and their input gradients
 // (pathfun_grad.hip, DESIGN I.13): the cosine, the rows of features and correlations, the staging of Omega / W tiles and of the
-// coefficients, and the argument block.  Both files generate the values with exactly this code, in the same order over k: the
-// values dgpamd_pathfun_grad returns are dgpamd_pathfun_eval's bit for bit.
+// coefficients, the argument block, and on the host the choice of the compiled width and the lane kernels' launches.  Both files
+// generate the values with exactly this code, in the same order over k: the values dgpamd_pathfun_grad returns are
+// dgpamd_pathfun_eval's bit for bit.
 #pragma once
 #include "common.hpp"
 #include "tile.hpp"
 
 #include <math.h>
+#include <type_traits>
 
 #ifndef PATHFUN_LIBM_COS
 #define PATHFUN_LIBM_COS 0   // 1: the library's cos in place of cos_reduced (A/B builds of tools/gpu_pathfun_bench.py)
@@ -148,7 +150,7 @@ __device__ __forceinline__ void load_coef(const double *__restrict__ C, int64_t 
 }
 
 // The argument checks and the argument block of dgpamd_pathfun_eval and dgpamd_pathfun_grad (fn: the entry's name for the message;
-// out_g stays null here).
+// out_g is null for the values alone).
 #define PATHFUN_BAD(msg)                                           \
     do {                                                           \
         snprintf(ctx->err, sizeof(ctx->err), "%s: %s", fn, msg);   \
@@ -157,7 +159,8 @@ __device__ __forceinline__ void load_coef(const double *__restrict__ C, int64_t 
 static inline int pathfun_args(dgpamd_ctx *ctx, const char *fn, PathfunArgs &a, bool &shared, int kind, int64_t n, int64_t M, int D,
                                int64_t F, int P, const double *x, int64_t stride_x, const int32_t *group_h, int ngroups,
                                const double *W, int64_t stride_w, const double *Omega, const double *b, const double *theta,
-                               const double *v, const double *length_h, int nlen, double scale, double *out) {
+                               const double *v, const double *length_h, int nlen, double scale, double *out, double *out_g) {
+    if (!ctx) return DGPAMD_BAD_ARG;
     if (n < 0 || M <= 0 || F <= 0 || P <= 0 || !x || !Omega || !b || !theta || !length_h || !out)
         PATHFUN_BAD("null pointer or empty problem");
     if (n > 0 && (!W || !v)) PATHFUN_BAD("n > 0 needs W and v");
@@ -183,11 +186,43 @@ static inline int pathfun_args(dgpamd_ctx *ctx, const char *fn, PathfunArgs &a, 
     a.stride_w = stride_w;
     a.Omega = Omega; a.b = b; a.theta = theta; a.v = v;
     a.cf = sqrt(2.0 / (double)F); a.sscale = sqrt(scale);
-    a.out = out; a.out_g = nullptr;
+    a.out = out; a.out_g = out_g;
     memset(a.group, 0, sizeof(a.group));
     return DGPAMD_OK;
 }
 #undef PATHFUN_BAD
+
+// fn(std::integral_constant<int, DT>) at the narrowest compiled width DT >= D.  The rows are padded with zero columns to that width
+// (a zero column changes neither sum; the work grows with the padded width).  Powers of two, plus 6 and 10: the bench model's first
+// layer has 5 inputs and its output node 5 + 5, and a DGP node behind layer 1 sees (nodes below) + (connected inputs) columns,
+// typically in this range.
+template <class Fn>
+static inline int pathfun_width(int D, Fn fn) {
+    if (D <= 2) return fn(std::integral_constant<int, 2>());
+    else if (D <= 4) return fn(std::integral_constant<int, 4>());
+    else if (D <= 6) return fn(std::integral_constant<int, 6>());
+    else if (D <= 8) return fn(std::integral_constant<int, 8>());
+    else if (D <= 10) return fn(std::integral_constant<int, 10>());
+    else if (D <= 16) return fn(std::integral_constant<int, 16>());
+    else if (D <= 32) return fn(std::integral_constant<int, 32>());
+    return fn(std::integral_constant<int, 64>());
+}
+
+// A lane kernel (one lane per row, blockIdx.y the path) over P paths: the groups travel by value, DGPAMD_MAXB paths per launch.
+static inline void launch_lane(dgpamd_ctx *ctx, void (*kernel)(PathfunArgs), PathfunArgs a, const int32_t *group, int P) {
+    const PathfunArgs all = a;
+    for (int q0 = 0; q0 < P; q0 += DGPAMD_MAXB) {
+        const int pc = P - q0 < DGPAMD_MAXB ? P - q0 : DGPAMD_MAXB;
+        a.P = pc;
+        a.x = all.x + (int64_t)q0 * a.stride_x;
+        a.theta = all.theta + (int64_t)q0 * a.F;
+        a.v = all.v ? all.v + (int64_t)q0 * a.n : nullptr;
+        a.out = all.out ? all.out + (int64_t)q0 * a.M : nullptr;
+        a.out_g = all.out_g ? all.out_g + (int64_t)q0 * a.M * a.D : nullptr;
+        for (int q = 0; q < pc; ++q) a.group[q] = group ? group[q0 + q] : 0;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((a.M + 255) / 256), (unsigned)pc), dim3(256), 0, ctx->stream, a);
+    }
+}
 
 // The launches of dgpamd_pathfun_eval for a filled argument block (pathfun.hip): dgpamd_pathfun_grad takes its values from here
 // where its own kernel would sum them in another order (shared x beyond the widths of its matrix form).

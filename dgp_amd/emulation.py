@@ -552,13 +552,9 @@ class emulator:
         from . import pathwalk
         e = self.engine
         xd = e.tensor(x)
-
-        def first(nd):
-            xin = pathwalk.cols(xd, nd.input_dim)
-            return xin if nd.connect is None else torch.cat((xin, pathwalk.cols(xd, nd.connect)), 1)
-
-        out = [cur.cpu().numpy() for cur in pathwalk.walk(e, [self.all_layer] * self.N, J, xd, None, first,
-                                                           lambda l, k, nodes, xin: draw(l, k, nodes[0], xin))]
+        walk = pathwalk.walk(e, [self.all_layer] * self.N, J, xd, None, lambda nd: pathwalk.first(xd, nd),
+                             lambda l, k, nodes, xin: draw(l, k, nodes[0], xin))
+        out = [cur.cpu().numpy() for cur in walk]
         out = [list(a.transpose(2, 1, 0)) for a in out]
         return out if full_layer else out[-1]
 

@@ -189,17 +189,29 @@ class gp:
         paths.check_points(x)
         k = self.kernel
         e = k.engine
+        train = self._joint_train()
+        Z = np.random.standard_normal((sample_size, len(x)))
+        y = e.tensor(np.asarray(k.output, float).reshape(1, -1))
+        out = paths.Dense().draw_shared(e, paths.hyper(k), e.tensor(x[:, self._columns()]), train, y, e.tensor(Z), sample_size)
+        return out.T.cpu().numpy()
+
+    def _joint_train(self):
+        """train = (W with global columns, L^-1) for paths.Dense and pathfun.NodePaths.build_shared; the L^-1 is built when
+        first asked for (and dropped with the statistics when compute_stats runs again)."""
+        from . import paths
+        k = self.kernel
         if k._stats is None:
             k.compute_stats()
         st = k._stats
-        if 'joint' not in st:   # (dropped with the statistics when compute_stats runs again)
-            st['joint'] = paths.factor_inverse(e, k.name, st['W'], st['Wg'], None if k.rep is None else e.tensor(k.W_diag),
+        if 'joint' not in st:
+            st['joint'] = paths.factor_inverse(k.engine, k.name, st['W'], st['Wg'], None if k.rep is None else k.engine.tensor(k.W_diag),
                                                k.length, k.nugget[0], 'the gp model')
-        xin = x[:, k.input_dim] if k.connect is None else np.concatenate((x[:, k.input_dim], x[:, k.connect]), 1)
-        Z = np.random.standard_normal((sample_size, len(x)))
-        y = e.tensor(np.asarray(k.output, float).reshape(1, -1))
-        out = paths.Dense().draw_shared(e, paths.hyper(k), e.tensor(xin), (st['Wall'], st['joint']), y, e.tensor(Z), sample_size)
-        return out.T.cpu().numpy()
+        return st['Wall'], st['joint']
+
+    def _columns(self):
+        """The columns of x that the model reads, in the order of its training inputs: input_dim, then connect."""
+        k = self.kernel
+        return np.array(k.input_dim) if k.connect is None else np.concatenate((k.input_dim, k.connect))
 
     def sample_functions(self, sample_size=50, n_features=2048):
         """sample_size posterior draws of the GP as functions (pathwise conditioning on a random-Fourier-feature prior
@@ -230,8 +242,8 @@ class gp:
         M = len(x)
         drawer = vpaths.Vecchia(m, np.random.permutation(M))
         Z = np.random.standard_normal((sample_size, M))
-        xin = x[:, k.input_dim] if k.connect is None else np.concatenate((x[:, k.input_dim], x[:, k.connect]), 1)
-        out = drawer.draw_shared(e, paths.hyper(k), e.tensor(xin), (e.tensor(k._X()), None if k.rep is None else e.tensor(k.W_diag)),
+        train = (e.tensor(k._X()), None if k.rep is None else e.tensor(k.W_diag))
+        out = drawer.draw_shared(e, paths.hyper(k), e.tensor(x[:, self._columns()]), train,
                                  e.tensor(np.asarray(k.output, float).reshape(1, -1)), e.tensor(Z), sample_size, 'the gp model')
         return out.cpu().numpy().T
 

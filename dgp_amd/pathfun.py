@@ -7,8 +7,12 @@ Matheron's rule turns it into a posterior draw:
     f(x) = sqrt(scale) (phi(x)^T theta + c(x, W) v),   v = L^-T L^-1 (y / sqrt(scale) - Phi(W) theta - sqrt(nugget omega) * eps),
 theta ~ N(0, I_F), eps ~ N(0, I_n).  Its mean over (theta, eps) is c(x, W) R^-1 y for every F; its covariance tends to the
 posterior's as F grows.  A path is held as (theta, v) and evaluated by dgpamd_pathfun_eval at any rows, any number of times,
-with the same values at the same rows.  NodePaths is the paths of one node; PathFunctions walks a DGP hierarchy with them
-(pathwalk.walk, beside the drawers paths.Dense and vpaths.Vecchia).
+with the same values at the same rows.
+
+NodePaths is the paths of one node: draw_node alone consumes the generator at creation, and NodePaths.build_shared /
+build_per_group condition its draws on a training side in the form paths.Dense.draw_shared / draw_per_path take theirs.
+PathFunctions (an emulator: pathwalk.walk over its hierarchy, beside the drawers paths.Dense and vpaths.Vecchia) and GpPaths
+(one node, numpy's global generator) are built from these and evaluate in blocks of rows through one loop, _row_blocks.
 
 The input gradient of a path is as closed-form as the path (DESIGN I.13): dgpamd_pathfun_grad returns a node's values and
 its (P, M, D) gradient from one pass, and PathFunctions.value_and_grad carries the Jacobian with respect to the emulator's
@@ -78,10 +82,20 @@ def weights(e, hyper, W, Linv, Omega, b, theta, y, eps, omega):
     return v + solve((r - Rv).contiguous())
 
 
+def draw_node(rng, kind, length, D, F, S, J, n):
+    """What is random in the S * J paths of one GP node, host arrays Omega (F, D), b (F,), theta (S * J, F), eps (S * J, n), in
+    the order features(rng, kind, length, D, F), standard_normal((S, J, F)), standard_normal((S, J, n)); rng a numpy Generator
+    or the numpy.random module.  S = 1 takes from the stream what (J, F) and (J, n) take.  An iterator: each array is drawn
+    when it is asked for and not kept here, so list(map(e.tensor, draw_node(...))) holds one host array at a time."""
+    yield from features(rng, kind, length, D, F)
+    yield rng.standard_normal((S, J, F)).reshape(S * J, F)
+    yield rng.standard_normal((S, J, n)).reshape(S * J, n)
+
+
 class NodePaths:
     """P function-valued draws of one GP node: hyper = paths.hyper(node); Omega (F, D), b (F,) its features; theta (P, F);
     W (n, D) one training set for every path, or (G, n, D) with group (host ints (P,)) picking each path's; v (P, n).
-    Everything is the object's own copy."""
+    All its own copies.  build_*: train = (W, paths.factor_inverse's L^-1), omega (n,) or None, draws = draw_node's, all on the device."""
 
     def __init__(self, hyper, Omega, b, theta, W, v, group=None):
         kind, length, scale, nugget = hyper
@@ -89,27 +103,62 @@ class NodePaths:
         self.Omega, self.b, self.theta, self.W, self.v = Omega, b, theta, W, v
         self.group = None if group is None else np.asarray(group, dtype=np.int32).copy()
 
+    @classmethod
+    def build_shared(cls, e, hyper, train, Y, omega, draws, rep):
+        """One training set for every path, rows Y (R, n) of right-hand sides: path q of the R * rep is conditioned on row
+        q // rep.  One weights call for all of them."""
+        Om, b, theta, eps = draws
+        W = train[0].clone()
+        return cls(hyper, Om, b, theta, W, weights(e, hyper, W, train[1], Om, b, theta, Y.repeat_interleave(rep, 0), eps, omega))
+
+    @classmethod
+    def build_per_group(cls, e, hyper, train, y, omega, draws, group):
+        """Every group its own training set: train[g] = (W, Linv), y[g] (n,) (lists, or paths.PerGroup); group host ints (P,),
+        the paths of group 0, then those of group 1, ... (np.repeat(np.arange(G), J)).  One weights call per group."""
+        Om, b, theta, eps = draws
+        ends = np.searchsorted(group, np.arange(group[-1] + 2))   # (group g's paths: ends[g] .. ends[g + 1] - 1)
+        Ws, vs = [], []
+        for g in range(len(ends) - 1):
+            (W, Linv), mine = train[g], slice(ends[g], ends[g + 1])
+            Ws.append(W)
+            vs.append(weights(e, hyper, W, Linv, Om, b, theta[mine], y[g], eps[mine], omega))
+        return cls(hyper, Om, b, theta, torch.stack(Ws), torch.cat(vs), group)
+
+    def _train(self, x):
+        """(W, group) as the device entries take them with x: (M, D) shared by every path, or (P, M, D)."""
+        if x.dim() == 3 and self.W.dim() == 2:
+            return self.W[None], None
+        return self.W, (self.group if x.dim() == 3 else None)
+
     def __call__(self, e, x):
         """The paths at x: (M, D) shared by every path, or (P, M, D).  Returns (P, M)."""
         kind, length, scale, _ = self.hyper
-        if x.dim() == 3 and self.W.dim() == 2:
-            W, group = self.W[None], None
-        else:
-            W, group = self.W, (self.group if x.dim() == 3 else None)
+        W, group = self._train(x)
         return e.pathfun_eval(kind, x, W, self.Omega, self.b, self.theta, self.v, length, scale, group=group)
 
     def value_and_grad(self, e, x):
         """The paths and their input gradients at x ((M, D) shared, or (P, M, D)): (P, M), bit for bit what __call__
         returns, and (P, M, D), d path p at row m / d column d of its own input."""
         kind, length, scale, _ = self.hyper
-        if x.dim() == 3 and self.W.dim() == 2:
-            W, group = self.W[None], None
-        else:
-            W, group = self.W, (self.group if x.dim() == 3 else None)
+        W, group = self._train(x)
         return e.pathfun_grad(kind, x, W, self.Omega, self.b, self.theta, self.v, length, scale, group=group)
 
     def noise_sd(self):
         return np.sqrt(self.hyper[2] * self.hyper[3])
+
+
+def _row_blocks(e, x, P, width):
+    """(m0, x[m0:m0 + step]) over the rows of x in order, contiguous blocks of step = _rows_per_call(e, P, width) rows."""
+    if len(x) == 0:
+        raise ValueError('sample_functions: x has no rows')
+    step = _rows_per_call(e, P, width)
+    for m0 in range(0, len(x), step):
+        yield m0, np.ascontiguousarray(x[m0:m0 + step])
+
+
+def _join(blocks):
+    """Per-block lists over layers of (P, rows, ...) arrays -> one list over layers, the blocks' rows in order."""
+    return [np.concatenate(bl, 1) for bl in zip(*blocks)]
 
 
 def _scatter_add(J, g, columns):
@@ -149,57 +198,24 @@ class PathFunctions:
             for k, nd in enumerate(layer):
                 if nd.type != 'gp':
                     continue
-                hyper = paths.hyper(nd)
-                st = emu._joint_stats(l, k)
-                n = len(nd.output)
+                hyper, st = paths.hyper(nd), emu._joint_stats(l, k)
                 D = (st['W'] if l == 0 else st['per'][0]['W']).shape[1]
-                Om, b = features(rng, nd.name, nd.length, D, F)
-                Om, b = e.tensor(Om), e.tensor(b)
-                theta = e.tensor(rng.standard_normal((S, J, F)).reshape(S * J, F))
-                eps = e.tensor(rng.standard_normal((S, J, n)).reshape(S * J, n))
+                draws = list(map(e.tensor, draw_node(rng, nd.name, nd.length, D, F, S, J, len(nd.output))))
                 omega = None if nd.rep is None else e.tensor(nd.W_diag)
                 if l == 0:
-                    W = st['W'].clone()
-                    v = weights(e, hyper, W, st['Linv'], Om, b, theta, st['Y'].repeat_interleave(J, 0), eps, omega)
-                    self.nodes[l, k] = NodePaths(hyper, Om, b, theta, W, v)
+                    self.nodes[l, k] = NodePaths.build_shared(e, hyper, (st['W'], st['Linv']), st['Y'], omega, draws, J)
                 else:
-                    Ws, vs = [], []
-                    for s in range(S):
-                        ps, mine = st['per'][s], slice(s * J, (s + 1) * J)
-                        Ws.append(ps['W'])
-                        vs.append(weights(e, hyper, ps['W'], ps['Linv'], Om, b, theta[mine], ps['y'], eps[mine], omega))
-                    self.nodes[l, k] = NodePaths(hyper, Om, b, theta, torch.stack(Ws), torch.cat(vs), np.repeat(np.arange(S), J))
+                    train = paths.PerGroup(lambda s: (st['per'][s]['W'], st['per'][s]['Linv']))
+                    y = paths.PerGroup(lambda s: st['per'][s]['y'])
+                    self.nodes[l, k] = NodePaths.build_per_group(e, hyper, train, y, omega, draws, np.repeat(np.arange(S), J))
 
     def __call__(self, x, full_layer=False, noise=False):
         paths.check_2d(x)
         e, P = self.engine, self.N * self.sample_size
         width = 4 * max(len(layer) for layer in self.layers) + 3 * max(nf.Omega.shape[1] for nf in self.nodes.values()) + 4
-        step, M = _rows_per_call(e, P, width), len(x)
-        if M == 0:
-            raise ValueError('sample_functions: x has no rows')
-        blocks = None
-        for m0 in range(0, M, step):
-            out = self._block(np.ascontiguousarray(x[m0:m0 + step]), noise)
-            blocks = [[a] for a in out] if blocks is None else [bl + [a] for bl, a in zip(blocks, out)]
-        out = [list(np.concatenate(bl, 1).transpose(2, 1, 0)) for bl in blocks]
+        out = _join(self._block(xb, noise=noise)[0] for _, xb in _row_blocks(e, x, P, width))
+        out = [list(a.transpose(2, 1, 0)) for a in out]
         return out if full_layer else out[-1]
-
-    def _block(self, x, noise):
-        e, P = self.engine, self.N * self.sample_size
-        xd = e.tensor(x)
-
-        def first(nd):
-            xin = pathwalk.cols(xd, nd.input_dim)
-            return xin if nd.connect is None else torch.cat((xin, pathwalk.cols(xd, nd.connect)), 1)
-
-        def draw(l, k, nodes, xin):
-            nf = self.nodes[l, k]
-            out = nf(e, xin)
-            if noise:
-                out += nf.noise_sd() * e.tensor(self.rng.standard_normal((P, len(x))))
-            return out
-        return [cur.cpu().numpy() for cur in pathwalk.walk(e, [self.layers] * self.N, self.sample_size, xd, None, first, draw)]
-
 
     def _check_differentiable(self):
         for layer in self.layers:
@@ -216,48 +232,43 @@ class PathFunctions:
         does not read get zero.  Raises ValueError for an emulator with a likelihood node or a Categorical top."""
         self._check_differentiable()
         paths.check_2d(x)
-        e, P = self.engine, self.N * self.sample_size
-        M, Dx = x.shape
-        if M == 0:
-            raise ValueError('sample_functions: x has no rows')
+        e, P, Dx = self.engine, self.N * self.sample_size, x.shape[1]
         K, D = max(len(layer) for layer in self.layers), max(nf.Omega.shape[1] for nf in self.nodes.values())
         # paths(x)'s doubles per row and path, a node's gradient twice (the kernel's and the slice multiplied), and Dx per node
         # for the Jacobians of two layers, one gathered operand and the node's own
         width = 4 * K + 3 * D + 4 + 2 * D + (3 * K + 2) * Dx
-        step = _rows_per_call(e, P, width)
-        vals = grads = None
-        for m0 in range(0, M, step):
-            v, g = self._block_grad(np.ascontiguousarray(x[m0:m0 + step]), full_layer)
-            vals = [[a] for a in v] if vals is None else [bl + [a] for bl, a in zip(vals, v)]
-            grads = [[a] for a in g] if grads is None else [bl + [a] for bl, a in zip(grads, g)]
-        vals = [list(np.concatenate(bl, 1).transpose(2, 1, 0)) for bl in vals]
-        grads = [list(np.concatenate(bl, 1).transpose(2, 1, 3, 0)) for bl in grads]
+        blocks = [self._block(xb, jacobians='all' if full_layer else 'last') for _, xb in _row_blocks(e, x, P, width)]
+        vals = [list(a.transpose(2, 1, 0)) for a in _join(v for v, _ in blocks)]
+        grads = [list(a.transpose(2, 1, 3, 0)) for a in _join(g for _, g in blocks)]
         return (vals, grads) if full_layer else (vals[-1], grads[-1])
 
     def grad(self, x, full_layer=False):
         """value_and_grad(x, full_layer)[1]."""
         return self.value_and_grad(x, full_layer)[1]
 
-    def _block_grad(self, x, full_layer):
-        """The walk of _block with every node's (P, M, D_node) gradient folded into the Jacobian of its layer with respect to
-        x, (P, M, K_layer, Dx), on the device.  First layer: the gradient scattered into the node's input_dim and connect
-        columns of x.  Deeper: J[p, m, :] = sum_k g[p, m, k] J_below[p, m, input_dim[k], :] plus the connect part scattered
-        into x's columns -- one fused multiply-add per element and k, in the order of k, so that a row's Jacobian does not
-        depend on the rows that share its block (a library contraction may pick another summation order at another size).
-        Returns (values, Jacobians): per layer (P, M, K) and, for the last layer or with full_layer every layer,
-        (P, M, K, Dx) host arrays."""
+    def _block(self, x, noise=False, jacobians=None):
+        """The walk at one block of rows: (values, Jacobians), per layer (P, M, K) host arrays and, with jacobians 'last' for
+        the last layer or 'all' for every layer, (P, M, K, Dx) ones.  Without jacobians the nodes are evaluated by
+        dgpamd_pathfun_eval and no Jacobian is allocated; noise adds every GP node's N(0, scale * nugget) term.
+        With them every node's (P, M, D_node) gradient is folded into the Jacobian of its layer with respect to x, on the
+        device.  First layer: the gradient scattered into the node's input_dim and connect columns of x.  Deeper:
+        J[p, m, :] = sum_k g[p, m, k] J_below[p, m, input_dim[k], :] plus the connect part scattered into x's columns -- one
+        fused multiply-add per element and k, in the order of k, so that a row's Jacobian does not depend on the rows that
+        share its block (a library contraction may pick another summation order at another size)."""
+        assert not (noise and jacobians), 'the noise term has no derivative'
         e, P = self.engine, self.N * self.sample_size
         xd = e.tensor(x)
         M, Dx = x.shape
         Js = {}
 
-        def first(nd):
-            xin = pathwalk.cols(xd, nd.input_dim)
-            return xin if nd.connect is None else torch.cat((xin, pathwalk.cols(xd, nd.connect)), 1)
-
         def draw(l, k, nodes, xin):
-            nd = nodes[0]
-            out, g = self.nodes[l, k].value_and_grad(e, xin)
+            nd, nf = nodes[0], self.nodes[l, k]
+            if jacobians is None:
+                out = nf(e, xin)
+                if noise:
+                    out += nf.noise_sd() * e.tensor(self.rng.standard_normal((P, M)))
+                return out
+            out, g = nf.value_and_grad(e, xin)
             if l not in Js:
                 Js.pop(l - 2, None)
                 Js[l] = e.zeros(P, M, len(self.layers[l]), Dx)
@@ -273,9 +284,10 @@ class PathFunctions:
             return out
 
         vals, jac, L = [], [], len(self.layers)
-        for l, cur in enumerate(pathwalk.walk(e, [self.layers] * self.N, self.sample_size, xd, None, first, draw)):
+        for l, cur in enumerate(pathwalk.walk(e, [self.layers] * self.N, self.sample_size, xd, None,
+                                              lambda nd: pathwalk.first(xd, nd), draw)):
             vals.append(cur.cpu().numpy())
-            if full_layer or l == L - 1:
+            if jacobians == 'all' or (jacobians == 'last' and l == L - 1):
                 jac.append(Js[l].cpu().numpy())
         return vals, jac
 
@@ -294,34 +306,20 @@ class GpPaths:
         J, F = int(sample_size), int(n_features)
         if J < 1 or F < 1:
             raise ValueError('sample_functions needs sample_size >= 1 and n_features >= 1')
-        if k._stats is None:
-            k.compute_stats()
-        st = k._stats
+        train = model._joint_train()
+        n, D = train[0].shape
+        draws = list(map(e.tensor, draw_node(np.random, k.name, k.length, D, F, 1, J, n)))
+        y = e.tensor(np.asarray(k.output, float).reshape(1, -1))
         omega = None if k.rep is None else e.tensor(k.W_diag)
-        if 'joint' not in st:
-            st['joint'] = paths.factor_inverse(e, k.name, st['W'], st['Wg'], omega, k.length, k.nugget[0], 'the gp model')
-        W = st['Wall'].clone()
-        n, D = W.shape
-        hyper = paths.hyper(k)
-        Om, b = features(np.random, k.name, k.length, D, F)
-        Om, b = e.tensor(Om), e.tensor(b)
-        theta = e.tensor(np.random.standard_normal((J, F)))
-        eps = e.tensor(np.random.standard_normal((J, n)))
-        y = e.tensor(np.asarray(k.output, float).reshape(-1))
-        self.engine, self.sample_size = e, J
+        self.engine, self.sample_size, self.columns = e, J, model._columns()
         self.input_dim, self.connect = np.array(k.input_dim), None if k.connect is None else np.array(k.connect)
-        self.node = NodePaths(hyper, Om, b, theta, W, weights(e, hyper, W, st['joint'], Om, b, theta, y, eps, omega))
+        self.node = NodePaths.build_shared(e, paths.hyper(k), train, y, omega, draws, J)
 
     def __call__(self, x, noise=False):
         paths.check_2d(x)
-        if len(x) == 0:
-            raise ValueError('sample_functions: x has no rows')
         e, J = self.engine, self.sample_size
-        xin = x[:, self.input_dim] if self.connect is None else np.concatenate((x[:, self.input_dim], x[:, self.connect]), 1)
-        step, out = _rows_per_call(e, J, 2 + xin.shape[1]), []
-        for m0 in range(0, len(x), step):
-            out.append(self.node(e, e.tensor(np.ascontiguousarray(xin[m0:m0 + step]))).cpu().numpy().T)
-        out = np.concatenate(out, 0)
+        xin = x[:, self.columns]
+        out = np.concatenate([self.node(e, e.tensor(xb)).cpu().numpy().T for _, xb in _row_blocks(e, xin, J, 2 + xin.shape[1])], 0)
         if noise:
             out = out + self.node.noise_sd() * np.random.standard_normal((J, len(x))).T
         return out
@@ -331,17 +329,13 @@ class GpPaths:
         gradients[m, d, j] = d draw j at row m / d x[m, d]; the node's gradient is added into its input_dim and connect
         columns of x, every other column is zero."""
         paths.check_2d(x)
-        if len(x) == 0:
-            raise ValueError('sample_functions: x has no rows')
         e, J = self.engine, self.sample_size
-        columns = list(self.input_dim) + ([] if self.connect is None else list(self.connect))
-        xin = x[:, columns]
-        M, Dx = x.shape
-        step, out, grad = _rows_per_call(e, J, 2 + 3 * xin.shape[1] + Dx), [], np.zeros((M, Dx, J))
-        for m0 in range(0, M, step):
-            f, g = self.node.value_and_grad(e, e.tensor(np.ascontiguousarray(xin[m0:m0 + step])))
+        xin, (M, Dx) = x[:, self.columns], x.shape
+        out, grad = [], np.zeros((M, Dx, J))
+        for m0, xb in _row_blocks(e, xin, J, 2 + 3 * xin.shape[1] + Dx):
+            f, g = self.node.value_and_grad(e, e.tensor(xb))
             out.append(f.cpu().numpy().T)
-            _scatter_add(grad[m0:m0 + step].transpose(0, 2, 1), g.cpu().numpy().transpose(1, 0, 2), columns)
+            _scatter_add(grad[m0:m0 + len(xb)].transpose(0, 2, 1), g.cpu().numpy().transpose(1, 0, 2), self.columns)
         return np.concatenate(out, 0), grad
 
     def grad(self, x):

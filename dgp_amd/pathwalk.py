@@ -21,6 +21,12 @@ def cols(t, idx):
     return t[..., torch.as_tensor(idx, device=t.device)]
 
 
+def first(xd, nd):
+    """The input of first-layer node nd at the rows xd (M, Dx) of the hierarchy's input: its input_dim, then its connect columns."""
+    xin = cols(xd, nd.input_dim)
+    return xin if nd.connect is None else torch.cat((xin, cols(xd, nd.connect)), 1)
+
+
 def per_path(t, P):
     """(M, D) shared by every path as (P, M, D); a (P, M, D) tensor as it is."""
     return t if t.dim() == 3 else t[None].expand(P, *t.shape)

@@ -440,3 +440,124 @@ def test_indefinite_training_matrix_raises(eng):
     emu = emulator([[nd]], N=1)
     with pytest.raises(np.linalg.LinAlgError, match='layer 1, node 1'):
         emu.sample_functions(sample_size=3, n_features=32)
+
+
+# ------------------------------------------------------------------------------------------------ row blocks, the builder
+@pytest.mark.parametrize('which', ['two-connect', 'three'])
+def test_emulator_row_blocks_change_no_bit_and_draw_noise_per_block(eng, which, monkeypatch):
+    """Blocks of 7 rows at M = 40: every GP layer of paths(x) bit for bit the unblocked call's; with noise=True every GP node
+    in walk order, block by block, takes one standard_normal((N * J, rows of the block)) from the emulator's generator: its
+    result is its paths at the (noisy) inputs it was given plus sqrt(scale nugget) times those normals."""
+    from dgp_amd import emulator, pathfun
+    X, model = _model(which)
+    emu = emulator(model.estimate(), N=2, seed=5)
+    S, J, F, M = 2, 3, 200, 40
+    x = np.random.default_rng(8).uniform(size=(M, X.shape[1]))
+    pf = emu.sample_functions(sample_size=J, n_features=F)
+    whole = pf(x, full_layer=True)
+    monkeypatch.setattr(pathfun, '_rows_per_call', lambda e, P, width: 7)
+    blocked = pf(x, full_layer=True)
+    assert len(whole) == len(blocked) == emu.n_layer
+    for a, c in zip(whole, blocked):
+        assert len(a) == len(c) and all(np.array_equal(u, w) and u.shape == (M, S * J) for u, w in zip(a, c))
+    state = copy.deepcopy(emu._sample_rng)
+    noisy = pf(x, full_layer=True, noise=True)
+    z = [[np.empty((M, S * J)) for _ in layer] for layer in emu.all_layer]
+    for m0 in range(0, M, 7):
+        for l, layer in enumerate(emu.all_layer):
+            for k in range(len(layer)):
+                z[l][k][m0:m0 + 7] = state.standard_normal((S * J, min(7, M - m0))).T
+    assert emu._sample_rng.bit_generator.state == state.bit_generator.state   # nothing else was drawn
+    e = pf.engine
+    for l, layer in enumerate(emu.all_layer):
+        for k, nd in enumerate(layer):
+            if l == 0:
+                values = whole[0][k]
+            else:   # the node's paths at the noisy outputs of the layer below: rows are independent, so these are the walk's bits
+                xin = np.stack([np.stack([noisy[l - 1][kk][:, p] for kk in nd.input_dim], 1) for p in range(S * J)])
+                if nd.connect is not None:
+                    xin = np.concatenate((xin, np.broadcast_to(x[:, nd.connect], (S * J, M, len(nd.connect)))), 2)
+                values = npy(pf.nodes[l, k](e, e.tensor(xin))).T
+            dev = np.abs(noisy[l][k] - (values + np.sqrt(nd.scale[0] * nd.nugget[0]) * z[l][k])).max()
+            print('%s layer %d node %d: max |noisy - (values + sd z)| = %.3g (1e-13)' % (which, l + 1, k + 1, dev))
+            assert dev <= 1e-13
+
+
+def _gp_case(case, rng, n=60, rep=15):
+    """test_gp_sample_functions_replays_numpy's models: n distinct rows, with 'replicates' the first `rep` twice and a
+    `connect` column."""
+    X = rng.uniform(size=(n, 3))
+    connect = None
+    if 'replicates' in case:
+        X, connect = np.concatenate((X, X[:rep])), np.array([2])
+    Y = (np.sin(3 * X[:, 0]) + X[:, 1] * X[:, 2] + 0.05 * rng.normal(size=len(X)))[:, None]
+    return _gp(case.split('-')[0], X, Y, connect=connect)
+
+
+@pytest.mark.parametrize('case', ['matern2.5-replicates-connect', 'sexp-plain'])
+def test_gp_row_blocks_change_no_bit_and_draw_noise_once(eng, case, monkeypatch):
+    """Blocks of 7 rows at M = 35: paths(x) and value_and_grad(x) bit for bit the unblocked calls'; noise=True still takes one
+    np.random.standard_normal((J, 35)) for all rows."""
+    from dgp_amd import pathfun
+    rng = np.random.default_rng(11)
+    m = _gp_case(case, rng)
+    J = 3
+    np.random.seed(21)
+    paths = m.sample_functions(sample_size=J, n_features=200)
+    x = rng.uniform(size=(35, 3))
+    whole, (vals, grad) = paths(x), paths.value_and_grad(x)
+    monkeypatch.setattr(pathfun, '_rows_per_call', lambda e, P, width: 7)
+    assert np.array_equal(paths(x), whole)
+    v2, g2 = paths.value_and_grad(x)
+    assert np.array_equal(v2, vals) and np.array_equal(g2, grad) and np.array_equal(vals, whole) and grad.shape == (35, 3, J)
+    s, eta = m.kernel.scale[0], m.kernel.nugget[0]
+    np.random.seed(5)
+    noisy = paths(x, noise=True)
+    np.random.seed(5)
+    assert np.allclose(noisy, whole + np.sqrt(s * eta) * np.random.standard_normal((J, 35)).T, rtol=0, atol=1e-14)
+
+
+def test_builders_take_the_dense_drawer_s_training_side(eng):
+    """A gp model's (Wall, L^-1), n = 30, D = 3, matern2.5 with replicates, and two rows of right-hand sides -- what
+    paths.Dense.draw_shared and draw_per_path are given -- through build_shared (rep = J) and build_per_group (PerGroup views,
+    group = repeat(arange(2), J)) with the same draws: each against the restatement at 35 rows.  The second group of
+    build_per_group has training inputs of its own (the model's, shifted) with their own L^-1."""
+    import pathfun_ref as R
+    from dgp_amd import pathfun
+    from dgp_amd import paths as dpaths
+    rng = np.random.default_rng(12)
+    m = _gp_case('matern2.5-replicates-connect', rng, n=30, rep=8)
+    k = m.kernel
+    e = k.engine
+    train = m._joint_train()
+    W, (n, D) = k._X(), k._X().shape
+    omega = e.tensor(k.W_diag)
+    assert (n, D) == (30, 3) and k.rep is not None and np.array_equal(npy(train[0]), W)
+    S, J, F, M = 2, 3, 200, 35
+    y = np.asarray(k.output, float).reshape(-1)
+    Y = np.stack((y, y + 0.5))
+    hyper = dpaths.hyper(k)
+    kind, length, s, eta = hyper
+    Omega, b, theta, eps = pathfun.draw_node(np.random.default_rng(3), kind, length, D, F, S, J, n)
+    draws = [e.tensor(a) for a in (Omega, b, theta, eps)]
+    W2 = W + 0.05 * rng.uniform(size=W.shape)
+    W2d = e.tensor(W2)
+    Linv2 = dpaths.factor_inverse(e, kind, W2d[:, :2].contiguous(), W2d[:, 2:].contiguous(), omega, length, eta, 'test')
+    trains = [train, (W2d, Linv2)]
+    Yd = e.tensor(Y)
+    shared = pathfun.NodePaths.build_shared(e, hyper, train, Yd, omega, draws, J)
+    grouped = pathfun.NodePaths.build_per_group(e, hyper, dpaths.PerGroup(lambda g: trains[g]), dpaths.PerGroup(lambda g: Yd[g]),
+                                                omega, draws, np.repeat(np.arange(S), J))
+    assert shared.W.shape == (n, D) and shared.group is None and shared.W.data_ptr() != train[0].data_ptr()
+    assert grouped.W.shape == (S, n, D) and np.array_equal(grouped.group, np.repeat(np.arange(S), J))
+    x = rng.uniform(size=(M, D))
+    v = R.weights(W, np.repeat(Y, J, 0), Omega, b, theta, eps, kind, length, s, eta, k.W_diag)
+    within(npy(shared(e, e.tensor(x))), R.evaluate(x, W, Omega, b, theta, v, kind, length, s),
+           R.tolerance(x, W, Omega, b, theta, v, kind, length, s), 'build_shared')
+    out = npy(grouped(e, e.tensor(np.broadcast_to(x, (S * J, M, D)).copy())))
+    for g, Wg in enumerate((W, W2)):
+        a = slice(g * J, (g + 1) * J)
+        vg = R.weights(Wg, Y[g], Omega, b, theta[a], eps[a], kind, length, s, eta, k.W_diag)
+        assert g == 0 or np.abs(vg - v[a]).max() > 1e-3 * np.abs(vg).max()   # (the second training set matters)
+        within(out[a], R.evaluate(x, Wg, Omega, b, theta[a], vg, kind, length, s),
+               R.tolerance(x, Wg, Omega, b, theta[a], vg, kind, length, s), 'build_per_group, group %d' % g)

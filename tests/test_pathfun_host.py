@@ -134,3 +134,54 @@ def test_restatement_alone_passes_the_distributional_check():
     zm, zc = R.dist_z(draws, mean, R.exact_cov(x, W, kind, length, s, eta) + noise, C + noise)
     print('restatement, seed %d: mean max z = %.3g (5); covariance max z = %.3g (6)' % (R.SEED_DIST, zm, zc))
     assert zm <= 5.0 and zc <= 6.0
+
+
+@pytest.mark.parametrize('nlen', ['one', 'D'])
+@pytest.mark.parametrize('kind', ['sexp', 'matern2.5'])
+def test_draw_node_consumes_the_generator_in_the_documented_order(kind, nlen):
+    """features (normals (F, D), chi^2_5 for matern2.5, phases), then standard_normal((S, J, F)), then standard_normal((S, J,
+    n)), and nothing else; with S = 1 on numpy's global generator, the order gp.sample_functions documents."""
+    from dgp_amd import pathfun
+    S, J, F, n, D = 2, 3, 5, 4, 3
+    length = np.array([0.8]) if nlen == 'one' else np.array([0.6, 1.1, 0.9])
+    g = np.broadcast_to(length, (D,))
+    rng, r = np.random.default_rng(31), np.random.default_rng(31)
+    Omega, b, theta, eps = pathfun.draw_node(rng, kind, length, D, F, S, J, n)
+    z = r.standard_normal((F, D))
+    want = np.sqrt(2.0) * z / g if kind == 'sexp' else z / np.sqrt(r.chisquare(5, (F, D)) / 5.0) / g
+    assert np.array_equal(Omega, want) and np.array_equal(b, r.uniform(0.0, 2.0 * np.pi, F))
+    assert theta.shape == (S * J, F) and np.array_equal(theta, r.standard_normal((S, J, F)).reshape(S * J, F))
+    assert eps.shape == (S * J, n) and np.array_equal(eps, r.standard_normal((S, J, n)).reshape(S * J, n))
+    assert rng.bit_generator.state == r.bit_generator.state
+    # an iterator: asked for Omega and b alone, it has drawn the features alone
+    it = pathfun.draw_node(rng, kind, length, D, F, S, J, n)
+    next(it), next(it)
+    pathfun.features(r, kind, length, D, F)
+    assert rng.bit_generator.state == r.bit_generator.state
+    np.random.seed(9)
+    got = list(pathfun.draw_node(np.random, kind, length, D, F, 1, J, n))
+    np.random.seed(9)
+    z = np.random.standard_normal((F, D))
+    want = np.sqrt(2.0) * z / g if kind == 'sexp' else z / np.sqrt(np.random.chisquare(5, (F, D)) / 5.0) / g
+    wb = np.random.uniform(0.0, 2.0 * np.pi, F)
+    wt, we = np.random.standard_normal((J, F)), np.random.standard_normal((J, n))
+    assert all(np.array_equal(a, c) for a, c in zip(got, (want, wb, wt, we)))
+    state = np.random.get_state()
+    np.random.seed(9)
+    list(pathfun.draw_node(np.random, kind, length, D, F, 1, J, n))
+    assert all(np.array_equal(a, c) for a, c in zip(state[1:], np.random.get_state()[1:]))
+
+
+@pytest.mark.parametrize('step', [1, 7, 40, 1000])
+def test_row_blocks_tile_the_rows_once_and_in_order(step, monkeypatch):
+    from dgp_amd import pathfun
+    monkeypatch.setattr(pathfun, '_rows_per_call', lambda e, P, width: step)
+    M = 40
+    x = np.arange(2 * M, dtype=float).reshape(M, 2)[:, ::-1]   # (not contiguous)
+    blocks = list(pathfun._row_blocks(None, x, 6, 10))
+    assert [m0 for m0, _ in blocks] == list(range(0, M, step))
+    assert all(xb.flags['C_CONTIGUOUS'] and 1 <= len(xb) <= step for _, xb in blocks)
+    assert np.array_equal(np.concatenate([xb for _, xb in blocks]), x)
+    with pytest.raises(ValueError, match='sample_functions: x has no rows'):
+        list(pathfun._row_blocks(None, x[:0], 6, 10))
+
