@@ -657,6 +657,17 @@ class Engine:
         self._chk(self._enter() or lib.dgpamd_debug_mathfn(self.h, self.MATHFN[fn], a.numel(), _dp(a), _dp(out0), _dp(out1)))
         return out0 if out1 is None else (out0, out1)
 
+    LINKFN = dict(i=0, jd=1, jd0=2, jsep=3, jsep0=4, erfcx=5)
+
+    def debug_linkfn(self, fn, args):
+        """Testing aid (dgpamd_debug_linkfn): one of the Matern-2.5 linked-GP factors of csrc/linkfun.hpp on every row
+        (X1, X2, m, v, l) of the float64 tensor `args` (count x 5), one lane per row.  fn: a key of Engine.LINKFN."""
+        args = args.contiguous()
+        assert args.dim() == 2 and args.shape[1] == 5
+        out = self.empty(args.shape[0])
+        self._chk(self._enter() or lib.dgpamd_debug_linkfn(self.h, self.LINKFN[fn], args.shape[0], _dp(args), _dp(out)))
+        return out
+
     def nn_query(self, q, x, m):
         M, D = q.shape
         n = x.shape[0]

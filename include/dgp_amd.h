@@ -479,6 +479,25 @@ int dgpamd_debug_poison_lds(dgpamd_ctx *ctx);
 #define DGPAMD_FN_COUNT 13
 int dgpamd_debug_mathfn(dgpamd_ctx *ctx, int fn, int64_t count, const double *a, double *out0, double *out1);
 
+/* Testing aid: the Matern-2.5 linked-GP factors of csrc/linkfun.hpp (the functions themselves, not copies), one lane per case.
+ * args: count x 5 doubles, rows of (X1, X2, m, v, l): the two points, and the mean, variance and lengthscale of Z ~ N(m, v);
+ * out: count doubles.  v == 0 gives the product of point correlations, as in every kernel that calls these functions.
+ *   DGPAMD_LINK_I       E[k(X1, Z)]                   matern_I_dim
+ *   DGPAMD_LINK_JD      E[k(X1, Z) k(X2, Z)]          matern_Jd
+ *   DGPAMD_LINK_JD0     E[k(X1, Z)^2]                 matern_Jd0
+ *   DGPAMD_LINK_JSEP    E[k(X1, Z) k(X2, Z)]          matern_role_S(min) . matern_role_T(max), combined as the pair kernels do
+ *   DGPAMD_LINK_JSEP0   E[k(X1, Z)^2]                 both roles on X1 (the diagonal of the separable kernels)
+ *   DGPAMD_LINK_ERFCX   exp(X1^2) erfc(X1)            the device erfcx those functions call
+ * An unknown fn, count <= 0 or a null pointer: DGPAMD_BAD_ARG. */
+#define DGPAMD_LINK_I 0
+#define DGPAMD_LINK_JD 1
+#define DGPAMD_LINK_JD0 2
+#define DGPAMD_LINK_JSEP 3
+#define DGPAMD_LINK_JSEP0 4
+#define DGPAMD_LINK_ERFCX 5
+#define DGPAMD_LINK_COUNT 6
+int dgpamd_debug_linkfn(dgpamd_ctx *ctx, int fn, int64_t count, const double *args, double *out);
+
 /* ---- a19-a21  Vecchia likelihoods and sampler ---------------------------------
  * vecchia_llik vecchia.py:164-180 ; vecchia_nllik :182-242 (raw sums; the host
  * finishes the scale_est / replicate branches) ; L_matrix :409-424 ;

@@ -85,3 +85,12 @@ def test_mathfn_numbers_match_header():
     header = {k.lower(): int(v) for k, v in re.findall(r'#define\s+DGPAMD_FN_([A-Z0-9_]+)\s+(\d+)', src)}
     count = header.pop('count')
     assert header == Engine.MATHFN and sorted(header.values()) == list(range(count))
+
+
+def test_linkfn_numbers_match_header():
+    """Engine.LINKFN (the keys of Engine.debug_linkfn) carries the DGPAMD_LINK_* numbers of the header, all of them."""
+    from dgp_amd.ops import Engine
+    src = open(os.path.join(ROOT, 'include', 'dgp_amd.h')).read()
+    header = {k.lower(): int(v) for k, v in re.findall(r'#define\s+DGPAMD_LINK_([A-Z0-9_]+)\s+(\d+)', src)}
+    count = header.pop('count')
+    assert header == Engine.LINKFN and sorted(header.values()) == list(range(count))

@@ -1,4 +1,7 @@
-"""Numerical check (numpy) of the separable S/T form of the Matern-2.5 J factor against the oracle's Jd."""
+"""Numerical check (numpy) of the separable S/T form of the Matern-2.5 J factor against the oracle's Jd.
+
+Kept for the derivation's sake: this is the form that followed the reference's expression term by term.  csrc/linkfun.hpp now follows
+the integral (its restatement and the checks against exact values: tests/linkfun_ref.py, tests/test_linkfun_host.py)."""
 import sys
 import numpy as np
 from scipy.special import erf
