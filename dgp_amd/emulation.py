@@ -29,7 +29,7 @@ import torch
 
 from .imputation import imputer, DrawStream
 from .ops import default_engine
-from . import dist as ddist
+from . import dist as ddist, paths, pathwalk
 
 
 class _LazyPer:
@@ -58,6 +58,31 @@ class _LazyPer:
         o._per_cache[ck] = item
         o._per_bytes += self.nbytes
         return item
+
+
+def _host(per_layer):
+    """_layer_moments' device pairs as numpy arrays."""
+    return [(a.cpu().numpy(), b.cpu().numpy()) for a, b in per_layer]
+
+
+def _mice_var(e, x, x_extra, nd, nugget_s):
+    """functions.mice_var (functions.py:244-256) on the device: scale / diag(R^-1) of the correlation matrix of
+    the candidate set (smoothing nugget max(nugget_s, nugget)).  pinvh in the reference; a Cholesky-based
+    inverse here (R is positive definite for any positive nugget)."""
+    Xin = x[:, nd.input_dim]
+    if nd.connect is not None:
+        Xin = np.concatenate((Xin, x_extra[:, nd.connect]), 1)
+    n = len(Xin)
+    Np = e.padded_dim(n)
+    A, Ainv = e.empty(Np, Np), e.empty(Np, Np)
+    e.kmatrix(nd.name, e.tensor(Xin), None, None, nd.length, max(nugget_s, nd.nugget[0]), out=A, full=False)
+    work = e.potrf_workspace(n, 1)
+    _, info = e.potrf(n, A, work=work)
+    e.potri(n, A, Ainv, 0, work)
+    if int(e.fetch(info)[0]):
+        raise np.linalg.LinAlgError('candidate-set correlation matrix is not positive definite')
+    d = torch.diagonal(Ainv)[:n]
+    return (float(nd.scale[0]) / d).cpu().numpy()
 
 
 class emulator:
@@ -182,20 +207,8 @@ class emulator:
                 Xg = None if peek(nd, 'global_input') is None else e.tensor(peek(nd, 'global_input'))
                 W = None if nd.rep is None else e.tensor(nd.W_diag)
 
-                def factor(Xl, Y, nd=nd, n=n, Np=Np, Xg=Xg, W=W):
-                    A = e.workspace(('emuA', n), Np * Np * 8)
-                    Ainv = e.empty(Np, Np)
-                    e.kmatrix(nd.name, Xl, None, Xg, nd.length, nd.nugget[0], W=W, out=A, full=False, Y=Y)
-                    work = e.potrf_workspace(n, 1)
-                    _, info = e.potrf(n, A, work=work)
-                    r = Y.shape[0]
-                    e.potri(n, A, Ainv, r, work)
-                    if int(info.cpu().numpy()[0]):   # not numerically PD: pseudo-inverse (kernel_class.py:749-751)
-                        K = e.kmatrix(nd.name, Xl, None, Xg, nd.length, nd.nugget[0], W=W, full=True)
-                        Ainv.zero_()
-                        Ainv[:n, :n] = e.pinvh(K)
-                        return Ainv, (Y @ Ainv[:n, :n]).contiguous()
-                    return Ainv, (-Ainv[n:n + r, :n]).contiguous()
+                def factor(Xl, Y, nd=nd, Xg=Xg, W=W):
+                    return paths.inverse_with_rhs(e, nd.name, Xl, Xg, W, nd.length, nd.nugget[0], Y, 'emuA')
 
                 if l == 0:
                     Xl = e.tensor(peek(nd, 'input'))
@@ -216,166 +229,76 @@ class emulator:
         self._per_cache = collections.OrderedDict()
         self._per_bytes = 0
 
-    def _layer_moments(self, x):
+    def _layer_moments(self, x, mode='dense', m=None):
         """Per layer the (mean, variance) of every node at the rows of x for every imputation held by this rank, as
-        device tensors (S, M, K) -- the layer walk of emulation.py:701-779 (dense mode)."""
-        if self._stats is None:
-            self._build_stats()
+        device tensors (S, M, K) -- the layer walk of emulation.py:701-779 (pathwalk.moments); the mode is what a GP node
+        does with its inputs: 'dense' the stored statistics; 'loo' the same with test row k leaving out training row k;
+        'vecchia' no stored statistics, the node's m nearest training points (kernel_class.py:603-619,647-664)."""
         e = self.engine
-        M, S = len(x), self.N
+        if mode != 'vecchia' and self._stats is None:
+            self._build_stats()
         xd = e.tensor(x)
-        per_layer = []
-        for l, layer in enumerate(self.all_layer):
-            if l == self.n_layer - 1 and self._cat() is not None:
-                idx = torch.as_tensor(np.asarray(self._cat().input_dim), device=xd.device)
-                per_layer.append((per_layer[-1][0][:, :, idx].contiguous(), per_layer[-1][1][:, :, idx].contiguous()))
-                continue
-            K = len(layer)
-            mean = e.empty(S, M, K)
-            var = e.empty(S, M, K)
-            for k, nd in enumerate(layer):
-                if nd.type != 'gp':   # likelihood node: closed-form moments of y from the feeding latents' (host protocol)
-                    pm, pv = (t.cpu().numpy() for t in per_layer[-1])
-                    for s in range(S):
-                        mk, vk = nd.prediction(m=pm[s][:, nd.input_dim], v=pv[s][:, nd.input_dim])
-                        mean[s, :, k] = e.tensor(mk)
-                        var[s, :, k] = e.tensor(vk)
-                    continue
-                st = self._stats[(l, k)]
-                z = None if nd.connect is None else xd[:, torch.as_tensor(nd.connect, device=xd.device)].contiguous()
-                if l == 0:
-                    xin = xd[:, torch.as_tensor(nd.input_dim, device=xd.device)]
-                    xin = (xin if z is None else torch.cat((xin, z), 1)).contiguous()
-                    mk, vk = e.gp_predict(nd.name, xin, st['Wall'], nd.length, st['Rinv'], st['ld'], st['ry'], nd.scale[0],
-                                          nd.nugget[0])
-                    mean[:, :, k] = mk
-                    var[:, :, k] = vk[None, :]
-                else:
-                    pm, pv = per_layer[-1]
-                    idx = torch.as_tensor(nd.input_dim, device=xd.device)
-                    for s in range(S):
-                        ps = st['per'][s]
-                        mk, vk = e.linkgp_predict(nd.name, pm[s][:, idx].contiguous(), pv[s][:, idx].contiguous(), z, ps['W'],
-                                                  ps.get('Wg', st['Wg']), nd.length, ps['Rinv'], st['ld'], ps['ry'], nd.scale[0],
-                                                  nd.nugget[0])
-                        mean[s, :, k] = mk
-                        var[s, :, k] = vk
-            per_layer.append((mean, var))
-        return per_layer
+        node = self._node_vecchia(m) if mode == 'vecchia' else lambda *a: self._node_dense(*a, loo=mode == 'loo')
+        return list(pathwalk.moments(e, [self.all_layer] * self.N, xd, None, None,
+                                     lambda nd: pathwalk.Inputs(pathwalk.first(xd, nd).contiguous(), None, None), node))
 
-    def _layer_moments_loo(self, x):
-        """Leave-one-out layer walk of a dense emulator (emulation.py:90-143 with vecch False: every node conditions
-        on all training points but its own -- test row k leaves out training row k at every layer, which is what
-        get_pred_nn's all-points shortcut (vecchia.py:23-26) followed by kernel_class.py:610-611,655-656 does).  Nothing is
-        refactorised: first-layer nodes use the block-inverse identities  mean = y_d - (R^-1 y)_d / (R^-1)_dd,
+    def _node_dense(self, l, k, nodes, inp, loo=False):
+        """pathwalk.moments' node predictor on the stored statistics.  loo: every node conditions on all training points
+        but its own (emulation.py:90-143 with vecch False: test row k leaves out training row k at every layer, which is
+        what get_pred_nn's all-points shortcut (vecchia.py:23-26) followed by kernel_class.py:610-611,655-656 does).  Nothing
+        is refactorised: first-layer nodes use the block-inverse identities  mean = y_d - (R^-1 y)_d / (R^-1)_dd,
         var = scale (1 / (R^-1)_dd + nugget (1 - W_d));  linked nodes go through dgpamd_linkgp_loo, which applies the
-        rank-one downdate of R^-1 inside the pair weights.  Returns device (S, M, K) pairs per layer."""
-        if self._stats is None:
-            self._build_stats()
-        e = self.engine
-        M, S = len(x), self.N
-        xd = e.tensor(x)
-        per_layer = []
-        for l, layer in enumerate(self.all_layer):
-            if l == self.n_layer - 1 and self._cat() is not None:
-                idx = torch.as_tensor(np.asarray(self._cat().input_dim), device=xd.device)
-                per_layer.append((per_layer[-1][0][:, :, idx].contiguous(), per_layer[-1][1][:, :, idx].contiguous()))
-                continue
-            K = len(layer)
-            mean, var = e.empty(S, M, K), e.empty(S, M, K)
-            for k, nd in enumerate(layer):
-                if nd.type != 'gp':
-                    pm, pv = (t.cpu().numpy() for t in per_layer[-1])
-                    for s in range(S):
-                        mk, vk = nd.prediction(m=pm[s][:, nd.input_dim], v=pv[s][:, nd.input_dim])
-                        mean[s, :, k], var[s, :, k] = e.tensor(mk), e.tensor(vk)
-                    continue
-                st = self._stats[(l, k)]
-                n = st['n']
-                z = None if nd.connect is None else xd[:, torch.as_tensor(nd.connect, device=xd.device)].contiguous()
-                if l == 0:
-                    xin = xd[:, torch.as_tensor(nd.input_dim, device=xd.device)]
-                    xin = (xin if z is None else torch.cat((xin, z), 1)).contiguous()
-                    if M != n or not torch.equal(st['Wall'], xin):
-                        raise Exception('loo: the rows of X must be the training input positions of the emulator, in order.')
-                    d = torch.arange(n, device=xd.device)
-                    rho = st['Rinv'][:n, :n].diagonal()[d]
-                    wd = 1.0 if nd.rep is None else e.tensor(nd.W_diag)[d]
-                    for s in range(S):
-                        y = e.tensor(self.latents[s][l][:, k] if l < self.n_layer - 1 else
-                                     np.asarray(nd.output, float).reshape(-1))
-                        mean[s, :, k] = y[d] - st['ry'][s][d] / rho
-                    var[:, :, k] = (nd.scale[0] * (1.0 / rho + nd.nugget[0] * (1.0 - wd)))[None, :]
-                else:
-                    pm, pv = per_layer[-1]
-                    idx = torch.as_tensor(nd.input_dim, device=xd.device)
-                    for s in range(S):
-                        ps = st['per'][s]
-                        ms, vs = pm[s][:, idx].contiguous(), pv[s][:, idx].contiguous()
-                        d = ps['pos'] if 'pos' in ps else torch.arange(n, device=xd.device, dtype=torch.int32)
-                        mk, vk = e.linkgp_predict(nd.name, ms, vs, z, ps['W'], ps.get('Wg', st['Wg']), nd.length, ps['Rinv'], st['ld'],
-                                                  ps['ry'], nd.scale[0], nd.nugget[0], drop=d)
-                        mean[s, :, k], var[s, :, k] = mk, vk
-            per_layer.append((mean, var))
-        return per_layer
+        rank-one downdate of R^-1 inside the pair weights."""
+        e, nd, st, S = self.engine, nodes[0], self._stats[(l, k)], self.N
+        n = st['n']
+        if l == 0 and loo:
+            if inp.m.shape[0] != n or not torch.equal(st['Wall'], inp.m):
+                raise Exception('loo: the rows of X must be the training input positions of the emulator, in order.')
+            rho = st['Rinv'][:n, :n].diagonal()
+            wd = 1.0 if nd.rep is None else e.tensor(nd.W_diag)
+            Y = e.tensor(np.stack([self._ys(s, l, k) for s in range(S)]))
+            return Y - st['ry'] / rho, nd.scale[0] * (1.0 / rho + nd.nugget[0] * (1.0 - wd))
+        if l == 0:
+            return e.gp_predict(nd.name, inp.m, st['Wall'], nd.length, st['Rinv'], st['ld'], st['ry'], nd.scale[0], nd.nugget[0])
+        mean, var = e.empty(S, inp.m.shape[1]), e.empty(S, inp.m.shape[1])
+        for s in range(S):
+            ps = st['per'][s]
+            drop = None if not loo else ps['pos'] if 'pos' in ps else torch.arange(n, device=e.device, dtype=torch.int32)
+            e.linkgp_predict(nd.name, inp.m[s], inp.v[s], inp.z, ps['W'], ps.get('Wg', st['Wg']), nd.length, ps['Rinv'], st['ld'],
+                             ps['ry'], nd.scale[0], nd.nugget[0], mean=mean[s], var=var[s], drop=drop)
+        return mean, var
 
-    def _layer_moments_vecchia(self, x, m):
-        """The same layer walk in Vecchia mode (no stored statistics; every node conditions on its pred_m nearest
-        neighbours, kernel_class.py:603-619,647-664).  Returns numpy (S, M, K) pairs per layer."""
-        M, S = len(x), self.N
-        layers = [[] for _ in self.all_layer]
-        # Conditioning sets are searched once per GROUP of nodes that must get the same ones: nodes of a layer with the same
-        # input columns and ONE shared lengthscale see the same points in the same (distance, index) order whatever the
-        # lengthscale's value (a uniform scaling; the reference itself shares orderings between such siblings in training,
-        # imputation.py:245-262) -- and in the first layer also across imputations, whose inputs are the same X.  At
-        # BASELINE configs[3] (8 + 1 nodes, 2 imputations) that is 3 searches instead of 18, which were 60 % of a large
-        # Vecchia prediction.  DGPAMD_NN_SHARE=0 searches per node like the reference (vecchia.py:20-40 per gp_prediction).
+    def _node_vecchia(self, m):
+        """pathwalk.moments' node predictor in Vecchia mode: every node conditions on its m nearest training points, the
+        imputation's own latents below the first layer.
+        Conditioning sets are searched once per GROUP of nodes that must get the same ones: nodes of a layer with the same
+        input columns and ONE shared lengthscale see the same points in the same (distance, index) order whatever the
+        lengthscale's value (a uniform scaling; the reference itself shares orderings between such siblings in training,
+        imputation.py:245-262) -- and in the first layer also across imputations, whose inputs are the same X.  At
+        BASELINE configs[3] (8 + 1 nodes, 2 imputations) that is 3 searches instead of 18, which were 60 % of a large
+        Vecchia prediction.  DGPAMD_NN_SHARE=0 searches per node like the reference (vecchia.py:20-40 per gp_prediction)."""
+        e, S = self.engine, self.N
         share = os.environ.get('DGPAMD_NN_SHARE', '1') != '0'
         nn_sets = {}
 
-        def hand_over(nd, l, s_, xq):
-            if not share or nd.loo_state:
-                return
-            iso = len(nd.length) == 1
-            key = (l, None if l == 0 else s_, tuple(np.asarray(nd.input_dim).tolist()),
-                   None if nd.connect is None else tuple(np.asarray(nd.connect).tolist()), 'iso' if iso else tuple(nd.length.tolist()), m)
-            if key not in nn_sets:
-                nn_sets[key] = nd._pred_nn(xq, nd._X())
-            nd._nn_given = nn_sets[key]
-
-        for s in range(S):
-            al = self._structure(s)
-            m_in = v_in = None
-            for l, layer in enumerate(al):
-                if l == self.n_layer - 1 and self._cat() is not None:
-                    idx = np.asarray(layer[0].input_dim)
-                    layers[l].append((m_in[:, idx].copy(), v_in[:, idx].copy()))
-                    continue
-                mo, vo = np.empty((M, len(layer))), np.empty((M, len(layer)))
-                for k, nd in enumerate(layer):
-                    if nd.type == 'gp':
-                        nd.engine = self.engine
-                        nd.pred_m = m
-                    if nd.type != 'gp':
-                        mo[:, k], vo[:, k] = nd.prediction(m=m_in[:, nd.input_dim], v=v_in[:, nd.input_dim])
-                        continue
-                    z = None if nd.connect is None else x[:, nd.connect]
-                    try:
-                        if l == 0:
-                            xq = x[:, nd.input_dim]
-                            hand_over(nd, l, s, xq if z is None else np.concatenate((xq, z), 1))
-                            mo[:, k], vo[:, k] = nd.gp_prediction(xq, z)
-                        else:
-                            mq = m_in[:, nd.input_dim]
-                            hand_over(nd, l, s, mq if z is None else np.concatenate((mq, z), 1))
-                            mo[:, k], vo[:, k] = nd.linkgp_prediction(mq, v_in[:, nd.input_dim], z)
-                    finally:
-                        # a set this call did not consume (a branch without a neighbour search, an exception on the way)
-                        # must not meet a later prediction with the same number of rows
-                        nd.__dict__.pop('_nn_given', None)
-                m_in, v_in = mo, vo
-                layers[l].append((mo, vo))
-        return [(np.stack([a for a, _ in L]), np.stack([b for _, b in L])) for L in layers]
+        def node(l, k, nodes, inp):
+            nd = nodes[0]
+            nd.pred_m = m
+            mean, var = e.empty(S, inp.m.shape[-2]), e.empty(S, inp.m.shape[-2])
+            for s in range(S):
+                train = (nd._X() if l == 0 else self._train_in(s, l, nd, True), self._ys(s, l, k))
+                ms = inp.m if l == 0 else inp.m[s]
+                nn = None
+                if share and not nd.loo_state:
+                    key = (l, None if l == 0 else s, tuple(np.asarray(nd.input_dim).tolist()),
+                           None if nd.connect is None else tuple(np.asarray(nd.connect).tolist()),
+                           'iso' if len(nd.length) == 1 else tuple(nd.length.tolist()))
+                    if key not in nn_sets:
+                        nn_sets[key] = nd._pred_nn(ms if inp.z is None else torch.cat((ms, inp.z), 1), train[0])
+                    nn = nn_sets[key]
+                mean[s], var[s] = nd.predict_at(ms, nn, train) if l == 0 else nd.predict_link(ms, inp.v[s], inp.z, nn, train)
+            return mean, var
+        return node
 
     def _cat(self):
         """The Categorical likelihood node of the final layer, or None.  For it the last layer's moments are those of
@@ -395,29 +318,37 @@ class emulator:
             raise Exception("method must be either 'mean_var' or 'sampling'.")
         if getattr(self, 'shard_points', False) and not getattr(self, '_in_points', False):
             return self._predict_points(x, method, full_layer, sample_size, m, aggregation)
-        if self.vecch:
-            return self._predict_vecchia(x, full_layer, m, aggregation, method, sample_size)
-        if self.shard and (method == 'sampling' or not aggregation):
+        if not self.vecch and self.shard and (method == 'sampling' or not aggregation):
             # (each rank holds its own imputations only: the per-imputation lists / draws would silently be partial)
             raise NotImplementedError("with the imputations sharded over ranks predict() returns aggregated moments only; "
                                       "use emulator(..., shard=False) or shard='points' for method='sampling' / aggregation=False")
-        e = self.engine
-        M, S = len(x), self.N
-        per_layer = self._layer_moments(x)
+        per_layer = self._layer_moments(x, self._mode(), m)
         if method == 'sampling':
-            return self._draw_samples([(mean.cpu().numpy(), var.cpu().numpy()) for mean, var in per_layer], sample_size,
-                                      full_layer)
-        cat = self._cat()
+            return self._draw_samples(_host(per_layer), sample_size, full_layer)
+        return self._aggregate(per_layer, full_layer, aggregation)
+
+    def _mode(self):
+        return 'vecchia' if self.vecch else 'dense'
+
+    def _host_moments(self, x, m):
+        """_layer_moments in the emulator's own mode as numpy arrays (metric, nllik)."""
+        return _host(self._layer_moments(x, self._mode(), m))
+
+    def _aggregate(self, per_layer, full_layer=False, aggregation=True):
+        """predict's result from the layers' moments: mu = mean_s mu_s, var = mean_s(mu_s^2 + v_s) - mu^2 over the
+        imputations (emulation.py:846-847; summed on the device, over all ranks under `shard`), of the last layer or with
+        full_layer of every layer; without either the last layer's per-imputation lists.  A Categorical top turns its
+        feeding latents' moments into class probabilities last."""
+        e, cat, S = self.engine, self._cat(), self.N
         if not aggregation and not full_layer:
-            mu_s, v_s = per_layer[-1]
-            mu_s, v_s = [t.cpu().numpy() for t in mu_s], [t.cpu().numpy() for t in v_s]
+            mu_s, v_s = (list(t.cpu().numpy()) for t in per_layer[-1])
             if cat is not None:
                 pr = [cat.prediction(a, b) for a, b in zip(mu_s, v_s)]
                 return [p[0] for p in pr], [p[1] for p in pr]
             return mu_s, v_s
         outs = []
         for mean, var in (per_layer if full_layer else per_layer[-1:]):
-            s1, s2 = e.zeros(M, mean.shape[2]), e.zeros(M, mean.shape[2])
+            s1, s2 = e.zeros(*mean.shape[1:]), e.zeros(*mean.shape[1:])
             for s in range(S):
                 e.moments_accumulate(mean[s].contiguous(), var[s].contiguous(), s1, s2)
             if self.shard:
@@ -468,7 +399,6 @@ class emulator:
         cat.sampling for a Categorical node).  Normals come from the emulator's sampling generator, layer by layer and
         node by node, one standard_normal((N, sample_size, M)) block per GP node.  At most 8192 rows of x; an imputation
         whose training correlation matrix is not positive definite raises numpy.linalg.LinAlgError."""
-        from . import paths
         self._need_dense_unsharded()
         paths.check_points(x)
         e, rng, drawer = self.engine, self._sample_rng, paths.Dense()
@@ -523,7 +453,7 @@ class emulator:
         path, with one standard_normal((N, sample_size, M)) block per GP node as sample_paths.  With m >= n + M - 1 this is
         sample_paths' dense joint.  A conditioning block that does not factor is retried with a jitter, then raises
         numpy.linalg.LinAlgError naming its layer, node and imputation."""
-        from . import paths, vpaths
+        from . import vpaths
         if self.shard or getattr(self, 'shard_points', False):
             raise NotImplementedError("sample_paths_vecchia with the imputations sharded over ranks would return partial "
                                       "draws; use emulator(..., shard=False)")
@@ -549,7 +479,6 @@ class emulator:
         """sample_paths' and sample_paths_vecchia's walk (pathwalk.walk over all_layer, the same structure for every
         imputation) and their container.  draw(l, k, nd, xin) -> (N*J, M) draws GP node k of layer l at xin, (M, D) in the
         first layer and (N*J, M, D) below it, and takes the node's normals from the generator."""
-        from . import pathwalk
         e = self.engine
         xd = e.tensor(x)
         walk = pathwalk.walk(e, [self.all_layer] * self.N, J, xd, None, lambda nd: pathwalk.first(xd, nd),
@@ -574,7 +503,6 @@ class emulator:
         training correlation matrix (not the Matern cell reordering of the linked predictor: a permuted L^-1 is not
         triangular).  First layer: one L^-1 shared by every imputation, the N imputations' outputs as rows Y; deeper
         layers: L^-1 and y per imputation, through _LazyPer under the same byte budget."""
-        from . import paths
         if self._stats is None:
             self._build_stats()
         key = ('joint', l, k)
@@ -613,11 +541,7 @@ class emulator:
         indices = np.asarray(indices).reshape(-1)
         if len(X0) != len(x):
             x = X0
-        if self.vecch:
-            per_layer = self._layer_moments_vecchia(x, m)
-        else:
-            per_layer = [(a.cpu().numpy(), b.cpu().numpy()) for a, b in self._layer_moments(x)]
-        pm, pv = per_layer[-2]
+        pm, pv = self._host_moments(x, m)[-2]
         lik = [ghdiag(self.all_layer[-1][0].pllik, pm[s][indices, :], pv[s][indices, :], y) for s in range(self.N)]
         nl = -np.log(np.mean(lik, axis=0)).flatten()
         return np.mean(nl), nl
@@ -639,41 +563,6 @@ class emulator:
         if full_layer:
             return [g(a) for a in mu], [g(a) for a in var]
         return g(mu), g(var)
-
-    def _predict_vecchia(self, x, full_layer, m, aggregation, method='mean_var', sample_size=50, per_layer=None):
-        """Vecchia mode: no stored statistics; every node conditions on its pred_m nearest neighbours
-        (kernel_class.py:603-619,647-664) with the imputation's own latents."""
-        M, S = len(x), self.N
-        if per_layer is None:
-            per_layer = self._layer_moments_vecchia(x, m)
-        mus, vs = list(per_layer[-1][0]), list(per_layer[-1][1])
-        if method == 'sampling':
-            return self._draw_samples(per_layer, sample_size, full_layer)
-        cat = self._cat()
-        if full_layer:
-            outm, outv = [], []
-            for mu_l, v_l in per_layer:
-                mbar = mu_l.mean(0)
-                outm.append(mbar)
-                outv.append((mu_l ** 2 + v_l).mean(0) - mbar ** 2)
-            if cat is not None:
-                outm[-1], outv[-1] = cat.prediction(outm[-1], outv[-1])
-            return outm, outv
-        if not aggregation:
-            if cat is not None:
-                pr = [cat.prediction(a, b) for a, b in zip(mus, vs)]
-                return [p[0] for p in pr], [p[1] for p in pr]
-            return mus, vs
-        e = self.engine
-        s1, s2 = e.zeros(*mus[0].shape), e.zeros(*mus[0].shape)
-        for a, b in zip(mus, vs):
-            e.moments_accumulate(e.tensor(a), e.tensor(b), s1, s2)
-        if self.shard:
-            ddist.allreduce_sum(s1, s2)
-        e.moments_finalize(self.N_total if self.shard else S, s1, s2)
-        if cat is not None:
-            return cat.prediction(s1.cpu().numpy(), s2.cpu().numpy())
-        return s1.cpu().numpy(), s2.cpu().numpy()
 
     def ppredict(self, x, method='mean_var', full_layer=False, sample_size=50, m=50, chunk_num=None, core_num=None):
         """emulation.py:578-629 split x over a process pool; test points and imputations already run in parallel on the
@@ -698,7 +587,7 @@ class emulator:
         its nearest training points with the nearest one (at the first layer the point itself) dropped
         (kernel_class.py:610-611,655-656) -- m of them for a Vecchia emulator, all other n-1 points for a dense one.
         The dense case does not run n factorisations of size n-1 as the reference does: it reuses the emulator's R^-1
-        through the rank-one downdate of `_layer_moments_loo`."""
+        through the rank-one downdate of `_node_dense(loo=True)`."""
         if method is None:
             method = 'mean_var'
         n_train = len(self.all_layer[0][0].input)
@@ -706,11 +595,11 @@ class emulator:
         if isrep:
             X, indices = np.unique(X, return_inverse=True, axis=0)
         if not self.vecch:
-            per_layer = [(a.cpu().numpy(), b.cpu().numpy()) for a, b in self._layer_moments_loo(X)]
-            res = self._predict_vecchia(X, False, m, True, method, sample_size, per_layer=per_layer)
+            per_layer = self._layer_moments(X, 'loo')
         else:
             with self.change_vecch_state():
-                res = self._predict_vecchia(X, False, m + 1, True, method, sample_size)
+                per_layer = self._layer_moments(X, 'vecchia', m + 1)
+        res = self._draw_samples(_host(per_layer), sample_size, False) if method == 'sampling' else self._aggregate(per_layer)
         if isrep:
             res = type(res)(item[np.asarray(indices).reshape(-1), :] for item in res)
         return res
@@ -743,24 +632,21 @@ class emulator:
             return self._vigf(x_cand, obj, m, score_only)
         # MICE (emulation.py:377-394): mean over imputations of log(predictive variance / smoothed variance of a GP whose
         # design is the candidate set itself, functions.mice_var :244-256)
-        if self.vecch:
-            per_layer = self._layer_moments_vecchia(x_cand, m)
-        else:
-            per_layer = [(a.cpu().numpy(), b.cpu().numpy()) for a, b in self._layer_moments(x_cand)]
+        per_layer = self._host_moments(x_cand, m)
         sigma2 = per_layer[L][1]
         pred_in = per_layer[L - 1][0] if L > 0 else None
         M, D, S = len(x_cand), len(self.all_layer[L]), self.N
         if lik and self.n_layer == 2:
             # one GP layer under a likelihood (emulation.py:366-375): its predictive variance does not depend on the
             # imputation; the ratio itself is the score
-            s_0 = np.stack([self._mice_var(x_cand, x_cand, nd, nugget_s) for nd in self.all_layer[0]], 1)
+            s_0 = np.stack([_mice_var(self.engine, x_cand, x_cand, nd, nugget_s) for nd in self.all_layer[0]], 1)
             avg = sigma2[0] / s_0
         else:
             mice = np.zeros((M, D))
             for i in range(S):
                 s_i = np.empty((M, D))
                 for k, nd in enumerate(self.all_layer[L]):
-                    s_i[:, k] = self._mice_var(x_cand if pred_in is None else pred_in[i], x_cand, nd, nugget_s)
+                    s_i[:, k] = _mice_var(self.engine, x_cand if pred_in is None else pred_in[i], x_cand, nd, nugget_s)
                 with np.errstate(divide='ignore'):
                     mice += np.log(sigma2[i] / s_i)
             avg = mice / S
@@ -788,10 +674,7 @@ class emulator:
             index = np.argmin(d2, axis=1)
         else:
             index = e.nn_query(e.tensor(x_cand), e.tensor(X), 1).cpu().numpy().reshape(-1)
-        if self.vecch:
-            mean, var = self._layer_moments_vecchia(x_cand, m)[L]
-        else:
-            mean, var = (t.cpu().numpy() for t in self._layer_moments(x_cand)[L])
+        mean, var = self._host_moments(x_cand, m)[L]
         if lik:    # under a likelihood the last GP layer's "outputs" are the imputation's own latents (emulation.py:498-524,567-570)
             Ytr = np.stack([self.latents[s_][L][index, :] for s_ in range(self.N)])                          # (S, M, D)
         else:
@@ -804,26 +687,6 @@ class emulator:
             return vigf
         idx = np.argmax(vigf, axis=0)
         return idx, vigf[idx, np.arange(vigf.shape[1])]
-
-    def _mice_var(self, x, x_extra, nd, nugget_s):
-        """functions.mice_var (functions.py:244-256) on the device: scale / diag(R^-1) of the correlation matrix of
-        the candidate set (smoothing nugget max(nugget_s, nugget)).  pinvh in the reference; a Cholesky-based
-        inverse here (R is positive definite for any positive nugget)."""
-        e = self.engine
-        Xin = x[:, nd.input_dim]
-        if nd.connect is not None:
-            Xin = np.concatenate((Xin, x_extra[:, nd.connect]), 1)
-        n = len(Xin)
-        Np = e.padded_dim(n)
-        A, Ainv = e.empty(Np, Np), e.empty(Np, Np)
-        e.kmatrix(nd.name, e.tensor(Xin), None, None, nd.length, max(nugget_s, nd.nugget[0]), out=A, full=False)
-        work = e.potrf_workspace(n, 1)
-        _, info = e.potrf(n, A, work=work)
-        e.potri(n, A, Ainv, 0, work)
-        if int(e.fetch(info)[0]):
-            raise np.linalg.LinAlgError('candidate-set correlation matrix is not positive definite')
-        d = torch.diagonal(Ainv)[:n]
-        return (float(nd.scale[0]) / d).cpu().numpy()
 
     def pmetric(self, x_cand, method='ALM', obj=None, nugget_s=1., m=50, score_only=False, chunk_num=None, core_num=None):
         """emulation.py:170-321 (`chunk_num` / `core_num` are accepted and unused)."""

@@ -127,10 +127,8 @@ class gp:
         if method == 'ALM' or method == 'MICE':
             _, s2 = self.predict(x=x_cand, m=m)
             if method == 'MICE':
-                from .emulation import emulator
-                e = emulator.__new__(emulator)
-                e.engine = self.kernel.engine
-                s2 = s2 / e._mice_var(x_cand, x_cand, self.kernel, nugget_s).reshape(-1, 1)
+                from .emulation import _mice_var
+                s2 = s2 / _mice_var(self.kernel.engine, x_cand, x_cand, self.kernel, nugget_s).reshape(-1, 1)
             score = s2
         elif method == 'VIGF':
             if self.indices is not None:

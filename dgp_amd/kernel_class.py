@@ -13,7 +13,10 @@ R^-1 / R^-1 y on the device and never materialises Psexp.
 """
 import numpy as np
 from numpy.linalg import LinAlgError
+import torch
+
 from .ops import raise_not_pd
+from .paths import inverse_with_rhs
 from scipy.optimize import minimize, Bounds
 
 from .ops import default_engine
@@ -622,21 +625,8 @@ class kernel(TrackedInputs):
         positive definite the pseudo-inverse takes over, as in the reference (:749-751)."""
         e, s = self.engine, self._stage()
         n = len(self.output)
-        Np = e.padded_dim(n)
-        A = e.workspace(('llikA', n), Np * Np * 8)
-        Ainv = e.empty(Np, Np)
-        e.kmatrix(self.name, s['Xl'], None, s['Xg'], self.length, self.nugget[0], W=s['W'], out=A, full=False, Y=s['y'])
-        work = e.potrf_workspace(n, 1)
-        _, info = e.potrf(n, A, work=work)
-        e.potri(n, A, Ainv, 1, work)
-        if int(info.cpu().numpy()[0]):
-            K = e.kmatrix(self.name, s['Xl'], None, s['Xg'], self.length, self.nugget[0], W=s['W'], full=True)
-            Ainv.zero_()
-            Ainv[:n, :n] = e.pinvh(K)
-            ry = e.gemv(Ainv[:n, :n], s['y'])
-        else:
-            ry = (-Ainv[n, :n]).contiguous()
-        self._stats = dict(Rinv=Ainv, ld=Np, ry=ry, W=e.tensor(self._input),
+        Ainv, ry = inverse_with_rhs(e, self.name, s['Xl'], s['Xg'], s['W'], self.length, self.nugget[0], s['y'][None, :], 'llikA')
+        self._stats = dict(Rinv=Ainv, ld=e.padded_dim(n), ry=ry[0].contiguous(), W=e.tensor(self._input),
                            Wg=None if self._global_input is None else e.tensor(self._global_input),
                            Wall=e.tensor(self._X()), n=n)
 
@@ -668,93 +658,80 @@ class kernel(TrackedInputs):
         return np.stack([Xl[:, d][:, None] + Xl[:, d][None, :] for d in range(Xl.shape[1])])
 
     def _pred_nn(self, x, w):
-        """Conditioning sets of the test rows (vecchia.get_pred_nn, vecchia.py:20-40): the pred_m nearest training
-        points, nearest first -- or, when pred_m covers all n of them, the reference's shortcut: row k = k, k+1, ...
-        cyclically, no search (so that the leave-one-out walk of a dense emulator drops training point k for test
-        row k, emulation.py:90-143)."""
+        """Conditioning sets of the test rows x (device) among the training rows w (host) (vecchia.get_pred_nn,
+        vecchia.py:20-40): the pred_m nearest training points, nearest first -- or, when pred_m covers all n of them, the
+        reference's shortcut: row k = k, k+1, ... cyclically, no search (so that the leave-one-out walk of a dense emulator
+        drops training point k for test row k, emulation.py:90-143)."""
         e = self.engine
         n = len(w)
-        given = self.__dict__.pop('_nn_given', None)   # (handed over by the emulator: a sibling's search, see _layer_moments_vecchia)
-        if given is not None and given.shape[0] == len(x) and given.shape[1] == min(self.pred_m, n) - (1 if self.loo_state else 0):
-            return given
         if self.pred_m >= n:
-            import torch
             NN = ((torch.arange(n, device=e.device)[None, :] + torch.arange(len(x), device=e.device)[:, None]) % n).contiguous()
         else:
-            NN = e.nn_query(e.tensor(x / self.length), e.tensor(w / self.length), self.pred_m)
+            NN = e.nn_query((x / e.tensor(self.length)).contiguous(), e.tensor(w / self.length), self.pred_m)
         if self.loo_state:
             NN = NN[:, 1:].contiguous()
         return NN
 
+    def _vecchia_train(self, train):
+        """The training side of a Vecchia prediction: inputs with global columns (host), outputs and nugget weights
+        (device).  train: (inputs, outputs) to use instead of the node's own (an imputation of the emulator), or None."""
+        e = self.engine
+        X, y = (self._X(), self.output) if train is None else train
+        return X, e.tensor(np.asarray(y, float).reshape(-1)), e.tensor(np.ones(len(y)) if self.rep is None else self.W_diag)
+
+    def predict_at(self, x, nn=None, train=None):
+        """Mean and variance (M,) at the deterministic inputs x (M, D; global columns appended), device tensors in and out.
+        Vecchia mode: nn the rows' conditioning sets if the caller has them (_pred_nn's of a node that must get the same),
+        train as _vecchia_train's."""
+        e = self.engine
+        if self.vecch:
+            X, y, omega = self._vecchia_train(train)
+            return e.vecchia_gp(self.name, x, e.tensor(X), self._pred_nn(x, X) if nn is None else nn, y, self.scale[0],
+                                self.length, self.nugget[0], omega)
+        st = self._stats
+        return e.gp_predict(self.name, x, st['Wall'], self.length, st['Rinv'], st['ld'], st['ry'], self.scale[0], self.nugget[0])
+
+    def predict_link(self, m, v, z=None, nn=None, train=None):
+        """Mean and variance (M,) at Gaussian inputs N(m, v) (M, Dg) beside deterministic global columns z (M, Dz) or None,
+        device tensors in and out.  The Dg Gaussian columns are the node's local ones, followed by the leading global ones
+        when those are uncertain themselves (outputs of feeding emulators, kernel_class.py:672-733): the width of m says how
+        many, the training inputs are split at the same column.  nn, train as predict_at's."""
+        e, Dg = self.engine, m.shape[1]
+        if self.vecch:
+            X, y, omega = self._vecchia_train(train)
+            if nn is None:
+                nn = self._pred_nn(m if z is None else torch.cat((m, z), 1), X)
+            return e.vecchia_linkgp(self.name, m, v, z, e.tensor(X[:, :Dg]), None if z is None else e.tensor(X[:, Dg:]), nn, y,
+                                    self.scale[0], self.length, self.nugget[0], omega)
+        st = self._stats
+        link = st.setdefault('link', {})   # (Matern: the training points grouped by cells of the Gaussian columns, built once per width)
+        if Dg not in link:
+            X = self._X()
+            Wg = e.tensor(X[:, Dg:]) if X.shape[1] > Dg else None
+            cells = e.linkgp_cells(self.name, np.ascontiguousarray(X[:, :Dg]), Wg, st['Rinv'], st['ry'])
+            link[Dg] = cells if cells is not None else dict(W=e.tensor(X[:, :Dg]), Wg=Wg, Rinv=st['Rinv'], ry=st['ry'])
+        c = link[Dg]
+        return e.linkgp_predict(self.name, m, v, z, c['W'], c['Wg'], self.length, c['Rinv'], st['ld'], c['ry'], self.scale[0],
+                                self.nugget[0])
+
+    # The reference's signatures, numpy in and out, over the two cores.
     def gp_prediction(self, x, z):
         """Mean/variance at deterministic inputs (kernel_class.py:587-625)."""
-        e = self.engine
-        xa = x if z is None else np.concatenate((x, z), 1)
-        if self.vecch:
-            w = self._X()
-            nd = np.ones(len(self.output)) if self.rep is None else self.W_diag
-            m, v = e.vecchia_gp(self.name, e.tensor(xa), e.tensor(w), self._pred_nn(xa, w),
-                                e.tensor(np.asarray(self.output, float).reshape(-1)), self.scale[0], self.length,
-                                self.nugget[0], e.tensor(nd))
-        else:
-            st = self._stats
-            m, v = e.gp_predict(self.name, e.tensor(xa), st['Wall'], self.length, st['Rinv'], st['ld'], st['ry'],
-                                self.scale[0], self.nugget[0])
-        return m.cpu().numpy(), v.cpu().numpy()
+        return _numpy_pair(self.predict_at(self.engine.tensor(x if z is None else np.concatenate((x, z), 1))))
 
     def linkgp_prediction(self, m, v, z):
         """Mean/variance at Gaussian-distributed inputs (kernel_class.py:627-670)."""
         e = self.engine
-        zt = None if z is None else e.tensor(z)
-        if self.vecch:
-            x = m if z is None else np.concatenate((m, z), 1)
-            w = self._X()
-            nd = np.ones(len(self.output)) if self.rep is None else self.W_diag
-            mo, vo = e.vecchia_linkgp(self.name, e.tensor(m), e.tensor(v), zt, e.tensor(self._input),
-                                      None if self._global_input is None else e.tensor(self._global_input),
-                                      self._pred_nn(x, w), e.tensor(np.asarray(self.output, float).reshape(-1)),
-                                      self.scale[0], self.length, self.nugget[0], e.tensor(nd))
-        else:
-            st = self._link_stats()
-            mo, vo = e.linkgp_predict(self.name, e.tensor(m), e.tensor(v), zt, st['W'], st['Wg'], self.length, st['Rinv'],
-                                      st['ld'], st['ry'], self.scale[0], self.nugget[0])
-        return mo.cpu().numpy(), vo.cpu().numpy()
-
-    def _link_stats(self):
-        """compute_stats' arrays as the linked predictor takes them: for a Matern-2.5 node a copy with the training points
-        grouped by cells of the local inputs (Engine.linkgp_cells; built at the first linked prediction, dropped with the
-        statistics), else the statistics themselves."""
-        st = self._stats
-        if 'link' not in st:
-            cells = self.engine.linkgp_cells(self.name, self._input, st['Wg'], st['Rinv'], st['ry'])
-            st['link'] = st if cells is None else dict(cells, ld=st['ld'])
-        return st['link']
+        return _numpy_pair(self.predict_link(e.tensor(m), e.tensor(v), None if z is None else e.tensor(z)))
 
     def linkgp_prediction_full(self, m, v, m_z, v_z, z):
         """Linked prediction when part of the node's GLOBAL input is itself uncertain (outputs of feeding
         emulators): those columns join the Gaussian inputs, the rest stays deterministic (kernel_class.py:672-733).
         No R2sexp/Psexp bookkeeping is needed here -- the device kernel never uses them."""
         e = self.engine
-        nz = m_z.shape[1]
-        mm, vv = np.concatenate((m, m_z), axis=1), np.concatenate((v, v_z), axis=1)
-        W = np.concatenate((self._input, self._global_input[:, :nz]), axis=1)
-        Wg = self._global_input[:, nz:]
-        zt = None if z is None else e.tensor(z)
-        Wgt = None if z is None else e.tensor(Wg)
-        if self.vecch:
-            x = mm if z is None else np.concatenate((mm, z), 1)
-            w = self._X()
-            nd = np.ones(len(self.output)) if self.rep is None else self.W_diag
-            mo, vo = e.vecchia_linkgp(self.name, e.tensor(mm), e.tensor(vv), zt, e.tensor(W), Wgt, self._pred_nn(x, w),
-                                      e.tensor(np.asarray(self.output, float).reshape(-1)), self.scale[0], self.length,
-                                      self.nugget[0], e.tensor(nd))
-        else:
-            st = self._stats
-            hit = st.get('link_full')   # (Matern: the training points grouped by cells of the widened local input, built once)
-            if hit is None or hit[0] != nz:
-                cells = e.linkgp_cells(self.name, W, Wgt, st['Rinv'], st['ry'])
-                hit = st['link_full'] = (nz, cells if cells is not None else dict(W=e.tensor(W), Wg=Wgt, Rinv=st['Rinv'], ry=st['ry']))
-            c = hit[1]
-            mo, vo = e.linkgp_predict(self.name, e.tensor(mm), e.tensor(vv), zt, c['W'], c['Wg'], self.length, c['Rinv'],
-                                      st['ld'], c['ry'], self.scale[0], self.nugget[0])
-        return mo.cpu().numpy(), vo.cpu().numpy()
+        return _numpy_pair(self.predict_link(e.tensor(np.concatenate((m, m_z), axis=1)), e.tensor(np.concatenate((v, v_z), axis=1)),
+                                       None if z is None else e.tensor(z)))
+
+
+def _numpy_pair(pair):
+    return tuple(t.cpu().numpy() for t in pair)

@@ -1,8 +1,8 @@
 """Linked (D)GP emulation of a feed-forward system of emulators -- mirror of dgpsi.container / dgpsi.lgp
 (linkgp.py:12-608), mean/variance prediction; joint sample paths of the system (lgp.sample_paths with the drawer
 paths.Dense, lgp.sample_paths_vecchia with vpaths.Vecchia; DGP emulators walked by pathwalk.walk).  Pure orchestration
-over kernel.gp_prediction / linkgp_prediction / linkgp_prediction_full; aggregation over imputations as
-emulation.py:846-847."""
+over kernel.gp_prediction / linkgp_prediction (GP emulators) and pathwalk.moments over kernel.predict_at / predict_link
+(DGP emulators); aggregation over imputations as emulation.py:846-847."""
 import collections
 import contextlib
 import copy
@@ -199,37 +199,29 @@ class lgp:
     def dgp_pred(x, m, v, z, structure, pred_m):
         """Layer walk through a DGP emulator whose input is deterministic (x) or Gaussian (m, v [+ external z])
         (linkgp.py:517-608, GP nodes).  Returns (mean, var) of the layer before last and of the last layer."""
-        M = len(m) if x is None else len(x)
-        L = len(structure)
-        internal, external = structure[0][0].input_dim, structure[0][0].connect
-        mean_in = var_in = None
-        for l, layer in enumerate(structure):
-            mo, vo = np.empty((M, len(layer))), np.empty((M, len(layer)))
-            for k, nd in enumerate(layer):
-                if nd.type != 'gp':   # likelihood node on top of the emulator (linkgp.py:574-576)
-                    mo[:, k], vo[:, k] = nd.prediction(m=mean_in[:, nd.input_dim], v=var_in[:, nd.input_dim])
-                    continue
-                nd.pred_m = pred_m
-                _ensure_stats(nd)
-                if l == 0:
-                    mo[:, k], vo[:, k] = nd.linkgp_prediction(m=m, v=v, z=z) if x is None else nd.gp_prediction(x=x, z=z)
-                    continue
-                mk, vk = mean_in[:, nd.input_dim], var_in[:, nd.input_dim]
-                if nd.connect is None:
-                    mo[:, k], vo[:, k] = nd.linkgp_prediction(m=mk, v=vk, z=None)
-                elif x is not None:
-                    mo[:, k], vo[:, k] = nd.linkgp_prediction(m=mk, v=vk, z=x[:, nd.connect])
-                else:
-                    # the node's global inputs are themselves uncertain (outputs of feeding emulators) and/or external
-                    i1, i2 = pathwalk.connect_split(nd.connect, l == L - 1, m.shape[1], internal, external)
-                    if i1.size == 0:
-                        mo[:, k], vo[:, k] = nd.linkgp_prediction(m=mk, v=vk, z=z[:, i2])
-                    else:
-                        mo[:, k], vo[:, k] = nd.linkgp_prediction_full(m=mk, v=vk, m_z=m[:, i1], v_z=v[:, i1],
-                                                                        z=None if i2.size == 0 else z[:, i2])
-            if l < L - 1:
-                mean_in, var_in = mo, vo
-        return mean_in, var_in, mo, vo
+        if pathwalk.is_categorical(structure[-1]):   # (the walk would hand back the feeding latents' moments)
+            raise NotImplementedError('lgp: a DGP emulator with a Categorical likelihood on top cannot feed or end a linked system')
+        e = structure[0][0].engine
+        t = lambda a: None if a is None else e.tensor(np.asarray(a, float))
+        if x is not None:   # (the first layer takes every column of x and z, and of m and z)
+            m, first = x, pathwalk.Inputs(t(x if z is None else np.concatenate((x, z), 1)), None, None)
+        else:
+            first = pathwalk.Inputs(t(m), t(v), t(z))
+
+        def node(il, j, nodes, inp):
+            nd = nodes[0]
+            nd.pred_m = pred_m
+            _ensure_stats(nd)
+            if inp.v is None:
+                mk, vk = nd.predict_at(inp.m)
+            elif il == 0:
+                mk, vk = nd.predict_link(inp.m, inp.v, inp.z)
+            else:   # (its global inputs may themselves be uncertain -- outputs of feeding emulators -- and / or external)
+                mk, vk = nd.predict_link(inp.m[0], inp.v[0], inp.z)
+            return mk[None], vk[None]
+        out = [(a[0].cpu().numpy(), b[0].cpu().numpy())
+               for a, b in pathwalk.moments(e, [structure], t(m), first.v, first.z, lambda nd: first, node)]
+        return out[-2] + out[-1]
 
     def _emulate(self, model, x, m, v, z, pred_m, before=False):
         if model.type == 'gp':

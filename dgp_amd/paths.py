@@ -71,6 +71,27 @@ def factor_inverse(e, kind, Xl, Xg, W, length, nugget, where):
     return A
 
 
+def inverse_with_rhs(e, kind, Xl, Xg, W, length, nugget, Y, key):
+    """(R^-1, R^-1 Y) of R = K(W, W) + nugget diag(W_diag) for prediction: R^-1 a padded (Np x Np) device buffer, valid
+    [:n, :n]; Y (r, n) right-hand sides that ride along the one factorisation, R^-1 Y (r, n).  When R is not numerically
+    positive definite the pseudo-inverse takes over, as in the reference (kernel_class.py:749-751).  key names the cached
+    workspace that holds the factor."""
+    n, r = Xl.shape[0], Y.shape[0]
+    Np = e.padded_dim(n)
+    A = e.workspace((key, n), Np * Np * 8)
+    Ainv = e.empty(Np, Np)
+    e.kmatrix(kind, Xl, None, Xg, length, nugget, W=W, out=A, full=False, Y=Y)
+    work = e.potrf_workspace(n, 1)
+    _, info = e.potrf(n, A, work=work)
+    e.potri(n, A, Ainv, r, work)
+    if int(info.cpu().numpy()[0]):
+        K = e.kmatrix(kind, Xl, None, Xg, length, nugget, W=W, full=True)
+        Ainv.zero_()
+        Ainv[:n, :n] = e.pinvh(K)
+        return Ainv, (Y @ Ainv[:n, :n]).contiguous()
+    return Ainv, (-Ainv[n:n + r, :n]).contiguous()
+
+
 def _chunk(e, n, M, r, c):
     """Items per dgpamd_joint_cov / dgpamd_potrf call: <= 64 and within half of the free device memory."""
     Mp = e.padded_dim(M)

@@ -173,7 +173,7 @@ def test_emulator_loo_dense_downdate_equals_refit(eng, name):
     for nd in gps:
         nd.loo_state, nd.vecch = True, True
     try:
-        mu_ref, var_ref = emu._predict_vecchia(X, False, n, True)
+        mu_ref, var_ref = emu._aggregate(emu._layer_moments(X, 'vecchia', n))
     finally:
         for nd in gps:
             nd.loo_state, nd.vecch = False, False
@@ -1144,7 +1144,7 @@ def test_emulator_loo_under_a_likelihood_layer(eng, lik):
     for nd in gps:
         nd.loo_state, nd.vecch = True, True
     try:
-        mu_ref, var_ref = emu._predict_vecchia(X, False, n, True)
+        mu_ref, var_ref = emu._aggregate(emu._layer_moments(X, 'vecchia', n))
     finally:
         for nd in gps:
             nd.loo_state, nd.vecch = False, False
@@ -1357,16 +1357,14 @@ def test_mice_var_ghdiag_nllik_match_reference(eng, golden):
     from the reference (g22, g23): the smoothed candidate-set variance behind metric('MICE'), the Gauss-Hermite predictive
     likelihood, and the whole negative predicted log-likelihood of a Poisson-likelihood DGP from the reference's imputations."""
     from dgp_amd import kernel, Poisson, Hetero
-    from dgp_amd.emulation import emulator
+    from dgp_amd.emulation import emulator, _mice_var
     from dgp_amd.likelihood_class import ghdiag
     g = golden('g22_mice_ghdiag')
-    emu = emulator.__new__(emulator)
-    emu.engine = eng
     for i in range(2):
         glob = bool(g['m%d_glob' % i])
         nd = kernel(length=g['m%d_length' % i].copy(), scale=1.7, nugget=1e-6, name=str(g['m%d_name' % i]), input_dim=np.arange(3),
                     connect=np.arange(2) if glob else None, engine=eng)
-        s2 = emu._mice_var(g['m%d_x' % i], g['m%d_xe' % i], nd, 1e-3)
+        s2 = _mice_var(eng, g['m%d_x' % i], g['m%d_xe' % i], nd, 1e-3)
         close(s2, g['m%d_sigma2' % i].ravel(), rtol=1e-8)
     close(ghdiag(Poisson(input_dim=np.array([0])).pllik, g['gh_mu'], g['gh_var'], g['gh_y']), g['gh_poisson'], rtol=1e-12)
     close(ghdiag(Hetero(input_dim=np.array([0, 1])).pllik, g['gh_mu2'], g['gh_var2'], g['gh_y2']), g['gh_hetero'], rtol=1e-12)

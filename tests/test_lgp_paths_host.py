@@ -42,3 +42,26 @@ def test_malformed_input_raises_like_predict(method):
         sysm.all_layer[1][0].local_input_idx = [np.array([0]), None]
         with pytest.raises(Exception, match='length of 1'):
             f([np.zeros((5, 2)), [None]])
+
+
+def test_connect_cols_places_a_deeper_node_s_global_columns():
+    """pathwalk.connect_cols, the input assembly that pathwalk.walk and pathwalk.moments share, against connect_split's cases
+    (linkgp.py:538-560): a deterministic input is indexed by `connect` as it stands; a Gaussian one of D = 3 columns with
+    external columns behind it splits a middle layer's `connect` at D, and matches the last layer's against the first
+    layer's input_dim / connect."""
+    from types import SimpleNamespace
+    from dgp_amd.pathwalk import connect_cols, connect_split
+    node = lambda c: SimpleNamespace(connect=None if c is None else np.array(c))
+    internal, external = np.array([0, 2, 1]), np.array([4, 3])
+    head, alone = SimpleNamespace(input_dim=internal, connect=external), SimpleNamespace(input_dim=internal, connect=None)
+    same = lambda got, want: all(np.array_equal(a, np.asarray(b, dtype=int)) for a, b in zip(got, want)) and len(got) == 2
+    for last in (False, True):
+        for shared in (False, True):
+            assert same(connect_cols(node(None), last, shared, 3, head), ([], []))
+        assert same(connect_cols(node([4, 1]), last, True, 3, head), ([4, 1], []))
+    assert same(connect_cols(node([1, 3, 4]), False, False, 3, head), ([1], [0, 1]))
+    assert same(connect_cols(node([0, 1]), False, False, 3, alone), ([0, 1], []))
+    assert same(connect_cols(node([2, 3]), True, False, 3, head), ([1], [1]))
+    assert same(connect_cols(node([1, 0]), True, False, 3, alone), ([2, 0], []))
+    for c, last in (([1, 3, 4], False), ([2, 3], True)):
+        assert same(connect_cols(node(c), last, False, 3, head), connect_split(np.array(c), last, 3, internal, external))

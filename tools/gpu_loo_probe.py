@@ -22,7 +22,7 @@ for rep in range(int(os.environ.get('REPS', '4'))):
     for nd in gps:
         nd.loo_state, nd.vecch = True, True
     try:
-        mu_ref, var_ref = emu._predict_vecchia(X, False, n, True)
+        mu_ref, var_ref = emu._aggregate(emu._layer_moments(X, 'vecchia', n))
     finally:
         for nd in gps:
             nd.loo_state, nd.vecch = False, False
