@@ -204,6 +204,89 @@ def speculative_angles(theta, lo, hi, us):
     return th, br
 
 
+def _queue_per(b0, bn, qmax):
+    """Uniforms one queued update can take from a window at most: threshold and first angle, the shrinks inside the first and
+    the later batches, the closing shrink of the last one -- and the one of an open update the window may begin with."""
+    return 2 + (b0 - 1) + (qmax - 1) * bn + 2
+
+
+def _resume_args(st):
+    """one_sample_block's `resume` from a fetched queue state: the open update's threshold, angle, bracket, pending shrink."""
+    return dict(log_y=float(st['log_y']), theta=float(st['theta']), lo=float(st['lo']), hi=float(st['hi']), pending=bool(st['pending']))
+
+
+def run_queue_windows(ops, plans, batches, draws, stats, ll_cache, args_of, finish, resume_on_device, first_queued=None):
+    """The window loop of the device queue: peek the uniforms the remaining operations can need, put the device state in
+    place, queue the updates, fetch ONCE, book what the window consumed, act on its status -- until every operation is done.
+    ops: [(sweep, hidden layer)]; plans / batches: {layer: queue plan / (first batch, later batches, batches per update)};
+    args_of(j, lead) -> (F, NU, scales) of the queue call that starts at operation j (its prior work is queued in there: a
+    factorisation notes its info word in lead's state); finish(j, st): the host loop finishes the open operation j.
+    One plan (one hidden layer): ONE queue call takes all remaining operations, the log-likelihood is carried in
+    ll_cache[layer] from window to window and beyond; several plans: one call per operation, each computing its own, all on
+    the lead's state and uniforms.  resume_on_device: the next window continues an open update (status 3: out of queued
+    batches, 1: of uploaded uniforms) instead of finish().  Needs no device: the plans may be stand-ins with queue, fetch,
+    reset_state, resume_state, upload_uniforms and share_with."""
+    one = len(plans) == 1
+    per = max(_queue_per(*batches[l]) for l in plans)
+    pos, open_update = 0, None
+    while pos < len(ops):
+        us = draws.uniform_peek((len(ops) - pos) * per)
+        l0 = ops[pos][1]
+        lead = plans[l0]
+        cur = ll_cache.get(l0) if one else None
+        # The window's device state is put in place BEFORE its first operation: that operation's prior factorisation (a deeper
+        # layer's, or layer 0's under an injected stream) notes its info word in the state, and a reset behind it would
+        # drop a non-positive-definite prior silently (the queue would carry on with nu from a failed factor instead of
+        # raising LinAlgError like the host loop and the reference, imputation.py:54-63).
+        if open_update is not None:
+            lead.resume_state(open_update)
+        else:
+            lead.reset_state(0, cur)
+        ll0 = 2 if open_update is not None else (not one or cur is None)   # (dgpamd_ess_queue's compute_ll0)
+        open_update = None
+        for j in ([pos] if one else range(pos, len(ops))):
+            l = ops[j][1]
+            plan = plans[l]
+            if plan is not lead:
+                lead.upload_uniforms(us)
+                plan.share_with(lead)
+            F, NU, scales = args_of(j, lead)
+            plan.queue(F, NU, scales, us, 0, None, ll0, batches[l][1], batches[l][2], fresh=False)
+        if first_queued is not None:
+            first_queued()
+            first_queued = None
+        st = lead.fetch()   # the one synchronisation of the window (of the whole I-step unless an update was left open)
+        status, done, used = int(st['status']), int(st['updates']), int(st['cursor'])
+        draws.uniform_take(used)
+        stats['proposals'] += int(st['proposals'])
+        stats['batches'] += int(st['batches'])
+        stats['updates'] += done
+        if one:
+            ll_cache[l0] = float(st['ll'])
+        else:
+            ll_cache.clear()
+        pos += done
+        if status == 0:
+            break
+        if status == 2:
+            raise_not_pd(int(st['info']))
+        if (status in (1, 4) and not us) or (status == 4 and done == 0 and used == 0):   # (fewer than an update's first two are left)
+            raise RuntimeError('injected uniform stream exhausted')
+        if status == 4:   # the uploaded uniforms ran out between two updates
+            continue
+        # An open update has pending = 1, so the window that continues it takes at least the closing shrink's uniform; one that
+        # opened it took two.  A window that leaves one open having consumed nothing would be repeated for ever.
+        if done == 0 and used == 0:
+            raise RuntimeError('the device queue left an update open without consuming a uniform (status %d)' % status)
+        if resume_on_device:
+            # the next window continues it on the device (dgpamd_ess_queue, compute_ll0 = 2) -- the host loop's finish cost an idle
+            # millisecond 0.4 times per iteration at the bench shape (profiles/r06_idle_gaps.txt)
+            open_update = st
+            continue
+        finish(pos, st)   # (the rest is queued anew)
+        pos += 1
+
+
 class imputer:
     """Args as dgpsi.imputer (imputation.py:13) plus `draws` (a DrawStream), `engine`, and
     `batch` (speculative proposals per launch)."""
@@ -236,7 +319,7 @@ class imputer:
         st['_engine'] = None
         st['_factor_cache'] = {}
         st['_ess_plans'] = {}
-        for key in ('_attached', 'F', '_glob', '_yy', '_x0', '_ll_cache', '_const', '_Fh', '_vecch_dev', '_vecch_y', '_adopt', '_adopt_ll', '_given_inputs', '_sp_levels', '_lik_cache'):   # device state: rebuilt by the next sample()
+        for key in ('_attached', 'F', '_glob', '_yy', '_x0', '_ll_cache', '_const', '_Fh', '_upper_dev', '_adopt', '_adopt_ll', '_given_inputs', '_sp_levels', '_lik_cache'):   # device state: rebuilt by the next sample()
             st.pop(key, None)
         return st
 
@@ -485,18 +568,11 @@ class imputer:
         self.finish_detach()
         self._attach(trusted)
         n_layer = len(self.all_layer)
-        if n_layer > 2 and self._sample_queued_deep(burnin + 1):   # every sweep of every hidden layer queued on the device
+        if self._sample_queued(burnin + 1):   # every sweep of every hidden layer queued on the device
             self._detach(defer=not detach)
             return
-        first, ahead = self._sample_queued(burnin + 1) if n_layer == 2 else (0, None)   # sweeps done without host round trips
-        if first > burnin:
-            self._detach(defer=not detach)
-            return
-        if ahead is None:
-            ahead = self._prior_draws_ahead(burnin + 1) if n_layer > 1 else None
-        else:
-            ahead = ahead[first:]   # (the prior draws of every sweep were made for the queue)
-        for sweep in range(burnin + 1 - first):
+        ahead = self._prior_draws_ahead(burnin + 1) if n_layer > 1 else None
+        for sweep in range(burnin + 1):
             for l in range(n_layer - 1):
                 upper = self.all_layer[l + 1]
                 hetero = any(nd.type == 'likelihood' and getattr(nd, 'exact_post_idx', None) is not None for nd in upper)
@@ -508,84 +584,75 @@ class imputer:
         self._detach(defer=not detach)
 
     queued_calls = 0        # sample() calls that ran through the device queue (the tests read it)
-    queue_max_batches = 2   # speculative batches queued per update (batch, then batch_next): 12 + 4 proposals; an update that
-                            # needs more (a few per cent) is finished by the host loop and the rest of the I-step queued anew
+    queue_max_batches = 2   # speculative batches queued per update (batch, then batch_next); an update that needs more (a few
+                            # per cent) is left open: the next window continues it or the host loop finishes it (run_queue_windows)
 
     def _sample_queued(self, sweeps):
-        """All `sweeps` block updates of a two-layer model's hidden layer queued on the device without a single host
-        synchronisation (dgpamd_ess_queue; imputation.py:22-119): the accept / shrink loop runs in one-thread kernels on a
-        device state, the uniform stream is uploaded ahead and consumed exactly as the sequential loop would.  Returns the
-        number of sweeps completed and the prior draws of all sweeps (an update that ran out of queued batches or uniforms is finished by the host loop,
-        and the remaining sweeps take the ordinary path).  (0, None): not applicable (Vecchia / likelihood / reference-prior
-        nodes, node-wise updates)."""
-        if not self.block or not getattr(self, 'queued', True):
-            return 0, None
+        """sample() with every block update of every sweep and hidden layer queued on the device (dgpamd_ess_queue;
+        imputation.py:22-119): per operation (sweep, hidden layer) the layer's prior draw from its CURRENT inputs (layers above
+        the first: K assembly, factorisation and triangular product queued as well), the refresh of the output buffers of the
+        nodes upstairs and the update itself, continuing one shared device state; run_queue_windows drives the launches and
+        fetches once per window.  The normals are taken from the stream in the order the host loop takes them.  A model with one
+        hidden layer is the general case plus two extras: the log-likelihood of the latents is carried between calls
+        (_carried_ll0), and an update a window left open is continued by the next window on the device instead of by the host
+        loop.  True: the whole call ran through the queue.  False: a layer does not qualify (_queue_applies), nothing was
+        consumed and the host loop runs the call."""
+        hidden = list(range(len(self.all_layer) - 1))
+        if not hidden or not all(self._queue_applies(l) for l in hidden):
+            return False
+        one = len(hidden) == 1
+        e = self.engine
+        n, M = self.F[0].shape
+        if one:
+            self._carried_ll0()
+        # normals, in the host loop's order: layer 0 of every sweep first (one upload; _prior_draws_ahead) unless the stream is
+        # an injected one under several hidden layers, then sweep by sweep the deeper layers
+        nu0 = None if (not one and self.draws._z is not None) else self._prior_draws_ahead(sweeps, prefetch=False)
+        self.__dict__.pop('_want_ll0', None)
+        ops = [(s_, l) for s_ in range(sweeps) for l in hidden]
+        Zdev = {(s_, l): np.stack([self.draws.normal(n) for _ in self.all_layer[l]]) for s_, l in ops if l > 0 or nu0 is None}
+        Zdev = {key: e.tensor(z) for key, z in Zdev.items()}
+        plans = {l: self._queue_plan(l) for l in hidden}
+        batches = {l: self._queue_batches(l) for l in hidden}
+        scales = {l: [float(nd.scale[0]) if nd.type == 'gp' else 1.0 for nd in self.all_layer[l + 1]] for l in hidden}
+        nus = {}
+
+        def args_of(j, lead):   # (F, NU, scales) of the dgpamd_ess_queue call that starts at operation j
+            s_, l = ops[j]
+            if one:   # one call takes all remaining sweeps
+                return self.F[l], nu0[s_:], scales[l]
+            nus[j] = nu = nu0[s_] if (l == 0 and nu0 is not None) else self._prior_draw_queued(l, Zdev[(s_, l)], lead)
+            self._queue_refresh_y(l, plans[l])
+            return self.F[l], nu[None], scales[l]
+
+        def finish(j, st):   # the host loop finishes operation j from the device's bracket
+            s_, l = ops[j]
+            self.one_sample_block(l, nu=nu0[s_] if one else nus[j], resume=_resume_args(st))
+
+        # (several hidden layers: on-device resume is out of scope -- it changes the number of synchronisations, which nobody has measured)
+        resume_on_device = one and os.environ.get('DGPAMD_ESS_RESUME', '1') != '0'
+        # one hidden layer: the next call's normals are generated by a background thread while this one waits in the first fetch
+        # (started only once the window is queued: it would fight the launches for the interpreter)
+        ahead = (lambda: self.draws.prefetch(sweeps * M * n, engine=e)) if one else None
+        self.queued_calls += 1
+        run_queue_windows(ops, plans, batches, self.draws, self.stats, self._ll_cache, args_of, finish, resume_on_device, ahead)
+        if not one and nu0 is not None:
+            self.draws.prefetch(sweeps * M * n, engine=e)
+        return True
+
+    def _carried_ll0(self):
+        """One hidden layer only: the log-likelihood of the current latents, the first slice threshold's base, carried into this
+        call -- self._ll_cache[0] as the previous window or host update left it, else handed over by the M-step
+        (_adopted_ll0), else factored together with the prior's matrices (_want_ll0 rides along in _layer_factors).  With
+        several hidden layers every queued update computes its own."""
         layer, upper = self.all_layer[0], self.all_layer[1]
-        if not self._queue_applies(0):
-            return 0, None
         gp_top = all(nd.type == 'gp' for nd in upper)
-        if self._ll_cache.get(0) is None and gp_top:   # the first threshold's log-likelihood: handed over by the M-step if it can be ...
+        if self._ll_cache.get(0) is None and gp_top:
             v = self._adopted_ll0()
             if v is not None:
                 self._ll_cache[0] = v
-        if self._ll_cache.get(0) is None and gp_top and not any(nd.vecch for nd in layer + upper):   # ... else factored together with the prior's matrices
+        if self._ll_cache.get(0) is None and gp_top and not any(nd.vecch for nd in layer + upper):
             self._want_ll0 = list(enumerate(upper))
-        nu = self._prior_draws_ahead(sweeps, prefetch=False)   # (sweeps, n, M); the next call's normals are started below
-        self.__dict__.pop('_want_ll0', None)
-        if nu is None:
-            return 0, None
-        e = self.engine
-        F = self.F[0]
-        n, M = F.shape
-        plan = self._queue_plan(0)
-        b0, bn, qmax = self._queue_batches(0)
-        per = 2 + (b0 - 1) + (qmax - 1) * bn + 2
-        scales = [float(nd.scale[0]) if nd.type == 'gp' else 1.0 for nd in upper]
-        first = 0
-        begun = False
-        open_update = None   # the state of an update a queue left open (out of queued batches / of uploaded uniforms): the next queue goes on with it
-        while first < sweeps:
-            us = self.draws.uniform_peek((sweeps - first) * per)
-            cur = self._ll_cache.get(0)
-            if open_update is not None:
-                plan.resume_state(open_update)
-                plan.queue(F, nu[first:], scales, us, 0, None, 2, bn, qmax, fresh=False)
-                open_update = None
-            else:
-                plan.queue(F, nu[first:], scales, us, 0, cur, cur is None, bn, qmax)
-            if not begun:   # the next call's normals: generated by a background thread while this one waits in fetch()
-                self.draws.prefetch(sweeps * M * n, engine=e)   # (started only now: it would fight the launches above for the interpreter)
-                self.queued_calls += 1
-                begun = True
-            st = plan.fetch()   # the one synchronisation of the queue (of the whole I-step unless an update was left open)
-            status, done = int(st['status']), int(st['updates'])
-            self.draws.uniform_take(int(st['cursor']))
-            self.stats['proposals'] += int(st['proposals'])
-            self.stats['batches'] += int(st['batches'])
-            self.stats['updates'] += done
-            self._ll_cache[0] = float(st['ll'])
-            first += done
-            if status == 0:
-                break
-            if status == 2:
-                raise_not_pd(int(st['info']))
-            if status == 4:   # the uploaded uniforms ran out between two updates
-                if not us:
-                    raise RuntimeError('injected uniform stream exhausted')
-                continue
-            # the open update (out of queued batches, status 3, or of uploaded uniforms, status 1)
-            if status == 1 and not us:
-                raise RuntimeError('injected uniform stream exhausted')
-            if os.environ.get('DGPAMD_ESS_RESUME', '1') != '0':
-                # round 6: the next queue continues it on the device (dgpamd_ess_queue, compute_ll0 = 2) -- the host loop's finish cost an idle
-                # millisecond 0.4 times per iteration at the bench shape (profiles/r06_idle_gaps.txt)
-                open_update = st
-                continue
-            # (DGPAMD_ESS_RESUME=0, rounds 3-5: the host loop finishes it, the remaining sweeps are queued anew)
-            self.one_sample_block(0, nu=nu[first], resume=dict(log_y=float(st['log_y']), theta=float(st['theta']), lo=float(st['lo']),
-                                                                 hi=float(st['hi']), pending=bool(st['pending'])))
-            first += 1
-        return sweeps, nu
 
     def _queue_applies(self, l):
         """Can the updates of hidden layer l run through dgpamd_ess_queue?  Block updates; GP nodes in the layer; above it GP
@@ -683,9 +750,8 @@ class imputer:
                 d = dict(kind=nd.name, colmap=np.asarray(nd.input_dim, dtype=np.int32), Xglob=self._glob[(l + 1, k)], length=nd.length,
                          nugget=nd.nugget[0], W=None if nd.rep is None else e.tensor(nd.W_diag), y=y)
                 if nd.vecch:
-                    od = nd.ord_dev()
-                    d['vecch'] = dict(ord=od, nn=nd.nn_dev(), nd=e.tensor(np.ones(n) if nd.rep is None else nd.W_diag),
-                                      y=y[od].contiguous() if last else e.empty(n),
+                    v = self._upper_vecch(l + 1, k)
+                    d['vecch'] = dict(ord=v['ord'], nn=v['nn'], nd=v['nd'], y=v['y'] if last else e.empty(n),
                                       rows=ddist.vecchia_rows(n) if ddist.rows_split() else None)
                 if not last:
                     ybuf[k] = (y, d['vecch']['y'] if nd.vecch else None, d['vecch']['ord'] if nd.vecch else None)
@@ -714,91 +780,18 @@ class imputer:
             return self._vecchia_draws(l, list(range(M)), Z[:, None, :].contiguous())[:, 0].t().contiguous()
         Np = e.padded_dim(n)
         buf = e.workspace(('qprior', l, n, M), M * Np * Np * 8)[:M * Np * Np * 8].view(torch.float64).view(M, Np, Np)
-        for k, nd in enumerate(layer):
-            Xl, cm = self._node_input(l, k, nd)
-            e.kmatrix(nd.name, Xl, cm, self._glob[(l, k)], nd.length, nd.nugget[0], out=buf[k], full=False)
+        for k in range(M):
+            self._node_kmatrix(l, k, buf[k])
         _, info = e.potrf(n, buf, batch=M)
         plan.note_info(info)
         out = e.trmv_lower(n, buf, [float(nd.scale[0]) for nd in layer], Z, batch=M)
         return out.t().contiguous()
 
-    def _sample_queued_deep(self, sweeps):
-        """sample() for a model with more than one hidden layer with every update of every sweep queued on the device
-        (imputation.py:22-119): per sweep and hidden layer -- the layer's prior draw from its CURRENT inputs (layers above
-        the first: K assembly, factorisation and triangular product queued as well), the refresh of the output buffers of the
-        nodes upstairs, ONE update through dgpamd_ess_queue continuing the shared device state -- and one fetch at the end.
-        The normals are taken from the stream in the order the host loop takes them.  An update left open (out of queued
-        batches or uniforms) is finished by the host loop and the rest is queued anew.  Returns False when a layer does not
-        qualify (the host loop then runs the whole call)."""
-        L = len(self.all_layer)
-        hidden = list(range(L - 1))
-        if not all(self._queue_applies(l) for l in hidden):
-            return False
-        e = self.engine
-        n = self.F[0].shape[0]
-        injected = self.draws._z is not None
-        # normals, in the host loop's order: layer 0 of every sweep first (one upload; _prior_draws_ahead) unless the stream is
-        # an injected one, then sweep by sweep the deeper layers
-        nu0 = None if injected else self._prior_draws_ahead(sweeps, prefetch=False)
-        Zs = {}
-        for s_ in range(sweeps):
-            for l in hidden:
-                if l == 0 and nu0 is not None:
-                    continue
-                Zs[(s_, l)] = np.stack([self.draws.normal(n) for _ in self.all_layer[l]])
-        Zdev = {key: e.tensor(z) for key, z in Zs.items()}
-        ops = [(s_, l) for s_ in range(sweeps) for l in hidden]
-        qb = {l: self._queue_batches(l) for l in hidden}
-        per = max(2 + (b0 - 1) + (qmax - 1) * bn + 2 for b0, bn, qmax in qb.values())
-        plans = {l: self._queue_plan(l) for l in hidden}
-        pos = 0
-        while pos < len(ops):
-            us = self.draws.uniform_peek((len(ops) - pos) * per)
-            lead = plans[ops[pos][1]]
-            nus = {}
-            # The window's device state is reset BEFORE its first operation: that operation's prior factorisation (a deeper
-            # layer's, or layer 0's under an injected stream) notes its info word in the state, and a reset behind it would
-            # drop a non-positive-definite prior silently (the queue would carry on with nu from a failed factor instead of
-            # raising LinAlgError like the host loop and the reference, imputation.py:54-63).
-            lead.reset_state(0, None)
-            for j in range(pos, len(ops)):
-                s_, l = ops[j]
-                plan = plans[l]
-                if plan is not lead:
-                    lead.upload_uniforms(us)
-                    plan.share_with(lead)
-                if l == 0 and nu0 is not None:
-                    nu = nu0[s_]
-                else:
-                    nu = self._prior_draw_queued(l, Zdev[(s_, l)], lead)
-                nus[j] = nu
-                self._queue_refresh_y(l, plan)
-                scales = [float(nd.scale[0]) if nd.type == 'gp' else 1.0 for nd in self.all_layer[l + 1]]
-                plan.queue(self.F[l], nu[None], scales, us, 0, None, True, qb[l][1], qb[l][2], fresh=False)
-            st = lead.fetch()
-            status, done = int(st['status']), int(st['updates'])
-            self.draws.uniform_take(int(st['cursor']))
-            self.stats['proposals'] += int(st['proposals'])
-            self.stats['batches'] += int(st['batches'])
-            self.stats['updates'] += done
-            self._ll_cache = {}
-            pos += done
-            if status == 0:
-                break
-            if status == 2:
-                raise_not_pd(int(st['info']))
-            if status == 4:
-                if not us:
-                    raise RuntimeError('injected uniform stream exhausted')
-                continue
-            s_, l = ops[pos]   # the open update: finished by the host loop from the device's bracket
-            self.one_sample_block(l, nu=nus[pos], resume=dict(log_y=float(st['log_y']), theta=float(st['theta']), lo=float(st['lo']),
-                                                                hi=float(st['hi']), pending=bool(st['pending'])))
-            pos += 1
-        if nu0 is not None:
-            self.draws.prefetch(sweeps * self.F[0].shape[1] * n, engine=e)
-        self.queued_calls += 1
-        return True
+    def _node_kmatrix(self, l, k, out, **kw):
+        """K (lower tiles) of GP node k of layer l at its current inputs into the (Np, Np) buffer `out`."""
+        nd = self.all_layer[l][k]
+        Xl, cm = self._node_input(l, k, nd)
+        self.engine.kmatrix(nd.name, Xl, cm, self._glob[(l, k)], nd.length, nd.nugget[0], out=out, full=False, **kw)
 
     def _layer_factors(self, l, dense):
         """Cholesky factors of the dense nodes `dense` of layer l in ONE batched buffer (stride Np^2) so that the draws
@@ -820,13 +813,9 @@ class imputer:
             nb = len(dense) + len(extra)
             buf = hit[1] if hit is not None and hit[1].shape[0] == nb else e.empty(nb, Np, Np)
             for j, k in enumerate(dense):
-                nd = layer[k]
-                Xl, cm = self._node_input(l, k, nd)
-                e.kmatrix(nd.name, Xl, cm, self._glob[(l, k)], nd.length, nd.nugget[0], out=buf[j], full=False)
+                self._node_kmatrix(l, k, buf[j])
             for j, (k, nd) in enumerate(extra):   # K of an upper node at the current latents, its output riding along
-                Xl, cm = self._node_input(1, k, nd)
-                e.kmatrix(nd.name, Xl, cm, self._glob[(1, k)], nd.length, nd.nugget[0],
-                          W=None if nd.rep is None else e.tensor(nd.W_diag), out=buf[len(dense) + j], full=False, Y=self._node_y(1, k))
+                self._node_kmatrix(1, k, buf[len(dense) + j], W=None if nd.rep is None else e.tensor(nd.W_diag), Y=self._node_y(1, k))
             lls = []
             for c0 in range(0, nb, 64):
                 n1 = min(64, nb - c0)
@@ -841,6 +830,12 @@ class imputer:
                     self._ll_cache[0] = float(got[n1:].sum())
             self._factor_cache[l] = (sigs, buf)
         return self._factor_cache[l][1]
+
+    def _normals_ahead(self, sweeps, M, n):
+        """The next sweeps x M x n normals of the stream as a (sweeps, M, n) device tensor."""
+        if self.draws._z is None:
+            return self.draws.normals_device(self.engine, sweeps * M * n).view(sweeps, M, n)
+        return self.engine.tensor(np.stack([np.stack([self.draws.normal(n) for _ in range(M)]) for _ in range(sweeps)]))
 
     def _prior_draws_ahead(self, sweeps, prefetch=True):
         """Layer 0's prior draws for all `sweeps` sweeps of a sample() call at once: its factors depend only on X and
@@ -863,19 +858,13 @@ class imputer:
             return None
         if all_vecch:
             # Vecchia: M x sweeps independent sparse forward substitutions, all in one launch
-            if self.draws._z is None:
-                Zd = self.draws.normals_device(e, sweeps * M * n).view(sweeps, M, n)
-            else:
-                Zd = e.tensor(np.stack([np.stack([self.draws.normal(n) for _ in range(M)]) for _ in range(sweeps)]))
+            Zd = self._normals_ahead(sweeps, M, n)
             xs = self._vecchia_draws(0, list(range(M)), Zd.permute(1, 0, 2).contiguous())   # (M, sweeps, n)
             if prefetch:
                 self.draws.prefetch(sweeps * M * n, engine=e)
             return xs.permute(1, 2, 0).contiguous()
         buf = self._layer_factors(0, list(range(M)))
-        if self.draws._z is None:
-            Zd = self.draws.normals_device(e, sweeps * M * n).view(sweeps, M, n)
-        else:
-            Zd = e.tensor(np.stack([np.stack([self.draws.normal(n) for _ in range(M)]) for _ in range(sweeps)]))
+        Zd = self._normals_ahead(sweeps, M, n)
         scales = [float(nd.scale[0]) for nd in layer]
         out = e.empty(sweeps, M, n)
         for s_ in range(sweeps):
@@ -941,6 +930,26 @@ class imputer:
         xs = e.vecchia_spsolve_levels(torch.stack(Lms), NNall, sc, Zd.contiguous(), hit[1])
         return torch.stack([xs[j][:, rev[j]] for j in range(len(nodes))])
 
+    def _upper_vecch(self, l, k):
+        """Device tensors of Vecchia GP node k of layer l as the likelihood of the layer below, for the host loop and the
+        queue alike: ordering `ord`, neighbour array `nn`, ordered nugget weights `nd`, the column map `cm` as a long tensor
+        and, for observed outputs (the last layer), the ordered `y` (None for a hidden layer: its outputs are latents).  They
+        stay on the device (the neighbour array is 10 MB at n = 50 000) while the node keeps the arrays they were made from."""
+        nd = self.all_layer[l][k]
+        n = self.F[l - 1].shape[0]
+        sig = (id(nd.ord), id(nd.NNarray), id(nd.input_dim), None if nd.rep is None else id(nd.W_diag), n)
+        cache = self.__dict__.setdefault('_upper_dev', {})
+        hit = cache.get((l, k))
+        if hit is None or hit['sig'] != sig:
+            od = nd.ord_dev()
+            hit = cache[(l, k)] = dict(sig=sig, ord=od, nn=nd.nn_dev(), nd=self.engine.tensor(np.ones(n) if nd.rep is None else nd.W_diag),
+                                       cm=torch.as_tensor(np.asarray(nd.input_dim), device=od.device, dtype=torch.long), ysrc=None, y=None)
+        if l == len(self.all_layer) - 1:   # (ordered once per source tensor and ordering, not once per batch)
+            ysrc = self._node_y(l, k)
+            if hit['ysrc'] is not ysrc:
+                hit['ysrc'], hit['y'] = ysrc, ysrc[hit['ord']].contiguous()
+        return hit
+
     def _upper_loglik(self, l, FP, only=None):
         """sum over the nodes of layer l+1 (or those listed in `only`) of their log-likelihood for each candidate
         block FP[b] (imputation.py:70-78,91-106).  Returns (ll (B,) numpy, info (B,) numpy)."""
@@ -966,23 +975,9 @@ class imputer:
                         FPh = FP.cpu().numpy()
                     host += self._ref_prior_terms(nd, FPh)
             elif nd.type == 'gp':
-                # (index arrays, the 10-MB neighbour array and the nugget weights stay on the device while the node keeps them)
-                sig = (id(nd.ord), id(nd.NNarray), id(nd.input_dim), None if nd.rep is None else id(nd.W_diag), FP.shape[1])
-                hit = self.__dict__.setdefault('_vecch_dev', {}).get((l + 1, k))
-                if hit is None or hit[0] != sig:
-                    hit = (sig, (torch.as_tensor(np.asarray(nd.input_dim), device=FP.device, dtype=torch.long),
-                                 nd.ord_dev(), nd.nn_dev(),
-                                 e.tensor(np.ones(FP.shape[1]) if nd.rep is None else nd.W_diag)))
-                    self._vecch_dev[(l + 1, k)] = hit
-                cm, od, NN, nd_diag = hit[1]
-                ysrc = self._node_y(l + 1, k)
-                if l + 1 == len(self.all_layer) - 1:   # (observed outputs: ordered once per ordering, not once per batch)
-                    yhit = self.__dict__.setdefault('_vecch_y', {}).get((l + 1, k))
-                    if yhit is None or yhit[0] is not ysrc or yhit[1] is not od:
-                        yhit = self._vecch_y[(l + 1, k)] = (ysrc, od, ysrc[od].contiguous())
-                    y = yhit[2]
-                else:
-                    y = ysrc[od].contiguous()
+                v = self._upper_vecch(l + 1, k)
+                cm, od, NN, nd_diag = v['cm'], v['ord'], v['nn'], v['nd']
+                y = v['y'] if v['y'] is not None else self._node_y(l + 1, k)[od].contiguous()   # (a hidden layer's outputs: the current latents)
                 # the ordered inputs of ALL candidates in at most three device operations (was five small ones per candidate:
                 # the host could not keep the device busy between the row kernels); one when the node takes every column in order
                 ident = FP.shape[2] == len(nd.input_dim) and np.array_equal(np.asarray(nd.input_dim), np.arange(FP.shape[2]))

@@ -953,6 +953,21 @@ def _fill_lik_node(nd, colmap, lik, M):
     return (colmap, lik['y'], lik.get('rep'))
 
 
+def _fill_gp_node(nd, kind, colmap, Xglob, length, nugget, W, y, M):
+    """dgpamd_node fields of a GP node that reads its local inputs through `colmap` from an (n, M) latent block
+    (include/dgp_amd.h); returns what must stay alive with the struct."""
+    colmap = np.ascontiguousarray(np.asarray(colmap, dtype=np.int32))
+    length = np.ascontiguousarray(np.asarray(length, dtype=np.float64))
+    nd.kind, nd.Dl, nd.Dg = KIND[kind], len(colmap), 0 if Xglob is None else Xglob.shape[1]
+    nd.nlen, nd.nugget_est, nd.ldloc = len(length), 0, M
+    nd.Xloc, nd.colmap = None, colmap.ctypes.data
+    nd.Xglob = None if Xglob is None else Xglob.data_ptr()
+    nd.length, nd.nugget = length.ctypes.data, float(nugget)
+    nd.W = None if W is None else W.data_ptr()
+    nd.y = y.data_ptr()
+    return (colmap, length, Xglob, W, y)
+
+
 class _EssQueue:
     """Several elliptical-slice updates of one latent block queued without host synchronisation (dgpamd_ess_queue):
     node structs, scratch and the device state are kept alive here; fetch() is the one synchronisation.  Several queues
@@ -974,18 +989,9 @@ class _EssQueue:
             if d.get('lik') is not None:   # a likelihood node: dict(kind, y, rep, classes, par) + colmap
                 self.keep.append(_fill_lik_node(arr[i], d['colmap'], d['lik'], M))
                 continue
-            colmap = np.ascontiguousarray(np.asarray(d['colmap'], dtype=np.int32))
-            length = np.ascontiguousarray(np.asarray(d['length'], dtype=np.float64))
-            self.keep += [colmap, length, d['Xglob'], d['W'], d['y'], d.get('vecch')]
             nd = arr[i]
-            nd.kind, nd.Dl, nd.Dg = KIND[d['kind']], len(colmap), 0 if d['Xglob'] is None else d['Xglob'].shape[1]
-            nd.nlen, nd.nugget_est, nd.ldloc = len(length), 0, M
-            nd.Xloc, nd.colmap = None, colmap.ctypes.data
-            nd.Xglob = None if d['Xglob'] is None else d['Xglob'].data_ptr()
-            nd.length, nd.nugget = length.ctypes.data, float(d['nugget'])
-            nd.W = None if d['W'] is None else d['W'].data_ptr()
-            nd.y = d['y'].data_ptr()
             v = d.get('vecch')
+            self.keep += [_fill_gp_node(nd, d['kind'], d['colmap'], d['Xglob'], d['length'], d['nugget'], d['W'], d['y'], M), v]
             if v is not None:
                 nd.vecch_ord, nd.vecch_nn = v['ord'].data_ptr(), v['nn'].data_ptr()
                 nd.vecch_nd, nd.vecch_y = v['nd'].data_ptr(), v['y'].data_ptr()
@@ -1067,17 +1073,8 @@ class _EssPlan:
     def __init__(self, eng, n, M, kind, colmap, Xglob, length, nugget, W, y, batch):
         self.e, self.n, self.M, self.batch = eng, int(n), int(M), int(batch)
         Np = eng.padded_dim(n)
-        self.keep = (Xglob, W, y)
-        self.colmap = np.ascontiguousarray(np.asarray(colmap, dtype=np.int32))
-        self.length = np.ascontiguousarray(np.asarray(length, dtype=np.float64))
-        nd = self.node = _lib.Node()
-        nd.kind, nd.Dl, nd.Dg = KIND[kind], len(self.colmap), 0 if Xglob is None else Xglob.shape[1]
-        nd.nlen, nd.nugget_est, nd.ldloc = len(self.length), 0, M
-        nd.Xloc, nd.colmap = None, self.colmap.ctypes.data
-        nd.Xglob = None if Xglob is None else Xglob.data_ptr()
-        nd.length, nd.nugget = self.length.ctypes.data, float(nugget)
-        nd.W = None if W is None else W.data_ptr()
-        nd.y = y.data_ptr()
+        self.node = _lib.Node()
+        self.keep = _fill_gp_node(self.node, kind, colmap, Xglob, length, nugget, W, y, M)
         self.FP = eng.workspace(('essFP', n, M, batch), batch * n * M * 8)
         self.A = eng.workspace(('essA', n, batch), batch * Np * Np * 8)
         self.work = eng.potrf_workspace(n, batch)

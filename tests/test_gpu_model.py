@@ -1162,8 +1162,8 @@ def test_queued_ess_equals_host_loop(eng, nout, batch):
     """imputer.sample on a two-layer model: the device-resident accept / shrink loop (dgpamd_ess_queue, zero host round trips
     inside the I-step) takes the same decisions as the host loop -- same latents, same number of proposals, the
     uniform stream left at the same position -- with one and with several GP nodes in the layer above (their
-    log-likelihoods are summed, imputation.py:91-106); batch=2 forces updates that run out of queued batches and
-    are finished by the host loop."""
+    log-likelihoods are summed, imputation.py:91-106); batch=2 forces updates that run out of queued batches: with
+    the one hidden layer here the next queue continues them on the device."""
     from dgp_amd import dgp, kernel, combine
     rng = np.random.default_rng(5)
     n, d = 300, 3
@@ -1191,6 +1191,43 @@ def test_queued_ess_equals_host_loop(eng, nout, batch):
     assert uq == uh
 
 
+@pytest.mark.parametrize('nout', [1, 3])
+def test_queued_open_update_policies_agree(eng, nout, monkeypatch):
+    """The two ways an update that ran out of queued batches is carried on in a model with one hidden layer -- the next queue
+    continues it on the device (the default), or the host loop finishes it and the rest is queued anew (DGPAMD_ESS_RESUME=0,
+    read per call) -- take the same decisions: same latents, same counts, the uniform stream left at the same position.
+    Batches of 2, two queued per update: most updates are left open at least once."""
+    from dgp_amd import dgp, kernel, combine
+    rng = np.random.default_rng(5)
+    n, d = 300, 3
+    X = rng.uniform(size=(n, d))
+    Y = np.stack([np.sin(3 * X[:, 0] + k) + X[:, 1] ** 2 * (k + 1) for k in range(nout)], 1)
+    Y = (Y - Y.mean(0)) / Y.std(0)
+
+    def run(resume):
+        if resume:
+            monkeypatch.delenv('DGPAMD_ESS_RESUME', raising=False)
+        else:
+            monkeypatch.setenv('DGPAMD_ESS_RESUME', '0')
+        layers = combine([kernel(length=np.array([1.0]), name='matern2.5') for _ in range(d)],
+                         [kernel(length=np.array([0.8]), name='matern2.5' if k % 2 == 0 else 'sexp', scale_est=True, connect=np.arange(d))
+                          for k in range(nout)])
+        model = dgp(X, Y, layers, seed=3)
+        model.imp.batch = model.imp.batch_next = 2
+        before = model.imp.queued_calls
+        for _ in range(2):
+            model.imp.sample(burnin=6)
+        F = np.stack([nd.output[:, 0] for nd in model.all_layer[0]], 1)
+        return F, dict(model.imp.stats), model.imp.draws.uniform_peek(3), model.imp.queued_calls - before
+
+    Fd, sd, ud, qd = run(True)
+    Fh, sh, uh, qh = run(False)
+    print('stats: device resume', sd, 'host finish', sh, 'queued calls', qd, qh)
+    close(Fd, Fh, rtol=1e-9, atol=1e-11)
+    assert sd == sh, (sd, sh)   # proposals, updates, batches
+    assert ud == uh
+    assert qd == 2 and qh == 2
+
 
 @pytest.mark.parametrize('shape', ['vecchia_top', 'vecchia_all', 'three_layers', 'three_layers_vecchia'])
 @pytest.mark.parametrize('batch', [12, 2])
@@ -1201,7 +1238,8 @@ def test_queued_ess_equals_host_loop_other_shapes(eng, shape, batch):
     layers (imputation.py:22-42: per sweep and hidden layer the prior draw from the CURRENT inputs -- K assembly,
     factorisation, triangular product queued on the device as well -- then one queued update; one fetch per I-step).
     Same latents in every layer, same proposal / batch / update counts, the uniform stream left at the same position as
-    the host loop; batch=2 forces updates that run out of queued batches and are finished by the host."""
+    the host loop; batch=2 forces updates that run out of queued batches: with one hidden layer they are continued by the
+    next queue, with several they are finished by the host loop."""
     from dgp_amd import dgp, kernel, combine
     rng = np.random.default_rng(11)
     n, d = 260, 3
@@ -1277,7 +1315,8 @@ def test_queued_ess_equals_host_loop_likelihood_tops(eng, lik, batch):
     """The device-resident accept / shrink loop with a likelihood node on top (imputation.py:71-78,
     91-106 -> <likelihood>.llik()): the node's summed log-density is a library kernel (dgpamd_lik_loglik) that the host
     loop and the queue both use, so the two take the same decisions -- same latents in every layer, same proposal /
-    batch / update counts, the uniform stream left at the same position.  Count data with replicates for NegBin."""
+    batch / update counts, the uniform stream left at the same position.  Count data with replicates for NegBin.  batch=2
+    forces updates that run out of queued batches: two hidden layers here, so the host loop finishes them."""
     from dgp_amd import dgp, kernel, combine, Poisson, NegBin, ZIP, ZINB, Categorical
     rng = np.random.default_rng(23)
     n, d = 180, 2
