@@ -7,29 +7,11 @@
 // dgpamd_vpaths_nn finds the sets, dgpamd_vpaths_rows emits each row in dgpamd_vecchia_spsolve's layout and the
 // substitution is dgpamd_vecchia_levels + dgpamd_vecchia_spsolve_levels.
 #include "common.hpp"
+#include "vblock.hpp"
 #include "vecchia_pred.hpp"
-#include "wave.hpp"
 
 #include <climits>
 #include <math.h>
-
-namespace {
-
-// (the LDS kernels' corr_pts of vecchia.hip with exp_negated in place of the library's exp: other bits, not to be merged)
-template <int KIND>
-__device__ __forceinline__ double vp_corr(const double *xa, const double *xb, int D) {
-    double s = 0.0, pr = 1.0;
-    for (int d = 0; d < D; ++d) {
-        const double df = xa[d] - xb[d];
-        if (KIND == DGPAMD_SEXP)
-            corr_accum_sexp(df, s);
-        else
-            corr_accum_matern(df, pr, s);
-    }
-    return (KIND == DGPAMD_SEXP) ? exp_negated(s) : pr * exp_negated(SQRT5 * s);
-}
-
-}  // namespace
 
 // ---------------------------------------------------------------------------
 // Neighbour search.  One wave per (path, position): the candidates are scanned 64 at a time (training rows first, then the
@@ -165,7 +147,8 @@ __global__ __launch_bounds__(256) void vpaths_rows_reg_kernel(VPRowArgs a) {
         for (int d = 0; d < DM; ++d) xr[d] = (d < D && lane <= b) ? src[d] : 0.0;
     }
     const double dg = 1.0 + a.jitter + a.nugget * (tr && a.omega ? a.omega[nnv] : 1.0);
-    auto column = [&](int c) {
+    double reg[VG_BC], last;
+    vreg_fill(reg, last, b, [&](int c) {
         double s = 0.0, pr = 1.0;
 #pragma unroll
         for (int d = 0; d < DM; ++d) {
@@ -177,36 +160,11 @@ __global__ __launch_bounds__(256) void vpaths_rows_reg_kernel(VPRowArgs a) {
         }
         const double v = (KIND == DGPAMD_SEXP) ? exp_negated(s) : pr * exp_negated(SQRT5 * s);
         return lane == c ? dg : v;
-    };
-    double reg[VG_BC];
-    static_for<0, VG_BC>([&](auto ic) {
-        constexpr int c = decltype(ic)::value;
-        reg[c] = 0.0;
-        if (c < b) reg[c] = column(c);
     });
-    double last = column(b);
-    bool bad = false;
-    static_for<0, VG_BC>([&](auto ij) {
-        constexpr int j = decltype(ij)::value;
-        if (j < b) {
-            const double dj = readlane_f64(reg[j], j);
-            bad = bad || !(dj > 0.0);
-            const double rd = 1.0 / dj;
-            const double mi = lane > j ? reg[j] * rd : 0.0;
-            static_for<(j + 1) / 8, (VG_BC + 7) / 8>([&](auto ig) {
-                constexpr int c0 = 8 * decltype(ig)::value;
-                if (c0 < b) {
-                    static_for<0, 8>([&](auto iq) {
-                        constexpr int c = c0 + decltype(iq)::value;
-                        if constexpr (c > j && c < VG_BC) reg[c] = fma(-mi, readlane_f64(reg[c], j), reg[c]);
-                    });
-                }
-            });
-            last = fma(-mi, readlane_f64(last, j), last);
-        }
-    });
+    VPivotDivide pivot;
+    vreg_eliminate(reg, last, b, lane, pivot);
     const double schur = readlane_f64(last, b);
-    bad = bad || !(schur > 0.0);
+    const bool bad = pivot.bad || !(schur > 0.0);
     // b_i = U^-1 (L^-1 a): back substitution, pivot j broadcast from lane j
     double coef = 0.0, res = lane < b ? last : 0.0;
     static_for<0, VG_BC>([&](auto ik) {
@@ -263,13 +221,7 @@ __global__ __launch_bounds__(64) void vpaths_rows_lds_kernel(VPRowArgs a) {
     const int64_t p = w / a.M, i = w - p * a.M, n = a.n;
     const int64_t g = a.group ? a.group[p] : 0;
     const double *qp = a.q + p * a.M * D, *xg = a.x + g * n * D;
-    int b = 0;
-    for (int c0 = 0; c0 < m; c0 += 64) {
-        const int c = c0 + lane;
-        const int64_t v = c < m ? a.NN[w * m + c] : -1;
-        if (c < m) idx[c] = v;
-        b += __popcll(__ballot(v >= 0));
-    }
+    const int b = load_nn<false>(a.NN + w * m, m, idx, lane);
     __syncthreads();
     for (int e = lane; e < (b + 1) * D; e += 64) {
         const int r = e / D, d = e - r * D;
@@ -278,44 +230,11 @@ __global__ __launch_bounds__(64) void vpaths_rows_lds_kernel(VPRowArgs a) {
     }
     __syncthreads();
     const int bb = b + 1;
-    for (int e = lane; e < bb * (bb + 1) / 2; e += 64) {
-        int r, c;
-        tri_decode(e, r, c);
-        double v;
-        if (r == c)
-            v = 1.0 + a.jitter + a.nugget * (r < b && idx[r] < n && a.omega ? a.omega[idx[r]] : 1.0);
-        else
-            v = vp_corr<KIND>(xs + r * D, xs + c * D, D);
-        A[r * lda + c] = v;
-    }
-    bool bad = false;
-    for (int j = 0; j < bb; ++j) {
-        __syncthreads();
-        double d = A[j * lda + j];
-        if (!(d > 0.0)) {
-            bad = true;
-            d = 1.0;
-        }
-        const double sdj = sqrt(d), inv = 1.0 / sdj;
-        __syncthreads();
-        for (int r = j + 1 + lane; r < bb; r += 64) A[r * lda + j] *= inv;
-        if (lane == 0) A[j * lda + j] = sdj;
-        __syncthreads();
-        for (int r = j + 1 + lane; r < bb; r += 64) {
-            const double lr = A[r * lda + j];
-            for (int c = j + 1; c <= r; ++c) A[r * lda + c] = fma(-lr, A[c * lda + j], A[r * lda + c]);
-        }
-    }
-    __syncthreads();
+    fill_lower<KIND, VExpFast>(A, lda, bb, xs, D, 1.0,
+                               [&](int r) { return 1.0 + a.jitter + a.nugget * (r < b && idx[r] < n && a.omega ? a.omega[idx[r]] : 1.0); }, lane);
+    const int bad = lds_chol(A, lda, bb, bb, lane);
     for (int c = lane; c < b; c += 64) V[c] = A[b * lda + c];   // l21 = L11^-1 a
-    for (int c = b - 1; c >= 0; --c) {                        // V <- L11^-T V
-        __syncthreads();
-        if (lane == 0) V[c] /= A[c * lda + c];
-        __syncthreads();
-        const double vc = V[c];
-        for (int r = lane; r < c; r += 64) V[r] = fma(-A[c * lda + r], vc, V[r]);
-    }
-    __syncthreads();
+    lds_backsolve_T(A, lda, b, V, lda, 1, lane);              // V <- L11^-T V
     const double l22 = A[b * lda + b];
     const double sdv = sqrt(a.scale) * l22, isd = 1.0 / sdv;
     for (int r = 0; r < a.nrhs; ++r) {
@@ -377,33 +296,12 @@ extern "C" int dgpamd_vpaths_rows(dgpamd_ctx *ctx, int kind, int64_t P, int64_t 
     a.D = D; a.m = m; a.nrhs = nrhs; a.P = P; a.M = M; a.n = n; a.q = q; a.x = x; a.omega = omega; a.y = y; a.group = group;
     a.NN = NN; a.nugget = nugget; a.jitter = jitter; a.scale = scale; a.Lrows = Lrows; a.t = t; a.sd = sd; a.NNl = NNl;
     a.info = info;
-    const bool reg = m <= VG_BC && D <= 16 && !ctx->tune.vecchia_lds;
-    const size_t shm = vpaths_rows_lds_bytes(m, D);
-    const void *fn = kind == DGPAMD_SEXP ? (const void *)vpaths_rows_lds_kernel<DGPAMD_SEXP>
-                                         : (const void *)vpaths_rows_lds_kernel<DGPAMD_MATERN25>;
-    if (!reg) {
-        int rc = set_lds(ctx, fn, shm);
-        if (rc) return rc;
-    }
     HIP_TRY(ctx, hipMemsetAsync(info, 0, sizeof(int32_t), ctx->stream));
-    if (reg) {
-        const unsigned grid = (unsigned)((P * M + 3) / 4);
-        if (kind == DGPAMD_SEXP) {
-            if (D <= 8)
-                hipLaunchKernelGGL((vpaths_rows_reg_kernel<DGPAMD_SEXP, 8>), dim3(grid), dim3(256), 0, ctx->stream, a);
-            else
-                hipLaunchKernelGGL((vpaths_rows_reg_kernel<DGPAMD_SEXP, 16>), dim3(grid), dim3(256), 0, ctx->stream, a);
-        } else {
-            if (D <= 8)
-                hipLaunchKernelGGL((vpaths_rows_reg_kernel<DGPAMD_MATERN25, 8>), dim3(grid), dim3(256), 0, ctx->stream, a);
-            else
-                hipLaunchKernelGGL((vpaths_rows_reg_kernel<DGPAMD_MATERN25, 16>), dim3(grid), dim3(256), 0, ctx->stream, a);
-        }
-    } else if (kind == DGPAMD_SEXP) {
-        hipLaunchKernelGGL(vpaths_rows_lds_kernel<DGPAMD_SEXP>, dim3((unsigned)(P * M)), dim3(64), shm, ctx->stream, a);
-    } else {
-        hipLaunchKernelGGL(vpaths_rows_lds_kernel<DGPAMD_MATERN25>, dim3((unsigned)(P * M)), dim3(64), shm, ctx->stream, a);
-    }
-    LAUNCH_CHECK(ctx);
-    return DGPAMD_OK;
+    if (m > VG_BC || D > 16 || ctx->tune.vecchia_lds)
+        return launch_by_kind(ctx, kind, vpaths_rows_lds_kernel<DGPAMD_SEXP>, vpaths_rows_lds_kernel<DGPAMD_MATERN25>, dim3((unsigned)(P * M)),
+                              dim3(64), vpaths_rows_lds_bytes(m, D), a, q);
+    const dim3 grid4((unsigned)((P * M + 3) / 4));
+    if (D <= 8)
+        return launch_by_kind(ctx, kind, vpaths_rows_reg_kernel<DGPAMD_SEXP, 8>, vpaths_rows_reg_kernel<DGPAMD_MATERN25, 8>, grid4, dim3(256), 0, a, q);
+    return launch_by_kind(ctx, kind, vpaths_rows_reg_kernel<DGPAMD_SEXP, 16>, vpaths_rows_reg_kernel<DGPAMD_MATERN25, 16>, grid4, dim3(256), 0, a, q);
 }

@@ -847,7 +847,7 @@ def test_one_launch_factorisation_with_many_matrices(eng, B):
 def test_nn_query_filter_then_select_equals_streaming_topk(eng):
     """From 30 000 queries against 20 000 points on the query search (vecchia.py:20-40) takes the filter-then-select kernels of round 5
     (a sampled upper bound of every query's K-th nearest distance, a register-light scan that notes the candidates at or below it, the
-    K nearest of the notes; csrc/vecchia.hip nn_tau / nn_collect / nn_pick); DGPAMD_NN_FILTER=0 keeps the streaming top-k kernel.  Same
+    K nearest of the notes; csrc/vecchia_nn.hip nn_tau / nn_collect / nn_pick); DGPAMD_NN_FILTER=0 keeps the streaming top-k kernel.  Same
     neighbour arrays element for element -- uniform points, a cluster the strided sample all but misses (wide bounds, the exact
     slow path), exactly tied distances on a grid, all candidates equal, a query count that does not fill the last block -- and, on a
     sample of queries, the brute-force (distance, index) order."""

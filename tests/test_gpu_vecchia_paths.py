@@ -102,8 +102,11 @@ def test_neighbour_search_equals_brute_force(eng, case, D, n, m):
 @pytest.mark.parametrize('kind', ['sexp', 'matern2.5'])
 def test_rows_equal_numpy(eng, kind, extra, form):
     """b_i (training part through unit right-hand sides, test part from the rows), sqrt(d_i) and t_i, per path and group;
-    m = 80, D = 20 takes the LDS kernel."""
+    m = 80, D = 20 takes the LDS kernel.  The two smaller forms take the register kernel, and once more the LDS kernel (an
+    engine created under DGPAMD_VECCHIA_LDS=1): held to the same reference at the same tolerances, and to the register
+    kernel's rows within test_vecchia_row_kernels_register_and_lds_versions_agree's bound for the same pair of designs."""
     import torch
+    from test_gpu_ops import engine_under
     m, D = form['m'], form['D']
     rng = np.random.default_rng(m + D)
     n, M, P, nugget, scale = 45, 70, 3, 3e-3, 1.7
@@ -112,26 +115,38 @@ def test_rows_equal_numpy(eng, kind, extra, form):
     omega = np.ones(n) if extra == 'plain' else rng.choice([1.0, 0.5, 1 / 3], size=n)
     group = np.array([1, 0, 1], np.int32)
     Y = np.concatenate((np.eye(n)[None].repeat(2, 0), rng.normal(size=(2, 1, n))), 1)   # (G, n + 1, n)
-    NN = eng.vpaths_nn(eng.tensor(Q), eng.tensor(X), m, torch.as_tensor(group, device=eng.device))
-    Lr, NNl, t, sd, info = eng.vpaths_rows(kind, eng.tensor(Q), eng.tensor(X), NN, eng.tensor(Y), scale, nugget,
-                                           None if extra == 'plain' else eng.tensor(omega),
-                                           torch.as_tensor(group, device=eng.device))
-    assert int(npy(info)[0]) == 0
-    Lr, NNl, t, sd, NN = npy(Lr), npy(NNl), npy(t), npy(sd), npy(NN)
-    for p in range(P):
-        x = X[group[p]]
-        for i in range(M):
-            mem, b, s = row_ref(kind, Q[p], x, NN[p, i], i, nugget, omega)
-            tol = 1e-10 * max(1.0, np.abs(b).max())
-            assert abs(sd[p, i] - np.sqrt(scale * s)) <= 1e-10 * np.sqrt(scale * s)
-            tr, te = mem < n, mem >= n
-            np.testing.assert_allclose(t[p, mem[tr], i], b[tr], rtol=0, atol=tol)   # unit right-hand sides
-            np.testing.assert_allclose(t[p, n, i], Y[group[p], n, mem[tr]] @ b[tr], rtol=0, atol=tol * np.abs(Y).max() * n)
-            k = te.sum()
-            assert Lr[p, i, 0] == pytest.approx(1 / sd[p, i], rel=1e-14) and NNl[p, i, 0] == i
-            np.testing.assert_array_equal(NNl[p, i, 1:1 + k], mem[te] - n)
-            np.testing.assert_allclose(-Lr[p, i, 1:1 + k] * sd[p, i], b[te], rtol=0, atol=tol)
-            assert np.all(NNl[p, i, 1 + k:] == -1) and np.all(Lr[p, i, 1 + k:] == 0)
+    dNN = eng.vpaths_nn(eng.tensor(Q), eng.tensor(X), m, torch.as_tensor(group, device=eng.device))
+    NN = npy(dNN)
+    refs = [[row_ref(kind, Q[p], X[group[p]], NN[p, i], i, nugget, omega) for i in range(M)] for p in range(P)]
+
+    def rows(e):
+        Lr, NNl, t, sd, info = e.vpaths_rows(kind, eng.tensor(Q), eng.tensor(X), dNN, eng.tensor(Y), scale, nugget,
+                                             None if extra == 'plain' else eng.tensor(omega),
+                                             torch.as_tensor(group, device=eng.device))
+        assert int(npy(info)[0]) == 0
+        Lr, NNl, t, sd = npy(Lr), npy(NNl), npy(t), npy(sd)
+        for p in range(P):
+            for i in range(M):
+                mem, b, s = refs[p][i]
+                tol = 1e-10 * max(1.0, np.abs(b).max())
+                assert abs(sd[p, i] - np.sqrt(scale * s)) <= 1e-10 * np.sqrt(scale * s)
+                tr, te = mem < n, mem >= n
+                np.testing.assert_allclose(t[p, mem[tr], i], b[tr], rtol=0, atol=tol)   # unit right-hand sides
+                np.testing.assert_allclose(t[p, n, i], Y[group[p], n, mem[tr]] @ b[tr], rtol=0, atol=tol * np.abs(Y).max() * n)
+                k = te.sum()
+                assert Lr[p, i, 0] == pytest.approx(1 / sd[p, i], rel=1e-14) and NNl[p, i, 0] == i
+                np.testing.assert_array_equal(NNl[p, i, 1:1 + k], mem[te] - n)
+                np.testing.assert_allclose(-Lr[p, i, 1:1 + k] * sd[p, i], b[te], rtol=0, atol=tol)
+                assert np.all(NNl[p, i, 1 + k:] == -1) and np.all(Lr[p, i, 1 + k:] == 0)
+        return Lr, NNl, t, sd
+
+    reg = rows(eng)
+    if m <= 51:
+        with engine_under(VECCHIA_LDS=1) as e:
+            lds = rows(e)
+        np.testing.assert_array_equal(lds[1], reg[1])
+        for a, b in zip((lds[0], lds[2], lds[3]), (reg[0], reg[2], reg[3])):
+            np.testing.assert_allclose(a, b, rtol=1e-9, atol=1e-9 * np.abs(b).max())
 
 
 @pytest.mark.parametrize('s', [1.0, 1e4])
