@@ -122,6 +122,7 @@ SIGNATURES = {
     'dgpamd_vpaths_rows': (_i, [_p, _i, _l, _l, _l, _i, _i, _i, _p, _p, _p, _p, _p, _p, _d, _d, _d, _p, _p, _p, _p, _p]),
     'dgpamd_pathfun_eval': (_i, [_p, _i, _l, _l, _i, _l, _i, _p, _l, _p, _i, _p, _l, _p, _p, _p, _p, _p, _i, _d, _p]),
     'dgpamd_pathfun_grad': (_i, [_p, _i, _l, _l, _i, _l, _i, _p, _l, _p, _i, _p, _l, _p, _p, _p, _p, _p, _i, _d, _p, _p]),
+    'dgpamd_vpathfun_update': (_i, [_p, _i, _l, _l, _i, _i, _l, _l, _p, _p, _p, _p, _p, _p, _d, _d, _p, _i, _p, _p]),
 }
 
 MISSING = []

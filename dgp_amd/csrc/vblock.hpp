@@ -149,6 +149,22 @@ __device__ __forceinline__ void vreg_eliminate(double (&reg)[BC], double &last, 
     });
 }
 
+// After vreg_eliminate lane r < b holds row r of U = D L^T in reg[] and (L^-1 a)_r in `last`.  Returns, in lane j < b, entry j
+// of U^-1 (L^-1 a) = A^-1 a (0 in the lanes beyond): back substitution over the lanes, pivot j broadcast from lane j.
+template <int BC>
+__device__ __forceinline__ double vreg_backsolve(const double (&reg)[BC], const double last, const int b, const int lane) {
+    double coef = 0.0, res = lane < b ? last : 0.0;
+    static_for<0, BC>([&](auto ik) {
+        constexpr int j = BC - 1 - decltype(ik)::value;
+        if (j < b) {
+            const double xj = readlane_f64(res, j) / readlane_f64(reg[j], j);
+            coef = lane == j ? xj : coef;
+            res = lane < j ? fma(-reg[j], xj, res) : res;
+        }
+    });
+    return coef;
+}
+
 // The second half of both register-resident link_gp kernels: Gauss-Jordan elimination of K | N with J, y and I riding along, then
 // the mean and the variance (see the squared-exponential kernel, csrc/vecchia_pred_link_sexp.hip, for the algebra).
 __device__ __forceinline__ void linkgp_reg_finish(double (&reg)[VL_BC], double (&jm)[VL_BC], double yv, double Iv, const bool act,

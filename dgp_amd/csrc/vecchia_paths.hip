@@ -165,16 +165,7 @@ __global__ __launch_bounds__(256) void vpaths_rows_reg_kernel(VPRowArgs a) {
     vreg_eliminate(reg, last, b, lane, pivot);
     const double schur = readlane_f64(last, b);
     const bool bad = pivot.bad || !(schur > 0.0);
-    // b_i = U^-1 (L^-1 a): back substitution, pivot j broadcast from lane j
-    double coef = 0.0, res = lane < b ? last : 0.0;
-    static_for<0, VG_BC>([&](auto ik) {
-        constexpr int j = VG_BC - 1 - decltype(ik)::value;
-        if (j < b) {
-            const double xj = readlane_f64(res, j) / readlane_f64(reg[j], j);
-            coef = lane == j ? xj : coef;
-            res = lane < j ? fma(-reg[j], xj, res) : res;
-        }
-    });
+    const double coef = vreg_backsolve(reg, last, b, lane);   // b_i = U^-1 (L^-1 a)
     const double sdv = sqrt(a.scale * schur);
     for (int r = 0; r < a.nrhs; ++r) {
         const double tv = wave_sum_all(tr ? coef * a.y[(g * a.nrhs + r) * n + nnv] : 0.0);

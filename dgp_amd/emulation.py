@@ -445,6 +445,28 @@ class emulator:
         self._need_dense_unsharded()
         return pathfun.PathFunctions(self, sample_size, n_features)
 
+    def sample_functions_vecchia(self, sample_size=50, n_features=2048, m=50):
+        """sample_functions by local conditioning (vpathfun, DESIGN I.14), for dense and Vecchia emulators and any number of
+        training rows: the same object, call signatures, container, column layout, noise=True term and handling of
+        likelihood nodes and a Categorical top, from the same draws in the same order (equal generator states give the
+        features, feature weights and nugget normals of sample_functions).  Each GP node's prior draw is conditioned, row by
+        row, on the m nearest training rows of the row (coordinates divided by the lengths; the imputation's latents
+        below layer 1) -- the predictor of a Vecchia emulator with Matheron's rule carried through it -- so creation keeps
+        nothing n x n and factors nothing, and a row costs O(m^3) whatever n is.  The mean of the draws is the Vecchia
+        predictive mean with conditioning sets of m for every n_features, their variance tends to its variance; with m >= n
+        the draws are sample_functions'.  A draw is a deterministic function of x (the same values at the same rows in any
+        call or split of the rows) but only piecewise smooth: it jumps where a row's nearest training rows change, by about
+        the Vecchia error, and paths.grad / paths.value_and_grad raise NotImplementedError.  A conditioning block that does
+        not factor is rebuilt with a jitter, row by row (one RuntimeWarning per evaluation call), then raises
+        numpy.linalg.LinAlgError naming its layer, node and imputation."""
+        from . import pathfun, vpathfun, vpaths
+        if self.shard or getattr(self, 'shard_points', False):
+            raise NotImplementedError("sample_paths_vecchia with the imputations sharded over ranks would return partial "
+                                      "draws; use emulator(..., shard=False)")
+        vpaths.check_m(m)
+        return pathfun.PathFunctions(self, sample_size, n_features, vpathfun.emulator_nodes(self, sample_size, n_features, m),
+                                     vpathfun.check_status)
+
     def sample_paths_vecchia(self, x, sample_size=50, full_layer=False, m=50):
         """sample_paths by the Vecchia factorisation of each node's joint predictive distribution (vpaths, DESIGN I.11):
         the same container and column layout, for dense and Vecchia emulators and any number of rows.  The rows of x are

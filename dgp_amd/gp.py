@@ -227,6 +227,20 @@ class gp:
                                       'of their own (use remove_vecchia())')
         return pathfun.GpPaths(self, sample_size, n_features)
 
+    def sample_functions_vecchia(self, sample_size=50, n_features=2048, m=50):
+        """sample_functions by local conditioning (vpathfun, DESIGN I.14), for dense and Vecchia-mode models and any n: the
+        same callable paths(x, noise=False) -> (M, sample_size), from the same draws of numpy's global generator in the same
+        order.  Each row of x is conditioned on its m nearest training rows (coordinates divided by the lengths), as
+        predict does in Vecchia mode, so nothing n x n is made: the mean of the draws is that predictor's mean with
+        conditioning sets of m for every n_features, their variance tends to its variance, and m >= n gives
+        sample_functions' draws.  The same values at the same rows in any call or split of the rows; piecewise smooth only
+        (a draw jumps where a row's nearest training rows change), so paths.grad and paths.value_and_grad raise
+        NotImplementedError.  A conditioning block that does not factor is rebuilt with a jitter (one RuntimeWarning per
+        call), then raises numpy.linalg.LinAlgError."""
+        from . import pathfun, vpaths
+        vpaths.check_m(m)
+        return pathfun.GpPaths(self, sample_size, n_features, m)
+
     def sample_paths_vecchia(self, x, sample_size=50, m=50):
         """Joint posterior draws of the GP at the rows of x by the Vecchia factorisation of the joint predictive distribution
         (vpaths): (M, sample_size) as sample_paths, for dense and Vecchia-mode models and any M.  The rows are drawn in the

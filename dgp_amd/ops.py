@@ -791,6 +791,38 @@ class Engine:
                                                           _dp(NNl), _dp(t), _dp(sd), _dp(info)))
         return Lrows, NNl, t, sd, info
 
+    def vpathfun_update(self, kind, x, w, NN, r, prior, scale, nugget, jitters, omega=None, out=None):
+        """The locally conditioned pathwise update of function-valued draws (dgpamd_vpathfun_update):
+            out = sqrt(scale) (prior + sum_j b_j r[N_j]),  b = A_N^-1 c(W_N, x),
+        N the row's neighbours NN (rows, pm) int64 (nn_query's: valid first, -1 padded), A_N their correlation block with
+        diagonal 1 + jitter + nugget * omega_j.  x and w (n, D) are coordinates divided by the lengthscales.
+        Shared rows: x (M, D), r (n, P) neighbour-major, prior (M, P); returns out (M, P) -- path fastest, the layout the
+        kernel loads and stores coalesced.  Per-path rows: x (P, M, D), r (P, n), prior (P, M); returns out (P, M).
+        jitters: the ladder tried row by row (first entry normally 0).  Returns (out, info): info 2 device int32, [0] rows
+        that needed a later rung, [1] 1 + the smallest row (p * M + i for per-path rows) that failed them all, or -1."""
+        n, D = w.shape
+        shared = x.dim() == 2
+        if shared:
+            M, P = x.shape[0], r.shape[1]
+            R, rows_per_path, shape = M, 0, (M, P)
+            assert r.shape == (n, P)
+        else:
+            P, M = x.shape[:2]
+            R, rows_per_path, shape = P * M, M, (P, M)
+            assert r.shape == (P, n)
+        assert x.shape[-1] == D and NN.shape[0] == R and NN.dim() == 2 and NN.dtype == torch.int64 and prior.shape == shape
+        assert omega is None or omega.shape == (n,)
+        for t in (x, w, NN, r, prior, omega):
+            assert t is None or (t.is_contiguous() and (t is NN or t.dtype == torch.float64))
+        jit = _f64(jitters)
+        out = self.empty(*shape) if out is None else out
+        assert out.shape == shape and out.is_contiguous()
+        info = self.empty(2, dtype=torch.int32)
+        self._chk(self._enter() or lib.dgpamd_vpathfun_update(self.h, KIND[kind], R, n, D, NN.shape[1], P, rows_per_path, _dp(x), _dp(w),
+                                                              _dp(NN), _dp(omega), _dp(r), _dp(prior), float(scale), float(nugget),
+                                                              _hp(jit), len(jit), _dp(out), _dp(info)))
+        return out, info
+
     def vecchia_gp(self, kind, x, w, NN, y, scale, length, nugget, nugget_diag):
         M, D = x.shape
         length = _f64(length)

@@ -13,6 +13,8 @@ NodePaths is the paths of one node: draw_node alone consumes the generator at cr
 build_per_group condition its draws on a training side in the form paths.Dense.draw_shared / draw_per_path take theirs.
 PathFunctions (an emulator: pathwalk.walk over its hierarchy, beside the drawers paths.Dense and vpaths.Vecchia) and GpPaths
 (one node, numpy's global generator) are built from these and evaluate in blocks of rows through one loop, _row_blocks.
+They hold node paths by interface (__call__, value_and_grad, noise_sd, Omega, m): vpathfun.VecchiaNodePaths, the update by
+local conditioning of sample_functions_vecchia (DESIGN I.14), is built from the same draws and evaluated by the same code.
 
 The input gradient of a path is as closed-form as the path (DESIGN I.13): dgpamd_pathfun_grad returns a node's values and
 its (P, M, D) gradient from one pass, and PathFunctions.value_and_grad carries the Jacobian with respect to the emulator's
@@ -97,6 +99,8 @@ class NodePaths:
     W (n, D) one training set for every path, or (G, n, D) with group (host ints (P,)) picking each path's; v (P, n).
     All its own copies.  build_*: train = (W, paths.factor_inverse's L^-1), omega (n,) or None, draws = draw_node's, all on the device."""
 
+    m = 0   # neighbours looked up per row (vpathfun.VecchiaNodePaths: its conditioning-set size; _rows_per_call's width counts them)
+
     def __init__(self, hyper, Omega, b, theta, W, v, group=None):
         kind, length, scale, nugget = hyper
         self.hyper = (kind, np.array(length, dtype=np.float64), float(scale), float(nugget))
@@ -147,6 +151,39 @@ class NodePaths:
         return np.sqrt(self.hyper[2] * self.hyper[3])
 
 
+def build_nodes(emu, sample_size, n_features, node):
+    """{(l, k): node(l, k, nd, draw)} over the emulator's GP nodes in walk order (layer by layer, node by node).  draw(D)
+    takes the node's draws from the emulator's sampling generator -- draw_node for D input columns and N * sample_size
+    paths, on the device -- and is the only thing that consumes it: every kind of node paths built from equal generator
+    states holds the same features, theta and eps."""
+    e, rng = emu.engine, emu._sample_rng
+    S, J, F = emu.N, int(sample_size), int(n_features)
+    if J < 1 or F < 1:
+        raise ValueError('sample_functions needs sample_size >= 1 and n_features >= 1')
+    nodes = {}
+    for l, layer in enumerate(emu.all_layer):
+        for k, nd in enumerate(layer):
+            if nd.type == 'gp':
+                nodes[l, k] = node(l, k, nd, lambda D, nd=nd: list(map(e.tensor, draw_node(rng, nd.name, nd.length, D, F, S, J, len(nd.output)))))
+    return nodes
+
+
+def dense_nodes(emu, sample_size, n_features):
+    """The NodePaths of a dense emulator, on its joint statistics (emu._joint_stats: L^-1 of every node and imputation)."""
+    e, S, J = emu.engine, emu.N, int(sample_size)
+
+    def node(l, k, nd, draw):
+        hyper, st = paths.hyper(nd), emu._joint_stats(l, k)
+        draws = draw((st['W'] if l == 0 else st['per'][0]['W']).shape[1])
+        omega = None if nd.rep is None else e.tensor(nd.W_diag)
+        if l == 0:
+            return NodePaths.build_shared(e, hyper, (st['W'], st['Linv']), st['Y'], omega, draws, J)
+        train = paths.PerGroup(lambda s: (st['per'][s]['W'], st['per'][s]['Linv']))
+        return NodePaths.build_per_group(e, hyper, train, paths.PerGroup(lambda s: st['per'][s]['y']), omega, draws,
+                                         np.repeat(np.arange(S), J))
+    return build_nodes(emu, J, n_features, node)
+
+
 def _row_blocks(e, x, P, width):
     """(m0, x[m0:m0 + step]) over the rows of x in order, contiguous blocks of step = _rows_per_call(e, P, width) rows."""
     if len(x) == 0:
@@ -186,34 +223,22 @@ class PathFunctions:
     x.shape[1], entry [m, d, s * sample_size + j] = d path / d x[m, d] (columns of x the model does not read: zero), or
     with full_layer a list over layers of such lists."""
 
-    def __init__(self, emu, sample_size, n_features):
-        e, rng = emu.engine, emu._sample_rng
-        S, J, F = emu.N, int(sample_size), int(n_features)
-        if J < 1 or F < 1:
-            raise ValueError('sample_functions needs sample_size >= 1 and n_features >= 1')
-        self.engine, self.rng, self.N, self.sample_size, self.n_features = e, rng, S, J, F
+    def __init__(self, emu, sample_size, n_features, nodes=None, after=None):
+        """nodes: the (layer, node) -> node paths mapping of the emulator's GP nodes (build_nodes'; None: dense_nodes, what
+        sample_functions returns); after(engine, node paths): called at the end of every paths(x) (vpathfun.check_status)."""
+        self.nodes = dense_nodes(emu, sample_size, n_features) if nodes is None else nodes
+        self.engine, self.rng, self.N, self.sample_size, self.n_features = emu.engine, emu._sample_rng, emu.N, int(sample_size), int(n_features)
         self.layers = [[copy.copy(nd) for nd in layer] for layer in emu.all_layer]
-        self.nodes = {}
-        for l, layer in enumerate(emu.all_layer):
-            for k, nd in enumerate(layer):
-                if nd.type != 'gp':
-                    continue
-                hyper, st = paths.hyper(nd), emu._joint_stats(l, k)
-                D = (st['W'] if l == 0 else st['per'][0]['W']).shape[1]
-                draws = list(map(e.tensor, draw_node(rng, nd.name, nd.length, D, F, S, J, len(nd.output))))
-                omega = None if nd.rep is None else e.tensor(nd.W_diag)
-                if l == 0:
-                    self.nodes[l, k] = NodePaths.build_shared(e, hyper, (st['W'], st['Linv']), st['Y'], omega, draws, J)
-                else:
-                    train = paths.PerGroup(lambda s: (st['per'][s]['W'], st['per'][s]['Linv']))
-                    y = paths.PerGroup(lambda s: st['per'][s]['y'])
-                    self.nodes[l, k] = NodePaths.build_per_group(e, hyper, train, y, omega, draws, np.repeat(np.arange(S), J))
+        self.after = after
 
     def __call__(self, x, full_layer=False, noise=False):
         paths.check_2d(x)
         e, P = self.engine, self.N * self.sample_size
-        width = 4 * max(len(layer) for layer in self.layers) + 3 * max(nf.Omega.shape[1] for nf in self.nodes.values()) + 4
+        width = 4 * max(len(layer) for layer in self.layers) + 3 * max(nf.Omega.shape[1] for nf in self.nodes.values()) + 4 + \
+            max(nf.m for nf in self.nodes.values())
         out = _join(self._block(xb, noise=noise)[0] for _, xb in _row_blocks(e, x, P, width))
+        if self.after is not None:
+            self.after(e, self.nodes.values())
         out = [list(a.transpose(2, 1, 0)) for a in out]
         return out if full_layer else out[-1]
 
@@ -300,26 +325,36 @@ class GpPaths:
     paths.value_and_grad(x) -> ((M, sample_size), (M, Dx, sample_size)) and paths.grad(x) -> (M, Dx, sample_size), Dx =
     x.shape[1]: entry [m, d, j] = d draw j at row m / d x[m, d], zero in the columns of x that the GP does not read."""
 
-    def __init__(self, model, sample_size, n_features):
+    def __init__(self, model, sample_size, n_features, m=None):
+        """m None: the dense draws of sample_functions; else sample_functions_vecchia's, conditioned on the m nearest training
+        rows (vpathfun.VecchiaNodePaths: no factor of the training correlation matrix is made)."""
         k = model.kernel
         e = k.engine
         J, F = int(sample_size), int(n_features)
         if J < 1 or F < 1:
             raise ValueError('sample_functions needs sample_size >= 1 and n_features >= 1')
-        train = model._joint_train()
+        omega = None if k.rep is None else e.tensor(k.W_diag)
+        train = model._joint_train() if m is None else (e.tensor(k._X()), omega)
         n, D = train[0].shape
         draws = list(map(e.tensor, draw_node(np.random, k.name, k.length, D, F, 1, J, n)))
         y = e.tensor(np.asarray(k.output, float).reshape(1, -1))
-        omega = None if k.rep is None else e.tensor(k.W_diag)
         self.engine, self.sample_size, self.columns = e, J, model._columns()
         self.input_dim, self.connect = np.array(k.input_dim), None if k.connect is None else np.array(k.connect)
-        self.node = NodePaths.build_shared(e, paths.hyper(k), train, y, omega, draws, J)
+        if m is None:
+            self.node = NodePaths.build_shared(e, paths.hyper(k), train, y, omega, draws, J)
+        else:
+            from . import vpathfun
+            self.node = vpathfun.VecchiaNodePaths.build_shared(e, paths.hyper(k), train, y, draws, J, m, 'the gp model')
 
     def __call__(self, x, noise=False):
         paths.check_2d(x)
         e, J = self.engine, self.sample_size
         xin = x[:, self.columns]
-        out = np.concatenate([self.node(e, e.tensor(xb)).cpu().numpy().T for _, xb in _row_blocks(e, xin, J, 2 + xin.shape[1])], 0)
+        out = np.concatenate([self.node(e, e.tensor(xb)).cpu().numpy().T
+                              for _, xb in _row_blocks(e, xin, J, 2 + xin.shape[1] + self.node.m)], 0)
+        if self.node.m:
+            from . import vpathfun
+            vpathfun.check_status(e, [self.node])
         if noise:
             out = out + self.node.noise_sd() * np.random.standard_normal((J, len(x))).T
         return out

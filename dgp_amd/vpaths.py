@@ -17,11 +17,15 @@ import torch
 from .paths import JITTERS, check_2d
 
 
+def check_m(m):
+    if int(m) < 1:
+        raise ValueError('sample_paths_vecchia: the conditioning-set size m must be at least 1 (got %r)' % (m,))
+
+
 def check_args(x, m):
     """sample_paths' refusal of a non-2-D x, and m >= 1 (before anything touches the device)."""
     check_2d(x)
-    if int(m) < 1:
-        raise ValueError('sample_paths_vecchia: the conditioning-set size m must be at least 1 (got %r)' % (m,))
+    check_m(m)
 
 
 def _scaled(t, length):

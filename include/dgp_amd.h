@@ -614,6 +614,32 @@ int dgpamd_pathfun_grad(dgpamd_ctx *ctx, int kind, int64_t n, int64_t M, int D, 
                         const double *Omega, const double *b, const double *theta, const double *v,
                         const double *length_h, int nlen, double scale, double *out, double *out_g);
 
+/* ---- function-valued posterior draws by local conditioning (DESIGN I.14) -----------------------------------
+ * The pathwise update of a draw through the Vecchia predictor (gp_vecch, vecchia.py:635-654) in place of the dense
+ * c(x, W) R^-1 r.  One GP node, R rows.  Row i conditions on N(i), its neighbours NN[i] (R x pm, the valid entries first, -1
+ * padded: dgpamd_nn_query's) among the n training rows; with A the correlation block over N(i), diagonal 1 + jitter +
+ * nugget * omega_j (omega NULL: 1), and a = c(W_N, x_i):
+ *   b_i = A^-1 a,    out = sqrt(scale) (prior + sum_j b_ij r[N_j]).
+ * x (R x D) and w (n x D) are coordinates already divided by the lengthscales; prior is dgpamd_pathfun_eval's n = 0 result
+ * at scale 1; r the path's residual y / sqrt(scale) - Phi(W) theta - sqrt(nugget omega) * eps.
+ *   rows_per_path == 0  shared rows: every row serves all P paths and its block is factored once.  r is NEIGHBOUR-MAJOR
+ *       (n x P) and prior and out are ROW-MAJOR OVER PATHS (R x P): the lanes run over the paths, so the 64 residuals of a
+ *       training row and the 64 outputs of a row are consecutive doubles (coalesced loads and stores).
+ *   rows_per_path = M   per-path rows: R = P * M, row i belongs to path i / M; r is (P x n), prior and out are (P x M).
+ *       One call holds one training set: a caller with several (groups of paths) makes one call per group.
+ * jitter_h: the ladder of njitter (1 to 4) host doubles, tried in order ROW BY ROW: a block with a non-positive pivot or
+ * Schur complement is rebuilt with the next rung by the wave that owns it, so a row's result never depends on the rows that
+ * share its call.  info (2 device int32): [0] the number of rows that needed a rung beyond the first; [1] 1 + the smallest
+ * row index whose block failed every rung, -1 when none did (an unsigned atomic minimum: deterministic).
+ * out is one chain  acc = prior; acc = fma(b_ij, r[N_j], acc), j in list order; out = sqrt(scale) acc  in either form: the
+ * same row gives the same bits in any call, block or position.  pm <= 51 with D <= 16 runs register-resident (one wave per
+ * row, four per workgroup); otherwise one wave per row with the block in LDS, and a block over a CU's 160 KiB returns
+ * DGPAMD_BAD_ARG before anything is launched.  DGPAMD_VECCHIA_LDS=1 forces the LDS kernel. */
+int dgpamd_vpathfun_update(dgpamd_ctx *ctx, int kind, int64_t R, int64_t n, int D, int pm, int64_t P, int64_t rows_per_path,
+                           const double *x, const double *w, const int64_t *NN, const double *omega, const double *r,
+                           const double *prior, double scale, double nugget, const double *jitter_h, int njitter,
+                           double *out, int32_t *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,12 @@ for comparing builds of the library through DGPAMD_LIB).
 --grad: the input gradients alone (profiles/pathgrad_bench.txt; DESIGN I.13), F = 2048: at M = 1000, 8192 and 100 000 three
 alternating rounds of paths(x), paths.value_and_grad(x) and the forward-difference alternative (paths at x and at x + h e_d,
 d + 1 = 6 calls); then dgpamd_pathfun_grad against dgpamd_pathfun_eval by device events at M = 100 000 on a first-layer node
-(shared rows) and the output node (per-path rows)."""
+(shared rows) and the output node (per-path rows).
+--vecchia: the draws by local conditioning (profiles/vpathfun_bench.txt; DESIGN I.14), F = 2048, m = 50: (a) the bench model in
+Vecchia mode -- creating sample_functions_vecchia's paths, then at M = 1000, 8192 and 100 000 three alternating rounds of their
+paths(x), sample_paths_vecchia on the same rows, and paths(x) of sample_functions made before the emulator left dense mode;
+(b) a gp of configs[4]'s shape (n = 50 000, d = 8, Vecchia mode), 100 paths at M = 100 000; (c) dgpamd_vpathfun_update alone by
+device events, shared rows, 100 paths at those rows, against 100 calls of dgpamd_vecchia_gp on the same conditioning sets."""
 import os
 import sys
 import time
@@ -98,6 +103,61 @@ def grad_arm(emu, e, xs, N, J, n, rng):
               % ('shared' if shared else 'per-path', nf.hyper[0], P, n, F, M, D, times[0], times[1], times[1] / times[0], D + 1))
 
 
+def device_ms(e, f, reps=3):
+    f()
+    ev0, ev1 = e.event(), e.event()
+    e.record(ev0)
+    for _ in range(reps):
+        f()
+    e.record(ev1)
+    return e.elapsed_ms(ev0, ev1) / reps
+
+
+def vecchia_arm(emu, xs, N, J, m, rng):
+    from dgp_amd import gp, kernel
+    P, F = N * J, 2048
+    dense = emu.sample_functions(sample_size=J, n_features=F)   # (made while the emulator is dense: it keeps its own copies)
+    emu.to_vecchia()
+    for label in ('first', 'second'):
+        pv, ms = timed(lambda: emu.sample_functions_vecchia(sample_size=J, n_features=F, m=m))
+        print('(a) sample_functions_vecchia(sample_size=%d, n_features=%d, m=%d): creating %d paths, %-6s call %9.1f ms'
+              % (J, F, m, P, label, ms))
+    for M in (1000, 8192, 100000):
+        x = xs[M]
+        legs = [('sample_functions_vecchia: paths(x)', lambda: pv(x)),
+                ('sample_paths_vecchia', lambda: emu.sample_paths_vecchia(x, sample_size=J, m=m)),
+                ('sample_functions (dense): paths(x)', lambda: dense(x))]
+        for name, f in legs:   # warm every shape
+            out = f()
+            assert out[0].shape == (M, P) and np.all(np.isfinite(out[0]))
+        for rnd in range(3):   # alternating: each round times every method once
+            for name, f in legs:
+                _, ms = timed(f)
+                print('(a) M = %6d, %d paths, round %d: %-36s %10.1f ms' % (M, P, rnd + 1, name, ms))
+    n4, d4, M, P = 50000, 8, 100000, 100
+    X4 = rng.uniform(size=(n4, d4))
+    Y4 = (np.sin(X4.sum(1)) + 0.05 * rng.normal(size=n4))[:, None]
+    model = gp(X4, Y4, kernel(length=np.full(d4, 0.5), name='matern2.5', scale=1.0, nugget=1e-4), vecchia=True, m=m)
+    paths, ms = timed(lambda: model.sample_functions_vecchia(sample_size=P, n_features=F, m=m))
+    print('(b) gp n = %d, d = %d: sample_functions_vecchia(sample_size=%d, n_features=%d, m=%d) %9.1f ms' % (n4, d4, P, F, m, ms))
+    x4 = rng.uniform(size=(M, d4))
+    for label in ('first', 'second', 'third'):
+        out, ms = timed(lambda: paths(x4))
+        assert out.shape == (M, P) and np.all(np.isfinite(out))
+        print('(b) paths(x), M = %d, %d paths: %-6s call %9.1f ms' % (M, P, label, ms))
+    k = model.kernel
+    e, nf = k.engine, paths.node
+    t = e.tensor
+    xs4, xd, Wd = t(x4 / k.length), t(x4), t(k._X())
+    NN = e.nn_query(xs4, nf.Ws, m)
+    prior, y, ones = e.zeros(M, P), t(Y4[:, 0]), t(np.ones(n4))
+    one = device_ms(e, lambda: e.vpathfun_update(k.name, xs4, nf.Ws, NN, nf.r, prior, k.scale[0], k.nugget[0], (0.0, 1e-10, 1e-8)))
+    many = device_ms(e, lambda: [e.vecchia_gp(k.name, xd, Wd, NN, y, k.scale[0], k.length, k.nugget[0], ones) for _ in range(P)])
+    print('(c) shared rows, %s, M = %d, pm = %d, D = %d, %d paths: dgpamd_vpathfun_update %.2f ms; %d calls of dgpamd_vecchia_gp %.2f ms '
+          '(%.2f ms each): one launch / %d calls = %.3f' % (k.name, M, m, d4, P, one, P, many, many / P, P, one / many))
+    assert one < many, 'the one launch must be faster than the calls it replaces'
+
+
 def main():
     import bench
     from dgp_amd import emulator
@@ -112,6 +172,8 @@ def main():
     emu.sample_paths(xs[1000], sample_size=J)   # (the lazily built statistics are shared by every method below)
     if '--grad' in sys.argv:
         return grad_arm(emu, e, xs, N, J, n, rng)
+    if '--vecchia' in sys.argv:
+        return vecchia_arm(emu, xs, N, J, m, rng)
     pfs = {}
     for F in ((2048,) if big_only else (2048, 8192)):
         for label in ('first', 'second'):
