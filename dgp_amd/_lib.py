@@ -123,6 +123,9 @@ SIGNATURES = {
     'dgpamd_pathfun_eval': (_i, [_p, _i, _l, _l, _i, _l, _i, _p, _l, _p, _i, _p, _l, _p, _p, _p, _p, _p, _i, _d, _p]),
     'dgpamd_pathfun_grad': (_i, [_p, _i, _l, _l, _i, _l, _i, _p, _l, _p, _i, _p, _l, _p, _p, _p, _p, _p, _i, _d, _p, _p]),
     'dgpamd_vpathfun_update': (_i, [_p, _i, _l, _l, _i, _i, _l, _l, _p, _p, _p, _p, _p, _p, _d, _d, _p, _i, _p, _p]),
+    'dgpamd_mixture_eval': (_i, [_p, _i, _i, _l, _i, _p, _p, _p, _l, _p]),
+    'dgpamd_mixture_quantile': (_i, [_p, _i, _l, _i, _p, _p, _p, _p, _i, _p, _p]),
+    'dgpamd_mixture_crps': (_i, [_p, _i, _l, _p, _p, _p, _i, _p]),
 }
 
 MISSING = []

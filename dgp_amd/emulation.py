@@ -330,6 +330,33 @@ class emulator:
     def _mode(self):
         return 'vecchia' if self.vecch else 'dense'
 
+    def _dist_refusals(self, what):
+        """What predict_dist and loo_dist refuse: a final layer whose predictive distribution is no mixture of Gaussians, and
+        imputations spread over ranks (each rank would build the mixture of its own share)."""
+        if self._cat() is not None or any(nd.type == 'likelihood' for nd in self.all_layer[-1]):
+            raise ValueError('%s: with a likelihood node in the final layer the predictive distribution is not a mixture of '
+                             "Gaussians; draw from it with predict(method='sampling')" % what)
+        if self.shard or getattr(self, 'shard_points', False):
+            raise NotImplementedError("with the imputations sharded over ranks %s() would return a partial mixture; "
+                                      "use emulator(..., shard=False)" % what)
+
+    def predict_dist(self, x, m=50):
+        """The predictive distribution itself at the rows of x: the equal-weight mixture of the N imputations' Gaussians as a
+        mixture.PredictiveMixture -- mean() and var() are predict(x)'s, bit for bit; cdf, sf, logpdf, quantile, interval and crps
+        are evaluated exactly on the device (DESIGN I.15).  Dense and Vecchia-mode emulators (m: the conditioning-set size);
+        GP hierarchies only: a likelihood node or a Categorical top raises ValueError."""
+        from . import mixture
+        mixture.check_points(x)
+        self._dist_refusals('predict_dist')
+        return mixture.PredictiveMixture(self.engine, *self._layer_moments(x, self._mode(), m)[-1])
+
+    def loo_dist(self, X, m=30):
+        """loo(X)'s leave-one-out predictive distributions as a mixture.PredictiveMixture (one row per row of X, replicated rows
+        as loo returns them): PIT values are cdf(Y), interval coverage and the leave-one-out CRPS one call each."""
+        from . import mixture
+        self._dist_refusals('loo_dist')
+        return mixture.PredictiveMixture(self.engine, *self._loo_moments(X, m)[-1])
+
     def _host_moments(self, x, m):
         """_layer_moments in the emulator's own mode as numpy arrays (metric, nllik)."""
         return _host(self._layer_moments(x, self._mode(), m))
@@ -612,19 +639,32 @@ class emulator:
         through the rank-one downdate of `_node_dense(loo=True)`."""
         if method is None:
             method = 'mean_var'
-        n_train = len(self.all_layer[0][0].input)
-        isrep = len(X) != n_train
-        if isrep:
-            X, indices = np.unique(X, return_inverse=True, axis=0)
-        if not self.vecch:
-            per_layer = self._layer_moments(X, 'loo')
-        else:
-            with self.change_vecch_state():
-                per_layer = self._layer_moments(X, 'vecchia', m + 1)
+        per_layer, indices = self._loo_walk(X, m)
         res = self._draw_samples(_host(per_layer), sample_size, False) if method == 'sampling' else self._aggregate(per_layer)
-        if isrep:
-            res = type(res)(item[np.asarray(indices).reshape(-1), :] for item in res)
+        if indices is not None:
+            res = type(res)(item[indices, :] for item in res)
         return res
+
+    def _loo_walk(self, X, m):
+        """loo's layer walk: the per-layer moments at the distinct rows of X, and for an X with replicated rows the index of
+        each of its rows among them (else None)."""
+        n_train = len(self.all_layer[0][0].input)
+        indices = None
+        if len(X) != n_train:
+            X, indices = np.unique(X, return_inverse=True, axis=0)
+            indices = np.asarray(indices).reshape(-1)
+        if not self.vecch:
+            return self._layer_moments(X, 'loo'), indices
+        with self.change_vecch_state():
+            return self._layer_moments(X, 'vecchia', m + 1), indices
+
+    def _loo_moments(self, X, m):
+        """_loo_walk's moments with the replicated rows put back: per layer (mean, var), (S, len(X), K) device tensors."""
+        per_layer, indices = self._loo_walk(X, m)
+        if indices is None:
+            return per_layer
+        idx = torch.as_tensor(indices, device=self.engine.device)
+        return [(a[:, idx], b[:, idx]) for a, b in per_layer]
 
     def ploo(self, X, method=None, sample_size=50, m=30, core_num=None):
         """emulation.py:146-168 (`core_num` is accepted and unused)."""

@@ -175,6 +175,15 @@ class gp:
             return np.random.normal(mu, np.sqrt(s2), size=(sample_size, len(x))).T
         raise Exception("method must be 'mean_var' or 'sampling'.")
 
+    def predict_dist(self, x, m=50):
+        """predict(x)'s Gaussians as a mixture.PredictiveMixture of one component (M points, one output): cdf, sf, logpdf,
+        quantile, interval and crps of the predictive distribution, evaluated on the device (DESIGN I.15)."""
+        from . import mixture
+        mixture.check_points(x)
+        e = self.kernel.engine
+        mu, s2 = self.predict(x, m=m)
+        return mixture.PredictiveMixture(e, e.tensor(mu[None]), e.tensor(s2[None]))
+
     def sample_paths(self, x, sample_size=50):
         """Joint posterior draws of the GP at the rows of x: (M, sample_size), each column one draw over all M rows
         (predict(method='sampling') draws every row on its own).  The normals come from numpy's global generator,

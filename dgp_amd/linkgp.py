@@ -10,7 +10,7 @@ import copy
 import numpy as np
 import torch
 
-from . import paths, pathwalk
+from . import mixture, paths, pathwalk
 from .imputation import imputer
 from .kernel_class import peek
 
@@ -276,13 +276,11 @@ class lgp:
             raise Exception('local_input_idx should be a list that has length of %i.' % l)
         return idx
 
-    def predict(self, x, method='mean_var', full_layer=False, sample_size=50, m=50):
-        """Means and variances of the final-layer emulators' outputs (lists of (M x q) arrays), or of every
-        layer if full_layer (linkgp.py:285-501); method='sampling': per emulator an array (q, M, N * sample_size) of
-        draws from the imputations' predictive distributions."""
-        if method not in ('mean_var', 'sampling'):
-            raise Exception("method must be either 'mean_var' or 'sampling'.")
-        sampling = method == 'sampling'
+    def _system_moments(self, x, m, full_layer=False, sample_size=None):
+        """The walk through every system (imputation) of the set: per system the (M x q) means and variances of the final
+        layer's emulators -- of every layer's with full_layer -- and with a sample_size the draws from them (else empty
+        lists).  predict aggregates these; predict_dist keeps them as the components of the mixtures."""
+        sampling = sample_size is not None
         x = self._global_inputs(x)
         means, variances, draws = [], [], []
         for one in self.all_layer_set:
@@ -310,16 +308,23 @@ class lgp:
             means.append(lay_m if full_layer else lay_m[-1])
             variances.append(lay_v if full_layer else lay_v[-1])
             draws.append(lay_s if full_layer else lay_s[-1])
+        return means, variances, draws
+
+    def predict(self, x, method='mean_var', full_layer=False, sample_size=50, m=50):
+        """Means and variances of the final-layer emulators' outputs (lists of (M x q) arrays), or of every
+        layer if full_layer (linkgp.py:285-501); method='sampling': per emulator an array (q, M, N * sample_size) of
+        draws from the imputations' predictive distributions."""
+        if method not in ('mean_var', 'sampling'):
+            raise Exception("method must be either 'mean_var' or 'sampling'.")
+        sampling = method == 'sampling'
+        means, variances, draws = self._system_moments(x, m, full_layer, sample_size if sampling else None)
         if sampling:    # per emulator (q, M, S * sample_size): the imputations' draws side by side (linkgp.py:496-500)
             if full_layer:
                 return [[np.concatenate([draws[s_][l][k] for s_ in range(len(draws))], axis=2)
                          for k in range(len(self.all_layer[l]))] for l in range(self.L)]
             return [np.concatenate([draws[s_][k] for s_ in range(len(draws))], axis=2) for k in range(len(self.all_layer[-1]))]
 
-        def agg(ms, vs):   # emulation.py:846-847 over the imputations
-            ms, vs = np.asarray(ms), np.asarray(vs)
-            mu = ms.mean(0)
-            return mu, (ms ** 2 + vs).mean(0) - mu ** 2
+        agg = mixture.host_moments   # emulation.py:846-847 over the imputations
         if full_layer:
             out = [[agg([means[s][l][k] for s in range(len(means))], [variances[s][l][k] for s in range(len(means))])
                     for k in range(len(self.all_layer[l]))] for l in range(self.L)]
@@ -327,6 +332,24 @@ class lgp:
         out = [agg([means[s][k] for s in range(len(means))], [variances[s][k] for s in range(len(means))])
                for k in range(len(self.all_layer[-1]))]
         return [o[0] for o in out], [o[1] for o in out]
+
+    def predict_dist(self, x, m=50):
+        """The predictive distributions of the final-layer emulators' outputs at the rows of x: a list over those emulators of
+        mixture.PredictiveMixture, each the equal-weight mixture of the N systems' Gaussians (M points x q outputs) -- mean()
+        and var() are predict(x)'s; cdf, sf, logpdf, quantile, interval and crps are evaluated on the device (DESIGN I.15).
+        A final emulator that ends in a likelihood node raises ValueError: its predictive distribution is no mixture of
+        Gaussians (draw from it with predict(method='sampling'))."""
+        for c in self.all_layer[-1]:
+            if c.type == 'dgp' and any(nd.type == 'likelihood' for nd in c.structure[-1]):
+                raise ValueError('predict_dist: with a likelihood node on top of a final emulator the predictive distribution is '
+                                 "not a mixture of Gaussians; draw from it with predict(method='sampling')")
+        means, variances, _ = self._system_moments(x, m)
+        out = []
+        for k, c in enumerate(self.all_layer_set[0][-1]):
+            e = (c.structure if c.type == 'gp' else c.structure[0][0]).engine
+            out.append(mixture.PredictiveMixture(e, e.tensor(np.stack([ms[k] for ms in means])),
+                                                 e.tensor(np.stack([vs[k] for vs in variances])), host_moments=True))
+        return out
 
     # -------------------------------------------------------------- joint sample paths
     def sample_paths(self, x, sample_size=50, full_layer=False):

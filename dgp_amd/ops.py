@@ -636,6 +636,64 @@ class Engine:
     def moments_finalize(self, S, sum_mu, sum_m2):
         self._chk(self._enter() or lib.dgpamd_moments_finalize(self.h, sum_mu.numel(), float(S), _dp(sum_mu), _dp(sum_m2)))
 
+    # --------------------------------------------------------------- predictive mixture (csrc/mixture.hip)
+    MIX_WHAT = dict(cdf=0, sf=1, logpdf=2)
+    MIX_PATH = {None: 0, 'lds': 1, 'global': 2}
+    MIX_MAXT = 32
+
+    @staticmethod
+    def _mix_components(mu, var):
+        if mu.dim() != 2 or mu.shape != var.shape or mu.dtype != torch.float64 or var.dtype != torch.float64:
+            raise ValueError('mixture: mu and var must be float64 tensors of one shape (S, count)')
+        if mu.shape[0] < 1:
+            raise ValueError('mixture: at least one component is needed')
+        return mu.contiguous(), var.contiguous(), mu.shape[0], mu.shape[1]
+
+    def mixture_eval(self, what, mu, var, y):
+        """cdf / sf / logpdf (what: a key of Engine.MIX_WHAT) of the equal-weight mixtures of the S Gaussians N(mu[s, e], var[s, e]),
+        e < count, at y: (count, T) one row of thresholds per entry, or (T,) thresholds shared by all entries.  Returns (count, T)."""
+        mu, var, S, count = self._mix_components(mu, var)
+        if y.dtype != torch.float64 or not (y.dim() == 1 or (y.dim() == 2 and y.shape[0] == count)) or y.shape[-1] < 1:
+            raise ValueError('mixture: y must be a float64 tensor (count, T) or (T,), T >= 1')
+        y = y.contiguous()
+        T = y.shape[-1]
+        out = self.empty(count, T)
+        self._chk(self._enter() or lib.dgpamd_mixture_eval(self.h, self.MIX_WHAT[what], S, count, T, _dp(mu), _dp(var), _dp(y),
+                                                          T if y.dim() == 2 else 0, _dp(out)))
+        return out
+
+    def mixture_quantile(self, mu, var, p, path=None):
+        """out[e, t] = inf{q : F_e(q) >= p[t]} of the same mixtures; p: 1-d host array of probabilities in (0, 1).  Returns
+        ((count, T) tensor, the number of results that reached the kernel's iteration limit -- expected 0).  path: None (the
+        size of S decides), 'lds' or 'global' -- which of the two kernels runs (the same arithmetic)."""
+        from scipy.special import ndtri
+        mu, var, S, count = self._mix_components(mu, var)
+        p = _f64(p)
+        if p.size < 1 or not np.all((p > 0.0) & (p < 1.0)):
+            raise ValueError('mixture: the probabilities must lie in (0, 1)')
+        zp = np.ascontiguousarray(ndtri(p))
+        out, info = self.empty(count, p.size), self.zeros(1, dtype=torch.int32)
+        capped = 0
+        for t0 in range(0, p.size, self.MIX_MAXT):
+            T = min(self.MIX_MAXT, p.size - t0)
+            part = out if T == p.size else self.empty(count, T)
+            self._chk(self._enter() or lib.dgpamd_mixture_quantile(self.h, S, count, T, _dp(mu), _dp(var), _hp(p[t0:t0 + T]),
+                                                                  _hp(zp[t0:t0 + T]), self.MIX_PATH[path], _dp(part), _dp(info)))
+            if part is not out:
+                out[:, t0:t0 + T] = part
+            capped += int(self.fetch(info)[0]) if count else 0
+        return out, capped
+
+    def mixture_crps(self, mu, var, y, path=None):
+        """CRPS of the same mixtures at the observations y (count,).  Returns (count,).  path as mixture_quantile's."""
+        mu, var, S, count = self._mix_components(mu, var)
+        if y.dtype != torch.float64 or y.dim() != 1 or y.shape[0] != count:
+            raise ValueError('mixture: y must be a float64 tensor (count,)')
+        y = y.contiguous()
+        out = self.empty(count)
+        self._chk(self._enter() or lib.dgpamd_mixture_crps(self.h, S, count, _dp(mu), _dp(var), _dp(y), self.MIX_PATH[path], _dp(out)))
+        return out
+
     # --------------------------------------------------------------- vecchia
     def nn_ordered(self, x, m):
         n, D = x.shape

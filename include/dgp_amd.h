@@ -640,6 +640,40 @@ int dgpamd_vpathfun_update(dgpamd_ctx *ctx, int kind, int64_t R, int64_t n, int 
                            const double *prior, double scale, double nugget, const double *jitter_h, int njitter,
                            double *out, int32_t *info);
 
+/* ---- the exact predictive distribution: an equal-weight mixture of S Gaussians per point-output (DESIGN I.15) ----
+ * mu, var: (S x count) device doubles, count = M * K point-outputs, component s of entry e at [s * count + e] (the layout of
+ * the layer walk's per-imputation moments); weights 1 / S.  A component with var <= 0 is a point mass at mu: its cdf is the
+ * right-continuous step 1{y >= mu}, it has no density term, and the log density is -inf where no component has var > 0.
+ * With x_s = (y - mu_s) / sqrt(2 var_s):
+ *   DGPAMD_MIX_CDF     out = (1/S) sum_s erfc(-x_s) / 2
+ *   DGPAMD_MIX_SF      out = (1/S) sum_s erfc(+x_s) / 2           (summed from the upper tails, not 1 - cdf)
+ *   DGPAMD_MIX_LOGPDF  out = log (1/S) sum_s exp(-x_s^2) / sqrt(2 pi var_s), a log-sum-exp with the maximum taken first
+ * y: thresholds per entry (count x T, y_stride = T) or shared by all entries (T, y_stride = 0); out (count x T).
+ * dgpamd_mixture_quantile: out[e, t] = inf{q : F_e(q) >= p[t]}.  p and zp (the standard normal quantiles of p) are T HOST
+ * doubles, T <= DGPAMD_MIX_MAXT, 0 < p < 1.  Start bracket [min_s, max_s] of mu_s + zp sigma_s; Newton steps on the log of
+ * the smaller tail (lower for p <= 1/2, upper above) taken only inside the bracket, else its midpoint; stops when the
+ * bracket is 2^-52 max(|q|, max_s |mu_s|) wide, after at most 400 iterations.  info (1 device int32): the number of (e, t)
+ * that reached the iteration limit (expected 0).  With S = 1, or S equal components, out = fma(zp, sqrt(var), mu).
+ * dgpamd_mixture_crps: with A(m, v) = 2 sqrt(v) phi(m / sqrt(v)) + m (2 Phi(m / sqrt(v)) - 1), A(m, 0) = |m|,
+ *   out[e] = (1/S) sum_s A(y_e - mu_s, var_s) - (1 / 2S^2) [sum_s A(0, 2 var_s) + 2 sum_{s<t} A(mu_s - mu_t, var_s + var_t)],
+ * y, out: count doubles.
+ * Every output is one fixed sequence of operations on its own entry's components: any slice of a call gives the same bits.
+ * path (quantile, crps): 0 -- the kernel that stages an entry's components in LDS (64 entries x S x 2 doubles per wave)
+ * while eight such waves fit a CU (S <= 20), the one that re-reads global memory above that; 1 / 2 ask for the LDS kernel
+ * (S <= 160) / the global kernel: the same arithmetic on the same numbers.  count = 0 returns DGPAMD_OK without a launch.  DGPAMD_BAD_ARG before any launch: S < 1,
+ * T < 1, a p outside (0, 1), a null pointer.  (mu is device memory: a NaN in it is refused by the Python front,
+ * PredictiveMixture; the kernels pass it through as NaN and never loop on it.) */
+#define DGPAMD_MIX_CDF 0
+#define DGPAMD_MIX_SF 1
+#define DGPAMD_MIX_LOGPDF 2
+#define DGPAMD_MIX_MAXT 32
+int dgpamd_mixture_eval(dgpamd_ctx *ctx, int what, int S, int64_t count, int T, const double *mu, const double *var,
+                        const double *y, int64_t y_stride, double *out);
+int dgpamd_mixture_quantile(dgpamd_ctx *ctx, int S, int64_t count, int T, const double *mu, const double *var,
+                            const double *p, const double *zp, int path, double *out, int32_t *info);
+int dgpamd_mixture_crps(dgpamd_ctx *ctx, int S, int64_t count, const double *mu, const double *var, const double *y,
+                        int path, double *out);
+
 #ifdef __cplusplus
 }
 #endif
