@@ -126,6 +126,8 @@ SIGNATURES = {
     'dgpamd_mixture_eval': (_i, [_p, _i, _i, _l, _i, _p, _p, _p, _l, _p]),
     'dgpamd_mixture_quantile': (_i, [_p, _i, _l, _i, _p, _p, _p, _p, _i, _p, _p]),
     'dgpamd_mixture_crps': (_i, [_p, _i, _l, _p, _p, _p, _i, _p]),
+    'dgpamd_sobol_tiles': (_i, [_p, _l, _l, _i, _p, _p, _p, _p, _p]),
+    'dgpamd_sobol_add': (_i, [_p, _l, _l, _p, _p]),
 }
 
 MISSING = []

@@ -494,6 +494,22 @@ class emulator:
         return pathfun.PathFunctions(self, sample_size, n_features, vpathfun.emulator_nodes(self, sample_size, n_features, m),
                                      vpathfun.check_status)
 
+    def sobol(self, bounds, n_base=4096, sample_size=20, n_features=2048, seed=None, qmc=False, m=50):
+        """Sobol' sensitivity indices of the emulated function over the box bounds (Dx, 2), with their posterior
+        uncertainty (sensitivity, DESIGN I.16): draws N * sample_size functions -- sample_functions for a dense emulator,
+        sample_functions_vecchia(m=m) for one in Vecchia mode, with their refusals -- makes the base samples
+        sensitivity.saltelli_design(bounds, n_base, seed, qmc) and returns paths.sobol(A, B), a sensitivity.SobolResult:
+        first and total (K, Dx, N * sample_size), one first-order and one total-order index per output, input and draw;
+        result.summary() gives their means and intervals over the draws.  Emulators of GP nodes only (ValueError)."""
+        from . import pathfun, sensitivity
+        pathfun.check_pick_freeze(self.all_layer)
+        A, B = sensitivity.saltelli_design(bounds, n_base, seed, qmc)
+        if self.vecch:
+            fun = self.sample_functions_vecchia(sample_size, n_features, m)
+        else:
+            fun = self.sample_functions(sample_size, n_features)
+        return fun.sobol(A, B)
+
     def sample_paths_vecchia(self, x, sample_size=50, full_layer=False, m=50):
         """sample_paths by the Vecchia factorisation of each node's joint predictive distribution (vpaths, DESIGN I.11):
         the same container and column layout, for dense and Vecchia emulators and any number of rows.  The rows of x are

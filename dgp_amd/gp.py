@@ -250,6 +250,20 @@ class gp:
         vpaths.check_m(m)
         return pathfun.GpPaths(self, sample_size, n_features, m)
 
+    def sobol(self, bounds, n_base=4096, sample_size=20, n_features=2048, seed=None, qmc=False, m=50):
+        """Sobol' sensitivity indices of the GP over the box bounds (Dx, 2), with their posterior uncertainty (sensitivity,
+        DESIGN I.16): draws sample_size functions -- sample_functions in dense mode, sample_functions_vecchia(m=m) in
+        Vecchia mode -- makes the base samples sensitivity.saltelli_design(bounds, n_base, seed, qmc) and returns
+        paths.sobol(A, B), a sensitivity.SobolResult with first and total (Dx, sample_size); result.summary() gives their
+        means and intervals over the draws."""
+        from . import sensitivity
+        A, B = sensitivity.saltelli_design(bounds, n_base, seed, qmc)
+        if self.vecch:
+            fun = self.sample_functions_vecchia(sample_size, n_features, m)
+        else:
+            fun = self.sample_functions(sample_size, n_features)
+        return fun.sobol(A, B)
+
     def sample_paths_vecchia(self, x, sample_size=50, m=50):
         """Joint posterior draws of the GP at the rows of x by the Vecchia factorisation of the joint predictive distribution
         (vpaths): (M, sample_size) as sample_paths, for dense and Vecchia-mode models and any M.  The rows are drawn in the

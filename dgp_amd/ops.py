@@ -694,6 +694,32 @@ class Engine:
         self._chk(self._enter() or lib.dgpamd_mixture_crps(self.h, S, count, _dp(mu), _dp(var), _dp(y), self.MIX_PATH[path], _dp(out)))
         return out
 
+    # --------------------------------------------------------------- pick-freeze sums (csrc/sobol.hip)
+    def sobol_tiles(self, fA, fB, fAB, shift):
+        """The per-tile pick-freeze sums of dgpamd_sobol_tiles.  fA, fB, fAB: (P, M, K) float64 device tensors, the paths at the
+        rows of A, B and AB_i; shift (P, K).  fAB None: returns (ntiles, P, K, 4), the sums of g_A, g_B, g_A^2, g_B^2 over
+        each tile of 64 rows, g = f - shift; else (ntiles, P, K, 2), the sums of g_B (g_AB - g_A) and (g_A - g_AB)^2."""
+        if fA.dim() != 3:
+            raise ValueError('sobol: the values must be (P, M, K)')
+        P, M, K = fA.shape          # (an empty axis is the library's to refuse: DgpAmdError)
+        for t, shape in ((fA, (P, M, K)), (fB, (P, M, K)), (fAB, (P, M, K)), (shift, (P, K))):
+            if t is not None and (t.shape != shape or t.dtype != torch.float64 or not t.is_contiguous()):
+                raise ValueError('sobol: fA, fB, fAB must be contiguous float64 tensors of one shape (P, M, K), shift (P, K)')
+        partial = self.empty(-(-M // 64), P, K, 4 if fAB is None else 2)
+        self._chk(self._enter() or lib.dgpamd_sobol_tiles(self.h, P, M, K, _dp(fA), _dp(fB), _dp(fAB), _dp(shift), _dp(partial)))
+        return partial
+
+    def sobol_add(self, partial, sums):
+        """sums += the tiles of partial (ntiles, ...), one after the other in tile order (dgpamd_sobol_add); sums has the shape
+        of one tile's entries and is updated in place."""
+        if partial.shape[1:] != sums.shape:
+            raise ValueError('sobol: sums must have the shape of one tile of partial')
+        for t in (partial, sums):
+            if t.dtype != torch.float64 or not t.is_contiguous():
+                raise ValueError('sobol: partial and sums must be contiguous float64 tensors')
+        self._chk(self._enter() or lib.dgpamd_sobol_add(self.h, partial.shape[0], sums.numel(), _dp(partial), _dp(sums)))
+        return sums
+
     # --------------------------------------------------------------- vecchia
     def nn_ordered(self, x, m):
         n, D = x.shape

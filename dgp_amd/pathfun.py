@@ -19,6 +19,9 @@ local conditioning of sample_functions_vecchia (DESIGN I.14), is built from the 
 The input gradient of a path is as closed-form as the path (DESIGN I.13): dgpamd_pathfun_grad returns a node's values and
 its (P, M, D) gradient from one pass, and PathFunctions.value_and_grad carries the Jacobian with respect to the emulator's
 input through the same walk by the chain rule, on the device.
+
+paths.sobol(A, B) (DESIGN I.16) evaluates the draws at a Saltelli design through the same walk, PathFunctions._walk, which
+leaves every layer on the device, and takes the pick-freeze sums of their Sobol' indices there (sensitivity.pick_freeze).
 """
 import copy
 
@@ -184,11 +187,14 @@ def dense_nodes(emu, sample_size, n_features):
     return build_nodes(emu, J, n_features, node)
 
 
-def _row_blocks(e, x, P, width):
-    """(m0, x[m0:m0 + step]) over the rows of x in order, contiguous blocks of step = _rows_per_call(e, P, width) rows."""
+def _row_blocks(e, x, P, width, multiple=1):
+    """(m0, x[m0:m0 + step]) over the rows of x in order, contiguous blocks of step = _rows_per_call(e, P, width) rows,
+    rounded down to a multiple of `multiple` and at least that (sensitivity.pick_freeze: its blocks start at tiles of 64)."""
     if len(x) == 0:
         raise ValueError('sample_functions: x has no rows')
     step = _rows_per_call(e, P, width)
+    if multiple > 1:
+        step = max(multiple, step // multiple * multiple)
     for m0 in range(0, len(x), step):
         yield m0, np.ascontiguousarray(x[m0:m0 + step])
 
@@ -203,6 +209,16 @@ def _scatter_add(J, g, columns):
     fixed order."""
     for i, c in enumerate(columns):
         J[..., int(c)] += g[..., i]
+
+
+def check_pick_freeze(layers):
+    """What sobol refuses: pick-freeze compares one function at rows that share some of their columns."""
+    for layer in layers:
+        for nd in layer:
+            if nd.type != 'gp':
+                raise ValueError('sobol: the draws of this emulator pass through a sampled node (a likelihood node or a '
+                                 'Categorical top); a sampled node is drawn afresh on every evaluation, so a draw is not one '
+                                 'function of x and the pick-freeze estimators of its Sobol\' indices mean nothing')
 
 
 class PathFunctions:
@@ -271,6 +287,29 @@ class PathFunctions:
         """value_and_grad(x, full_layer)[1]."""
         return self.value_and_grad(x, full_layer)[1]
 
+    def sobol(self, A, B):
+        """Sobol' indices of every draw from the base samples A, B (n_base, Dx), host arrays of one shape, n_base >= 2
+        (sensitivity.saltelli_design makes them): a sensitivity.SobolResult with first and total (K, Dx, N * sample_size),
+        K the outputs of the last layer.  The draws are evaluated at A, B and the Dx designs AB_i in blocks of rows and
+        summed on the device; the result does not depend on the blocks by a bit.  Raises ValueError for an emulator with a
+        likelihood node or a Categorical top."""
+        from . import sensitivity
+        check_pick_freeze(self.layers)
+        sensitivity.check_design(A, B)
+        e, P = self.engine, self.N * self.sample_size
+        # paths(x)'s doubles per row and path, and the three designs and three sets of values of a block
+        width = 4 * max(len(layer) for layer in self.layers) + 3 * max(nf.Omega.shape[1] for nf in self.nodes.values()) + 4 + \
+            max(nf.m for nf in self.nodes.values()) + 3 * len(self.layers[-1]) + 3 * A.shape[1]
+
+        def evaluate(xd):
+            for cur, _ in self._walk(xd):
+                pass
+            return cur
+        sums = sensitivity.pick_freeze(e, evaluate, A, B, P, width)
+        if self.after is not None:
+            self.after(e, self.nodes.values())
+        return sensitivity.SobolResult(sums, len(A))
+
     def _block(self, x, noise=False, jacobians=None):
         """The walk at one block of rows: (values, Jacobians), per layer (P, M, K) host arrays and, with jacobians 'last' for
         the last layer or 'all' for every layer, (P, M, K, Dx) ones.  Without jacobians the nodes are evaluated by
@@ -280,10 +319,19 @@ class PathFunctions:
         J[p, m, :] = sum_k g[p, m, k] J_below[p, m, input_dim[k], :] plus the connect part scattered into x's columns -- one
         fused multiply-add per element and k, in the order of k, so that a row's Jacobian does not depend on the rows that
         share its block (a library contraction may pick another summation order at another size)."""
+        vals, jac = [], []
+        for l, (cur, J) in enumerate(self._walk(self.engine.tensor(x), noise, jacobians)):
+            vals.append(cur.cpu().numpy())
+            if jacobians == 'all' or (jacobians == 'last' and l == len(self.layers) - 1):
+                jac.append(J.cpu().numpy())
+        return vals, jac
+
+    def _walk(self, xd, noise=False, jacobians=None):
+        """_block's walk at the rows of the device tensor xd (M, Dx), nothing copied to the host: yields every layer's
+        ((P, M, K) values, (P, M, K, Dx) Jacobian or None without jacobians), device tensors."""
         assert not (noise and jacobians), 'the noise term has no derivative'
         e, P = self.engine, self.N * self.sample_size
-        xd = e.tensor(x)
-        M, Dx = x.shape
+        M, Dx = xd.shape
         Js = {}
 
         def draw(l, k, nodes, xin):
@@ -308,13 +356,9 @@ class PathFunctions:
                 _scatter_add(J, g[:, :, kd:], connect)
             return out
 
-        vals, jac, L = [], [], len(self.layers)
         for l, cur in enumerate(pathwalk.walk(e, [self.layers] * self.N, self.sample_size, xd, None,
                                               lambda nd: pathwalk.first(xd, nd), draw)):
-            vals.append(cur.cpu().numpy())
-            if jacobians == 'all' or (jacobians == 'last' and l == L - 1):
-                jac.append(Js[l].cpu().numpy())
-        return vals, jac
+            yield cur, Js.get(l)
 
 
 class GpPaths:
@@ -376,3 +420,19 @@ class GpPaths:
     def grad(self, x):
         """value_and_grad(x)[1]."""
         return self.value_and_grad(x)[1]
+
+    def sobol(self, A, B):
+        """Sobol' indices of every draw from the base samples A, B (n_base, Dx), host arrays of one shape, n_base >= 2: a
+        sensitivity.SobolResult with first and total (Dx, sample_size); a column of x that the GP does not read gets exactly 0.
+        Evaluated in blocks of rows and summed on the device; the result does not depend on the blocks by a bit."""
+        from . import sensitivity
+        sensitivity.check_design(A, B)
+        e, J = self.engine, self.sample_size
+
+        def evaluate(xd):
+            return self.node(e, pathwalk.cols(xd, self.columns).contiguous())[:, :, None]
+        sums = sensitivity.pick_freeze(e, evaluate, A, B, J, 2 + len(self.columns) + self.node.m + 3 + 3 * A.shape[1])
+        if self.node.m:
+            from . import vpathfun
+            vpathfun.check_status(e, [self.node])
+        return sensitivity.SobolResult(sums, len(A), squeeze=True)

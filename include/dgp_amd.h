@@ -674,6 +674,25 @@ int dgpamd_mixture_quantile(dgpamd_ctx *ctx, int S, int64_t count, int T, const 
 int dgpamd_mixture_crps(dgpamd_ctx *ctx, int S, int64_t count, const double *mu, const double *var, const double *y,
                         int path, double *out);
 
+/* ---- pick-freeze sums for Sobol' indices of function-valued draws (DESIGN I.16) ----
+ * fA, fB, fAB: the values of P paths at M design rows with K outputs, (P x M x K) device doubles, K fastest: at the rows of
+ * the base sample A, of B, and of AB_i (A with column i taken from B).  shift: (P x K) device doubles; every value enters as
+ * g = f - shift[p, k], one IEEE subtraction (the indices do not depend on the shift: the caller passes f_A at the first row
+ * of the whole design, which takes the cancellation out of sum g^2 for a path with a large mean).
+ * dgpamd_sobol_tiles: a tile is 64 consecutive rows (the last one may be short), ntiles = ceil(M / 64).
+ *   fAB == NULL:  partial[t, p, k, 0..3] = sum g_A, sum g_B, sum g_A^2, sum g_B^2
+ *   otherwise:    partial[t, p, k, 0..1] = sum g_B (g_AB - g_A)   (Saltelli 2010, first-order numerator),
+ *                                          sum (g_A - g_AB)^2     (Jansen, total-order numerator)
+ * over the rows of tile t; partial: (ntiles x P x K x 4 or 2) device doubles.  One row per lane; every product is rounded once
+ * and the 64 terms are added by one fixed tree (lanes past the end of a short tile add +0).
+ * dgpamd_sobol_add: sums[c] = (((sums[c] + partial[0, c]) + partial[1, c]) + ...), c < count, in tile order, in place: the
+ * running sum continues across calls, so a design split at any multiple of 64 rows gives the bits of one call.
+ * No atomics.  DGPAMD_BAD_ARG before any launch: P, M, K, ntiles or count < 1, a null pointer other than fAB.  A NaN value
+ * makes the sums of its own path and output NaN; nothing loops on data. */
+int dgpamd_sobol_tiles(dgpamd_ctx *ctx, int64_t P, int64_t M, int K, const double *fA, const double *fB, const double *fAB,
+                       const double *shift, double *partial);
+int dgpamd_sobol_add(dgpamd_ctx *ctx, int64_t ntiles, int64_t count, const double *partial, double *sums);
+
 #ifdef __cplusplus
 }
 #endif
