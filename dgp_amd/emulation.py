@@ -510,6 +510,20 @@ class emulator:
             fun = self.sample_functions(sample_size, n_features)
         return fun.sobol(A, B)
 
+    def thompson(self, bounds, batch_size=1, n_features=2048, maximize=False, output=0, **minimize_kw):
+        """A batch of Thompson-sampling proposals for minimising (maximize: maximising) output `output` of the emulated
+        function over the box bounds (Dx, 2) (optimize, DESIGN I.17): draws ceil(batch_size / N) functions per imputation
+        (sample_functions, with its refusals), minimises every draw on the device (paths.minimize(bounds, **minimize_kw))
+        and returns (X_new (batch_size, Dx), the optimize.PathOptimum of all draws): row b is the optimum of path
+        (b mod N) * J + b div N, so a batch spreads over the imputations first."""
+        from . import optimize
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError('thompson: batch_size must be at least 1')
+        J = -(-batch_size // self.N)
+        res = self.sample_functions(J, n_features).minimize(bounds, output=output, maximize=maximize, **minimize_kw)
+        return optimize.thompson_rows(res, batch_size, self.N, J), res
+
     def sample_paths_vecchia(self, x, sample_size=50, full_layer=False, m=50):
         """sample_paths by the Vecchia factorisation of each node's joint predictive distribution (vpaths, DESIGN I.11):
         the same container and column layout, for dense and Vecchia emulators and any number of rows.  The rows of x are

@@ -264,6 +264,18 @@ class gp:
             fun = self.sample_functions(sample_size, n_features)
         return fun.sobol(A, B)
 
+    def thompson(self, bounds, batch_size=1, n_features=2048, maximize=False, output=0, **minimize_kw):
+        """A batch of Thompson-sampling proposals for minimising (maximize: maximising) the GP over the box bounds (Dx, 2)
+        (optimize, DESIGN I.17): draws batch_size functions (sample_functions, with its refusals), minimises each on the
+        device (paths.minimize(bounds, **minimize_kw)) and returns (X_new (batch_size, Dx), the optimize.PathOptimum): row b
+        is the optimum of draw b."""
+        from . import optimize
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError('thompson: batch_size must be at least 1')
+        res = self.sample_functions(batch_size, n_features).minimize(bounds, output=output, maximize=maximize, **minimize_kw)
+        return optimize.thompson_rows(res, batch_size, 1, batch_size), res
+
     def sample_paths_vecchia(self, x, sample_size=50, m=50):
         """Joint posterior draws of the GP at the rows of x by the Vecchia factorisation of the joint predictive distribution
         (vpaths): (M, sample_size) as sample_paths, for dense and Vecchia-mode models and any M.  The rows are drawn in the

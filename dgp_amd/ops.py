@@ -720,6 +720,54 @@ class Engine:
         self._chk(self._enter() or lib.dgpamd_sobol_add(self.h, partial.shape[0], sums.numel(), _dp(partial), _dp(sums)))
         return sums
 
+    # --------------------------------------------------------------- box-constrained minimisation (csrc/boxmin.hip)
+    BOXMIN = dict(running=0, gtol=1, ftol=2, maxiter=3, maxeval=4, linesearch=5, nan=6)
+
+    @staticmethod
+    def boxmin_workspace(Q, D, history):
+        """Bytes of the state workspace of boxmin_step for Q problems of D columns (dgpamd_boxmin_workspace: a host-side
+        formula); sizes that the step refuses raise ValueError."""
+        nbytes = int(lib.dgpamd_boxmin_workspace(int(Q), int(D), int(history)))
+        if nbytes == 0:
+            raise ValueError('boxmin: need Q >= 1, 1 <= D <= %d and 1 <= history <= 16' % _lib.MAXD)
+        return nbytes
+
+    def boxmin_state(self, Q, D, history, lo, hi):
+        """What one minimisation keeps between its boxmin_step calls: the opaque workspace, the box on the device and on the
+        host, and the results x (Q, D), fun (Q,), status, n_iter, n_eval (Q,) int32 and running (1,) int32."""
+        lo, hi = _f64(lo), _f64(hi)
+        if lo.size != D or hi.size != D:
+            raise ValueError('boxmin: lo and hi must hold D = %d bounds' % D)
+        return dict(work=torch.empty(self.boxmin_workspace(Q, D, history), dtype=torch.uint8, device=self.device),
+                    history=int(history), lo_h=lo, hi_h=hi, lo=self.tensor(lo), hi=self.tensor(hi),
+                    x=self.empty(Q, D), fun=self.empty(Q), status=self.zeros(Q, dtype=torch.int32),
+                    n_iter=self.zeros(Q, dtype=torch.int32), n_eval=self.zeros(Q, dtype=torch.int32),
+                    running=self.zeros(1, dtype=torch.int32))
+
+    def boxmin_step(self, state, f, J, x_trial, k=0, sign=1.0, maxiter=100, max_eval=420, gtol=1e-6, ftol=1e-12, first=False):
+        """One transition of every problem's projected L-BFGS (dgpamd_boxmin_step).  state: boxmin_state's; f (Q, K) or
+        (P, R, K) and J (Q, K, D) or (P, R, K, D): the walk's values and Jacobian at x_trial (Q, D) or (P, R, D), contiguous
+        float64 device tensors, of which column k is read and multiplied by sign (+1 or -1); x_trial is overwritten with the
+        next trial points.  first: initialise the state from x_trial.  The results are state's tensors, updated in place."""
+        if x_trial.dim() not in (2, 3) or f.dim() != x_trial.dim() or J.dim() != x_trial.dim() + 1:
+            raise ValueError('boxmin: x_trial must be (Q, D) or (P, R, D), f (..., K) and J (..., K, D) beside it')
+        D, K = x_trial.shape[-1], f.shape[-1]
+        lead = x_trial.shape[:-1]
+        Q = int(np.prod(lead))
+        for t, shape in ((x_trial, (*lead, D)), (f, (*lead, K)), (J, (*lead, K, D))):
+            if t.shape != shape or t.dtype != torch.float64 or not t.is_contiguous():
+                raise ValueError('boxmin: x_trial, f, J must be contiguous float64 tensors (..., D), (..., K), (..., K, D)')
+        sizes = dict(x=Q * D, fun=Q, status=Q, n_iter=Q, n_eval=Q, running=1, lo=D, hi=D)
+        if state['work'].numel() < self.boxmin_workspace(Q, D, state['history']) or state['lo_h'].size != D or \
+                state['hi_h'].size != D or any(state[name].numel() != count for name, count in sizes.items()):
+            raise ValueError('boxmin: the state was made for another Q or D')
+        self._chk(self._enter() or lib.dgpamd_boxmin_step(
+            self.h, Q, D, K, int(k), float(sign), _dp(f), _dp(J), _dp(state['lo']), _dp(state['hi']), _hp(state['lo_h']),
+            _hp(state['hi_h']), state['history'], int(maxiter), int(max_eval), float(gtol), float(ftol), 1 if first else 0,
+            _dp(state['work']), _dp(x_trial), _dp(state['x']), _dp(state['fun']), _dp(state['status']), _dp(state['n_iter']),
+            _dp(state['n_eval']), _dp(state['running'])))
+        return x_trial
+
     # --------------------------------------------------------------- vecchia
     def nn_ordered(self, x, m):
         n, D = x.shape

@@ -22,6 +22,9 @@ input through the same walk by the chain rule, on the device.
 
 paths.sobol(A, B) (DESIGN I.16) evaluates the draws at a Saltelli design through the same walk, PathFunctions._walk, which
 leaves every layer on the device, and takes the pick-freeze sums of their Sobol' indices there (sensitivity.pick_freeze).
+
+paths.minimize(bounds) (DESIGN I.17) finds every draw's optimum over a box: the same walk at per-path rows (P, R, Dx), values
+and Jacobian, feeds a batched projected L-BFGS on the device (optimize.minimize, dgpamd_boxmin_step).
 """
 import copy
 
@@ -221,6 +224,14 @@ def check_pick_freeze(layers):
                                  'function of x and the pick-freeze estimators of its Sobol\' indices mean nothing')
 
 
+def _check_smooth(nodes):
+    """What minimize refuses beside value_and_grad's own refusals, before it evaluates anything."""
+    if any(nf.m for nf in nodes):
+        raise NotImplementedError('minimize: a draw made by local conditioning (sample_functions_vecchia) is only piecewise '
+                                  'differentiable, so a gradient method has nothing to follow; sample_functions gives '
+                                  'differentiable draws of a dense model')
+
+
 class PathFunctions:
     """emulator.sample_functions' result: N * sample_size posterior draws of the emulated function, each a closed-form
     function of x.  paths(x, full_layer=False, noise=False) evaluates all of them at the rows of x and returns
@@ -310,6 +321,43 @@ class PathFunctions:
             self.after(e, self.nodes.values())
         return sensitivity.SobolResult(sums, len(A))
 
+    def minimize(self, bounds, n_starts=8, n_candidates=2048, output=0, maximize=False, x0=None, seed=None, qmc=False,
+                 maxiter=100, gtol=1e-6, ftol=1e-12, history=6, check_every=8, max_eval=None):
+        """The minimum of every draw over the box bounds (Dx, 2) = [[low, high], ...], on the device (optimize, DESIGN
+        I.17): an optimize.PathOptimum with x (P, Dx), fun (P,), P = N * sample_size, the best of n_starts local optima of
+        output `output` of the last layer (maximize: the largest; fun is the draw's own value), and every start's x_all
+        (P, R, Dx), fun_all, status, n_iter, n_eval (P, R).  Starts: x0 (R, Dx) shared or (P, R, Dx), projected into the
+        box; else per draw the n_starts best of n_candidates rows in the box (np.random.default_rng(seed).uniform, or with
+        qmc scipy's scrambled Sobol' sequence, n_candidates a power of two), ties to the lower row.  All P * n_starts
+        problems advance in lock-step, a projected L-BFGS with `history` pairs (1 .. 16), until each has a projected
+        gradient within gtol, a relative decrease within ftol, maxiter accepted steps or max_eval evaluations (None:
+        4 maxiter + 20); the host looks at the count of running problems every check_every rounds.  The same arguments
+        give the same bits.  Raises ValueError for an emulator with a likelihood node or a Categorical top and for bad
+        bounds, output or n_starts; NotImplementedError for draws made by sample_functions_vecchia (they are only
+        piecewise differentiable: use sample_functions)."""
+        from . import optimize
+        self._check_differentiable()
+        _check_smooth(self.nodes.values())
+        e, P = self.engine, self.N * self.sample_size
+        K, D = max(len(layer) for layer in self.layers), max(nf.Omega.shape[1] for nf in self.nodes.values())
+        Dx = np.asarray(bounds).shape[0] if np.ndim(bounds) == 2 else None
+        read = max(int(np.max(c)) for l, layer in enumerate(self.layers) for nd in layer
+                   for c in ((nd.input_dim if l == 0 else []), ([] if nd.connect is None else nd.connect)) if len(c))
+        if Dx is not None and Dx <= read:
+            raise ValueError('minimize: bounds has %d rows, the emulator reads column %d of its input' % (Dx, read))
+
+        def values(xd):
+            for cur, _ in self._walk(xd):
+                pass
+            return cur
+
+        def value_and_jac(xt):
+            for cur, J in self._walk(xt, jacobians='last'):
+                pass
+            return cur, J
+        return optimize.minimize(e, P, len(self.layers[-1]), Dx, values, value_and_jac, 4 * K + 3 * D + 4, bounds, n_starts,
+                                 n_candidates, output, maximize, x0, seed, qmc, maxiter, gtol, ftol, history, check_every, max_eval)
+
     def _block(self, x, noise=False, jacobians=None):
         """The walk at one block of rows: (values, Jacobians), per layer (P, M, K) host arrays and, with jacobians 'last' for
         the last layer or 'all' for every layer, (P, M, K, Dx) ones.  Without jacobians the nodes are evaluated by
@@ -328,10 +376,12 @@ class PathFunctions:
 
     def _walk(self, xd, noise=False, jacobians=None):
         """_block's walk at the rows of the device tensor xd (M, Dx), nothing copied to the host: yields every layer's
-        ((P, M, K) values, (P, M, K, Dx) Jacobian or None without jacobians), device tensors."""
+        ((P, M, K) values, (P, M, K, Dx) Jacobian or None without jacobians), device tensors.  xd (P, M, Dx): every path
+        at M rows of its own (the node kernels' per-path form; optimize.minimize's trial points)."""
         assert not (noise and jacobians), 'the noise term has no derivative'
         e, P = self.engine, self.N * self.sample_size
-        M, Dx = xd.shape
+        assert xd.dim() == 2 or (xd.dim() == 3 and xd.shape[0] == P)
+        M, Dx = xd.shape[-2:]
         Js = {}
 
         def draw(l, k, nodes, xin):
@@ -357,7 +407,7 @@ class PathFunctions:
             return out
 
         for l, cur in enumerate(pathwalk.walk(e, [self.layers] * self.N, self.sample_size, xd, None,
-                                              lambda nd: pathwalk.first(xd, nd), draw)):
+                                              lambda nd: pathwalk.first(xd, nd).contiguous(), draw, own_input=True)):
             yield cur, Js.get(l)
 
 
@@ -420,6 +470,29 @@ class GpPaths:
     def grad(self, x):
         """value_and_grad(x)[1]."""
         return self.value_and_grad(x)[1]
+
+    def minimize(self, bounds, n_starts=8, n_candidates=2048, output=0, maximize=False, x0=None, seed=None, qmc=False,
+                 maxiter=100, gtol=1e-6, ftol=1e-12, history=6, check_every=8, max_eval=None):
+        """The minimum of every draw over the box bounds (Dx, 2): PathFunctions.minimize for the sample_size draws of a gp
+        model (P = sample_size, one output); a column of x that the GP does not read keeps its start."""
+        from . import optimize
+        _check_smooth([self.node])
+        e, J = self.engine, self.sample_size
+        cols = torch.as_tensor(self.columns, device=e.device)
+
+        def values(xd):
+            return self.node(e, xd[:, cols].contiguous())[:, :, None]
+
+        def value_and_jac(xt):
+            f, g = self.node.value_and_grad(e, xt[:, :, cols].contiguous())
+            jac = e.zeros(*xt.shape)
+            _scatter_add(jac, g, self.columns)
+            return f[:, :, None], jac[:, :, None]
+        Dx = np.asarray(bounds).shape[0] if np.ndim(bounds) == 2 else None
+        if Dx is not None and Dx <= int(np.max(self.columns)):
+            raise ValueError('minimize: bounds has %d rows, the model reads column %d' % (Dx, int(np.max(self.columns))))
+        return optimize.minimize(e, J, 1, Dx, values, value_and_jac, 2 + len(self.columns), bounds, n_starts, n_candidates, output,
+                                 maximize, x0, seed, qmc, maxiter, gtol, ftol, history, check_every, max_eval)
 
     def sobol(self, A, B):
         """Sobol' indices of every draw from the base samples A, B (n_base, Dx), host arrays of one shape, n_base >= 2: a

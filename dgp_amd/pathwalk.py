@@ -26,9 +26,10 @@ def cols(t, idx):
 
 
 def first(xd, nd):
-    """The input of first-layer node nd at the rows xd (M, Dx) of the hierarchy's input: its input_dim, then its connect columns."""
+    """The input of first-layer node nd at the rows xd of the hierarchy's input, (M, Dx) or per path (P, M, Dx): its input_dim,
+    then its connect columns."""
     xin = cols(xd, nd.input_dim)
-    return xin if nd.connect is None else torch.cat((xin, cols(xd, nd.connect)), 1)
+    return xin if nd.connect is None else torch.cat((xin, cols(xd, nd.connect)), -1)
 
 
 def per_path(t, P):
@@ -52,13 +53,15 @@ def connect_cols(nd, last, shared, D, head):
     return connect_split(nd.connect, last, D, head.input_dim, head.connect)
 
 
-def walk(e, structs, J, m, z, first, draw):
+def walk(e, structs, J, m, z, first, draw, own_input=False):
     """Paths of a DGP hierarchy, layer by layer: yields each layer's (P, M, K) device tensor, P = len(structs) * J, the
     last one the hierarchy's output (a Categorical top: its class probabilities).  structs[s] is the structure behind paths
     s*J .. (s+1)*J - 1 (an emulator: its all_layer for every imputation; an lgp: system s's snapshot); m the hierarchy's
     input, (M, D) shared by every path or (P, M, D); z its external input (M, Dz) or None; first(nd) the input of
     first-layer node nd, (M, D') or (P, M, D').  A deeper node sees its input_dim columns of the layer below plus its
-    `connect` columns: of m when every path shares it, else split over m and z as lgp.dgp_pred does.
+    `connect` columns: of m when every path shares it, else split over m and z as lgp.dgp_pred does.  own_input: a per-path
+    m (P, M, D) is the hierarchy's own input all the same (every path at rows of its own: PathFunctions.minimize), and
+    `connect` indexes it as it stands, as it does a shared one.
     draw(il, j, nodes, xin) -> (P, M) draws GP node j of layer il (nodes[s] = structs[s][il][j]) at xin; likelihood nodes
     sample from the path's latents after the GP nodes of their layer (structs[p // J]'s node for path p)."""
     S, L = len(structs), len(structs[0])
@@ -77,7 +80,7 @@ def walk(e, structs, J, m, z, first, draw):
             if il == 0:
                 xin = first(nd)
             else:
-                own, ext = connect_cols(nd, il == L - 1, m.dim() == 2, m.shape[-1], structs[0][0][0])
+                own, ext = connect_cols(nd, il == L - 1, m.dim() == 2 or own_input, m.shape[-1], structs[0][0][0])
                 xin = torch.cat([cols(prev, nd.input_dim)] + [per_path(cols(t, i), P) for t, i in ((m, own), (z, ext)) if i.size], 2)
             cur[:, :, j] = draw(il, j, [st[il][j] for st in structs], xin.contiguous())
         if any(nd.type != 'gp' for nd in layer):   # likelihood nodes sample y from the path's latents (emulation.py:785-822)

@@ -693,6 +693,54 @@ int dgpamd_sobol_tiles(dgpamd_ctx *ctx, int64_t P, int64_t M, int K, const doubl
                        const double *shift, double *partial);
 int dgpamd_sobol_add(dgpamd_ctx *ctx, int64_t ntiles, int64_t count, const double *partial, double *sums);
 
+/* ---- batched box-constrained minimisation of function-valued draws (DESIGN I.17) ----
+ * A projected L-BFGS for Q independent problems min phi_q(x), lo <= x <= hi, D <= DGPAMD_MAXD columns, driven by reverse
+ * communication: a call takes the objective and its gradient at the current trial points, advances every problem's state
+ * machine by one transition and writes the next trial points.  Nothing goes to the host.
+ * f (Q x K), J (Q x K x D): device doubles, the values and the Jacobian of the walk at x_trial, q = p R + r; the kernel reads
+ * column k alone and forms phi = sign f[q, k], grad = sign J[q, k, :] (sign +1 minimises the draw, -1 maximises it).
+ * lo, hi: D device doubles; lo_h, hi_h: host copies, for the checks below.  history 1 .. DGPAMD_BOXMIN_MAXHIST stored pairs.
+ * work: dgpamd_boxmin_workspace(Q, D, history) bytes (a host-side formula, no GPU; 0 for sizes the step refuses), opaque, kept
+ * by the caller between the calls of one minimisation.  x_trial (Q x D): read as the point just evaluated, overwritten with the
+ * next one; first != 0 initialises the state from it (and status, n_iter, n_eval, running).
+ * Results, written when a problem finishes: x (Q x D), fun (Q) the value of the draw (sign undone), status (Q) int32 one of
+ * DGPAMD_BOXMIN_*; n_iter, n_eval (Q) int32 accepted steps and evaluations so far; running: one int32, the problems whose
+ * status is DGPAMD_BOXMIN_RUNNING after the call (the only atomic: an integer count does not depend on order).
+ * Per problem (tests/boxmin_ref.py restates it):
+ *   INIT       (x, f, g) <- trial; phi or g not finite: NAN.  Then DIRECTION (after its GTOL test: MAXEVAL if max_eval is 1).
+ *   DIRECTION  B = {i: (x_i <= lo_i and g_i > 0) or (x_i >= hi_i and g_i < 0) or lo_i == hi_i}; pg = g off B, 0 on B.
+ *              max |P(x - g) - x| <= gtol: GTOL.  d = -H pg by the two-loop recursion, the components of B of q, s, y taken as
+ *              zero and d = 0 on B; a pair with s^T y <= 0 over the free components is skipped; gamma = s^T y / y^T y of the
+ *              newest pair over the free components (1 if it is skipped or there is none).  No pair, or pg^T d >= 0 or not
+ *              finite: d = -pg and t = min(1, 1 / max|pg|) 2^grow; else t = 1.  trial = P(x + t d).  grow (at most 30) counts
+ *              the accepted steps just before that stored no pair and needed no halving: without positive curvature the
+ *              steps along -pg double, and a linear objective overshoots its corner and is projected onto it exactly.
+ *   SEARCH     delta = trial - x; accept if phi_t and g_t are finite, phi_t <= f + 1e-4 g^T delta and g^T delta < 0.  Else
+ *              MAXEVAL at max_eval (x kept); after 20 halvings a quasi-Newton direction drops the pairs and restarts along
+ *              -pg, and -pg ends with LINESEARCH (x kept); else t <- t / 2, trial = P(x + t d).  A NaN is a failed test.
+ *   ACCEPT     s = delta, y = g_t - g enter the ring if s^T y > 1e-10 |s| |y| (grow <- 0; else grow <- grow + 1 after a search
+ *              without halvings, 0 after one with); (x, f, g) <- trial; n_iter += 1; GTOL as above;
+ *              FTOL if f_old - f <= ftol max(|f_old|, |f|, 1); MAXITER at maxiter; MAXEVAL at max_eval; else DIRECTION.
+ * A finished problem writes x_trial = x and changes nothing more.  One lane per problem and no cross-lane operation: any
+ * slice of the problems, run alone, gives the same bits.  Products are not fused into sums (the file is built without
+ * contraction).  DGPAMD_BAD_ARG before any launch: Q < 1, D < 1 or D > DGPAMD_MAXD, K < 1, k outside [0, K), sign not +-1,
+ * history outside 1 .. DGPAMD_BOXMIN_MAXHIST, maxiter or max_eval < 1, a null pointer, lo_h[i] > hi_h[i] or a NaN bound, a
+ * negative or NaN tolerance. */
+#define DGPAMD_BOXMIN_RUNNING 0
+#define DGPAMD_BOXMIN_GTOL 1
+#define DGPAMD_BOXMIN_FTOL 2
+#define DGPAMD_BOXMIN_MAXITER 3
+#define DGPAMD_BOXMIN_MAXEVAL 4
+#define DGPAMD_BOXMIN_LINESEARCH 5
+#define DGPAMD_BOXMIN_NAN 6
+#define DGPAMD_BOXMIN_COUNT 7
+#define DGPAMD_BOXMIN_MAXHIST 16
+size_t dgpamd_boxmin_workspace(int64_t Q, int D, int history);
+int dgpamd_boxmin_step(dgpamd_ctx *ctx, int64_t Q, int D, int K, int k, double sign, const double *f, const double *J,
+                       const double *lo, const double *hi, const double *lo_h, const double *hi_h, int history, int maxiter,
+                       int max_eval, double gtol, double ftol, int first, void *work, double *x_trial, double *x, double *fun,
+                       int32_t *status, int32_t *n_iter, int32_t *n_eval, int32_t *running);
+
 #ifdef __cplusplus
 }
 #endif
