@@ -128,6 +128,7 @@ SIGNATURES = {
     'dgpamd_mixture_crps': (_i, [_p, _i, _l, _p, _p, _p, _i, _p]),
     'dgpamd_sobol_tiles': (_i, [_p, _l, _l, _i, _p, _p, _p, _p, _p]),
     'dgpamd_sobol_add': (_i, [_p, _l, _l, _p, _p]),
+    'dgpamd_gradmom_tiles': (_i, [_p, _l, _l, _i, _i, _p, _p, _p, _p]),
     'dgpamd_boxmin_workspace': (_z, [_l, _i, _i]),
     'dgpamd_boxmin_step': (_i, [_p, _l, _i, _i, _i, _d, _p, _p, _p, _p, _p, _p, _i, _i, _i, _d, _d, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
 }

@@ -510,6 +510,19 @@ class emulator:
             fun = self.sample_functions(sample_size, n_features)
         return fun.sobol(A, B)
 
+    def active_subspace(self, bounds, n_rows=4096, sample_size=20, n_features=2048, seed=None, qmc=False):
+        """The active subspace and the derivative-based sensitivity measures of the emulated function over the box bounds
+        (Dx, 2), with their posterior uncertainty (sensitivity, DESIGN I.18): draws N * sample_size functions
+        (sample_functions, with its refusals), makes the design sensitivity.uniform_design(bounds, n_rows, seed, qmc) and
+        returns paths.active_subspace(X, bounds), a sensitivity.ActiveSubspaceResult: per output and draw C = E_x[grad f
+        grad f^T] (K, N * sample_size, Dx, Dx), the eigenvalues and eigenvectors of the box-normalised C, dgsm and
+        total_bound >= the total Sobol' index (K, Dx, N * sample_size); result.subspace(k) gives the mean subspace and every
+        draw's distance to it, result.summary() means and intervals over the draws.  One gradient pass where sobol needs
+        Dx + 2 value passes.  Emulators of GP nodes only (ValueError)."""
+        from . import sensitivity
+        X = sensitivity.uniform_design(bounds, n_rows, seed, qmc)
+        return self.sample_functions(sample_size, n_features).active_subspace(X, bounds)
+
     def thompson(self, bounds, batch_size=1, n_features=2048, maximize=False, output=0, **minimize_kw):
         """A batch of Thompson-sampling proposals for minimising (maximize: maximising) output `output` of the emulated
         function over the box bounds (Dx, 2) (optimize, DESIGN I.17): draws ceil(batch_size / N) functions per imputation

@@ -264,6 +264,16 @@ class gp:
             fun = self.sample_functions(sample_size, n_features)
         return fun.sobol(A, B)
 
+    def active_subspace(self, bounds, n_rows=4096, sample_size=20, n_features=2048, seed=None, qmc=False):
+        """The active subspace and the derivative-based sensitivity measures of the GP over the box bounds (Dx, 2), with
+        their posterior uncertainty (sensitivity, DESIGN I.18): draws sample_size functions (sample_functions, with its
+        refusals), makes the design sensitivity.uniform_design(bounds, n_rows, seed, qmc) and returns
+        paths.active_subspace(X, bounds), a sensitivity.ActiveSubspaceResult with C (sample_size, Dx, Dx), eigenvalues
+        (sample_size, Dx), eigenvectors (sample_size, Dx, Dx), dgsm and total_bound (Dx, sample_size)."""
+        from . import sensitivity
+        X = sensitivity.uniform_design(bounds, n_rows, seed, qmc)
+        return self.sample_functions(sample_size, n_features).active_subspace(X, bounds)
+
     def thompson(self, bounds, batch_size=1, n_features=2048, maximize=False, output=0, **minimize_kw):
         """A batch of Thompson-sampling proposals for minimising (maximize: maximising) the GP over the box bounds (Dx, 2)
         (optimize, DESIGN I.17): draws batch_size functions (sample_functions, with its refusals), minimises each on the

@@ -720,6 +720,25 @@ class Engine:
         self._chk(self._enter() or lib.dgpamd_sobol_add(self.h, partial.shape[0], sums.numel(), _dp(partial), _dp(sums)))
         return sums
 
+    # --------------------------------------------------------------- gradient second moments (csrc/gradmom.hip)
+    def gradmom_tiles(self, f, J, shift):
+        """The per-tile sums of dgpamd_gradmom_tiles.  f (P, M, K), J (P, M, K, Dx), shift (P, K): contiguous float64 device
+        tensors, the values and the Jacobian of the paths as the walk leaves them, 1 <= Dx <= 64.  Returns (ntiles, P, K, NC),
+        NC = 2 + Dx + Dx (Dx + 1) / 2: over each tile of 64 rows the sums of g = f - shift and g^2, of J_d, and of J_d J_e for
+        d <= e (the upper triangle packed row-major).  sobol_add adds the tiles onto running sums (P, K, NC)."""
+        if f.dim() != 3 or J.dim() != 4:
+            raise ValueError('gradmom: the values must be (P, M, K) and the Jacobian (P, M, K, Dx)')
+        P, M, K = f.shape           # (an empty axis is the library's to refuse: DgpAmdError)
+        Dx = J.shape[3]
+        if not 1 <= Dx <= 64:
+            raise ValueError('gradmom: the Jacobian must have 1 to 64 columns, got %d' % Dx)
+        for t, shape in ((f, (P, M, K)), (J, (P, M, K, Dx)), (shift, (P, K))):
+            if t.shape != shape or t.dtype != torch.float64 or not t.is_contiguous():
+                raise ValueError('gradmom: f (P, M, K), J (P, M, K, Dx) and shift (P, K) must be contiguous float64 tensors')
+        partial = self.empty(-(-M // 64), P, K, 2 + Dx + Dx * (Dx + 1) // 2)
+        self._chk(self._enter() or lib.dgpamd_gradmom_tiles(self.h, P, M, K, Dx, _dp(f), _dp(J), _dp(shift), _dp(partial)))
+        return partial
+
     # --------------------------------------------------------------- box-constrained minimisation (csrc/boxmin.hip)
     BOXMIN = dict(running=0, gtol=1, ftol=2, maxiter=3, maxeval=4, linesearch=5, nan=6)
 

@@ -25,6 +25,9 @@ leaves every layer on the device, and takes the pick-freeze sums of their Sobol'
 
 paths.minimize(bounds) (DESIGN I.17) finds every draw's optimum over a box: the same walk at per-path rows (P, R, Dx), values
 and Jacobian, feeds a batched projected L-BFGS on the device (optimize.minimize, dgpamd_boxmin_step).
+
+paths.active_subspace(X) (DESIGN I.18) contracts the same walk's Jacobian at the rows of a design into every draw's
+E_x[grad f grad f^T] on the device (sensitivity.gradient_moments, dgpamd_gradmom_tiles): the Jacobian never visits the host.
 """
 import copy
 
@@ -224,12 +227,12 @@ def check_pick_freeze(layers):
                                  'function of x and the pick-freeze estimators of its Sobol\' indices mean nothing')
 
 
-def _check_smooth(nodes):
-    """What minimize refuses beside value_and_grad's own refusals, before it evaluates anything."""
+def _check_smooth(nodes, what='minimize', why='a gradient method has nothing to follow'):
+    """What minimize and active_subspace refuse beside value_and_grad's own refusals, before they evaluate anything."""
     if any(nf.m for nf in nodes):
-        raise NotImplementedError('minimize: a draw made by local conditioning (sample_functions_vecchia) is only piecewise '
-                                  'differentiable, so a gradient method has nothing to follow; sample_functions gives '
-                                  'differentiable draws of a dense model')
+        raise NotImplementedError('%s: a draw made by local conditioning (sample_functions_vecchia) is only piecewise '
+                                  'differentiable, so %s; sample_functions gives '
+                                  'differentiable draws of a dense model' % (what, why))
 
 
 class PathFunctions:
@@ -357,6 +360,32 @@ class PathFunctions:
             return cur, J
         return optimize.minimize(e, P, len(self.layers[-1]), Dx, values, value_and_jac, 4 * K + 3 * D + 4, bounds, n_starts,
                                  n_candidates, output, maximize, x0, seed, qmc, maxiter, gtol, ftol, history, check_every, max_eval)
+
+    def active_subspace(self, X, bounds=None):
+        """The second moment of every draw's input gradient over the rows of X (M, Dx), a host array, M >= 2, Dx <= 64
+        (sensitivity.uniform_design makes a uniform sample of a box): a sensitivity.ActiveSubspaceResult with C
+        (K, N * sample_size, Dx, Dx), its eigen-decomposition (the active subspace), dgsm and, with bounds (Dx, 2), the
+        bound on the total Sobol' indices; K the outputs of the last layer.  The Jacobian of the walk is contracted on the
+        device in blocks of rows (DESIGN I.18); the result does not depend on the blocks by a bit.  Columns of X that the
+        model does not read give exactly zero rows and columns of C.  Raises ValueError for an emulator with a likelihood
+        node or a Categorical top, NotImplementedError for draws made by sample_functions_vecchia."""
+        from . import sensitivity
+        self._check_differentiable()
+        _check_smooth(self.nodes.values(), 'active_subspace', 'it has no gradient to take moments of')
+        bounds = sensitivity.check_rows(X, bounds)
+        e, P, Dx = self.engine, self.N * self.sample_size, X.shape[1]
+        K, D = max(len(layer) for layer in self.layers), max(nf.Omega.shape[1] for nf in self.nodes.values())
+        # value_and_grad's doubles per row and path, and the partial sums: NC / 64 per output
+        width = 4 * K + 3 * D + 4 + 2 * D + (3 * K + 2) * Dx + -(-len(self.layers[-1]) * sensitivity.n_sums(Dx) // 64)
+
+        def value_and_jac(xd):
+            for cur, J in self._walk(xd, jacobians='last'):
+                pass
+            return cur.contiguous(), J
+        sums = sensitivity.gradient_moments(e, value_and_jac, X, P, width)
+        if self.after is not None:
+            self.after(e, self.nodes.values())
+        return sensitivity.ActiveSubspaceResult(sums, len(X), bounds)
 
     def _block(self, x, noise=False, jacobians=None):
         """The walk at one block of rows: (values, Jacobians), per layer (P, M, K) host arrays and, with jacobians 'last' for
@@ -493,6 +522,27 @@ class GpPaths:
             raise ValueError('minimize: bounds has %d rows, the model reads column %d' % (Dx, int(np.max(self.columns))))
         return optimize.minimize(e, J, 1, Dx, values, value_and_jac, 2 + len(self.columns), bounds, n_starts, n_candidates, output,
                                  maximize, x0, seed, qmc, maxiter, gtol, ftol, history, check_every, max_eval)
+
+    def active_subspace(self, X, bounds=None):
+        """PathFunctions.active_subspace for the sample_size draws of a gp model: a sensitivity.ActiveSubspaceResult without
+        the output axis, C (sample_size, Dx, Dx), dgsm (Dx, sample_size), ...; a column of X that the GP does not read gives
+        exactly zero rows and columns of C."""
+        from . import sensitivity
+        _check_smooth([self.node], 'active_subspace', 'it has no gradient to take moments of')
+        bounds = sensitivity.check_rows(X, bounds)
+        e, J, Dx = self.engine, self.sample_size, X.shape[1]
+        if Dx <= int(np.max(self.columns)):
+            raise ValueError('active_subspace: X has %d columns, the model reads column %d' % (Dx, int(np.max(self.columns))))
+
+        def value_and_jac(xd):
+            f, g = self.node.value_and_grad(e, pathwalk.cols(xd, self.columns).contiguous())
+            jac = e.zeros(J, xd.shape[0], Dx)
+            _scatter_add(jac, g, self.columns)
+            return f[:, :, None], jac[:, :, None]
+        # value_and_grad's doubles per row and path, the Jacobian in x's columns, and the partial sums
+        width = 2 + 3 * len(self.columns) + 2 * Dx + -(-sensitivity.n_sums(Dx) // 64)
+        return sensitivity.ActiveSubspaceResult(sensitivity.gradient_moments(e, value_and_jac, X, J, width), len(X), bounds,
+                                                squeeze=True)
 
     def sobol(self, A, B):
         """Sobol' indices of every draw from the base samples A, B (n_base, Dx), host arrays of one shape, n_base >= 2: a

@@ -693,6 +693,22 @@ int dgpamd_sobol_tiles(dgpamd_ctx *ctx, int64_t P, int64_t M, int K, const doubl
                        const double *shift, double *partial);
 int dgpamd_sobol_add(dgpamd_ctx *ctx, int64_t ntiles, int64_t count, const double *partial, double *sums);
 
+/* ---- second moments of the input gradient of function-valued draws (DESIGN I.18) ----
+ * f (P x M x K), J (P x M x K x Dx, Dx fastest), shift (P x K): device doubles, the values and the Jacobian of P paths at M
+ * design rows with K outputs, and the shift of the values (g = f - shift[p, k], as dgpamd_sobol_tiles).  1 <= Dx <= 64.
+ * A tile is 64 consecutive rows (the last one may be short), ntiles = ceil(M / 64), NC = 2 + Dx + Dx (Dx + 1) / 2:
+ *   partial[t, p, k, 0..1]       = sum g, sum g^2
+ *   partial[t, p, k, 2 + d]      = sum J_d,      d < Dx
+ *   partial[t, p, k, 2 + Dx + ..] = sum J_d J_e,  d <= e < Dx, the upper triangle packed row-major
+ * over the rows of tile t; partial: (ntiles x P x K x NC) device doubles.  Rows past M contribute +0.  The products are formed
+ * and added by v_mfma_f64_16x16x4 over the 64 rows of the tile: their order inside a tile is the instruction's, and it is the
+ * same for every tile, path and launch.  dgpamd_sobol_add adds the tiles onto running sums (P x K x NC) in tile order, so a
+ * design split at any multiple of 64 rows gives the bits of one call.  No atomics.  A column of J that is zero gives +0 in its
+ * sum and in every product it takes part in.  DGPAMD_BAD_ARG before any launch: P, M or K < 1, Dx outside 1 .. 64, a null
+ * pointer, ntiles * P * K beyond 2^31 - 1. */
+int dgpamd_gradmom_tiles(dgpamd_ctx *ctx, int64_t P, int64_t M, int K, int Dx, const double *f, const double *J,
+                         const double *shift, double *partial);
+
 /* ---- batched box-constrained minimisation of function-valued draws (DESIGN I.17) ----
  * A projected L-BFGS for Q independent problems min phi_q(x), lo <= x <= hi, D <= DGPAMD_MAXD columns, driven by reverse
  * communication: a call takes the objective and its gradient at the current trial points, advances every problem's state

@@ -15,7 +15,10 @@ d + 1 = 6 calls); then dgpamd_pathfun_grad against dgpamd_pathfun_eval by device
 Vecchia mode -- creating sample_functions_vecchia's paths, then at M = 1000, 8192 and 100 000 three alternating rounds of their
 paths(x), sample_paths_vecchia on the same rows, and paths(x) of sample_functions made before the emulator left dense mode;
 (b) a gp of configs[4]'s shape (n = 50 000, d = 8, Vecchia mode), 100 paths at M = 100 000; (c) dgpamd_vpathfun_update alone by
-device events, shared rows, 100 paths at those rows, against 100 calls of dgpamd_vecchia_gp on the same conditioning sets."""
+device events, shared rows, 100 paths at those rows, against 100 calls of dgpamd_vecchia_gp on the same conditioning sets.
+--gradmom: the gradient second moments (profiles/gradmom_bench.txt; DESIGN I.18), F = 2048: at M = 8192 and 100 000 three
+alternating rounds of paths.active_subspace(x), of paths.grad(x) followed by the host contraction, and of
+paths.value_and_grad(x); then dgpamd_gradmom_tiles alone by device events at Dx = 5 and a synthetic Dx = 64."""
 import os
 import sys
 import time
@@ -113,6 +116,49 @@ def device_ms(e, f, reps=3):
     return e.elapsed_ms(ev0, ev1) / reps
 
 
+HBM = 6.3e12     # bytes / s a streaming kernel reaches on the MI355X (8.0e12 on paper)
+
+
+def gradmom_arm(emu, e, xs, N, J, rng):
+    """--gradmom (profiles/gradmom_bench.txt; DESIGN I.18), F = 2048: at M = 8192 and 100 000 three alternating rounds of
+    paths.active_subspace(x), of the route without it -- paths.grad(x), then the contraction on the host -- and of
+    paths.value_and_grad(x) alone; then dgpamd_gradmom_tiles alone by device events, the output preallocated, at the model's
+    Dx = 5 and at a synthetic Dx = 64 (100 paths, one output), against the time to read J once at the streaming HBM rate."""
+    from dgp_amd import _lib
+    P, F, d = N * J, 2048, 5
+    pf = emu.sample_functions(sample_size=J, n_features=F)
+
+    def host_route(x):
+        g = pf.grad(x)[0]                                       # (M, Dx, P) on the host
+        return np.einsum('mdp,mep->pde', g, g) / len(x)
+    for M in (8192, 100000):
+        x = xs[M]
+        legs = [('paths.active_subspace(x)', lambda: pf.active_subspace(x)),
+                ('paths.grad(x) + host einsum', lambda: host_route(x)),
+                ('paths.value_and_grad(x)', lambda: pf.value_and_grad(x))]
+        res, C = legs[0][1](), legs[1][1]()   # warm every shape
+        legs[2][1]()
+        assert res.C.shape == (1, P, d, d) and np.abs(res.C[0] - C).max() <= 1e-9 * np.abs(C).max()
+        ms = np.zeros((3, 3))
+        for rnd in range(3):   # alternating: each round times every arm once
+            for a, (name, f) in enumerate(legs):
+                _, ms[rnd, a] = timed(f)
+                print('M = %6d, %d paths, round %d: %-30s %10.1f ms' % (M, P, rnd + 1, name, ms[rnd, a]))
+        best = ms.min(0)
+        print('M = %6d: (grad + host einsum) / active_subspace = %.2f, active_subspace / value_and_grad = %.3f (fastest round of each)'
+              % (M, best[1] / best[0], best[0] / best[2]))
+    for M, Dx in ((8192, 5), (100000, 5), (8192, 64)):
+        f, Jd, shift = e.tensor(rng.normal(size=(P, M, 1))), e.tensor(rng.normal(size=(P, M, 1, Dx))), e.zeros(P, 1)
+        part = e.gradmom_tiles(f, Jd, shift)
+        ptr = [t.data_ptr() for t in (f, Jd, shift, part)]
+        ms = device_ms(e, lambda: e._chk(_lib.lib.dgpamd_gradmom_tiles(e.h, P, M, 1, Dx, *ptr)), reps=50)
+        read, wrote = 8.0 * Jd.numel(), 8.0 * part.numel()
+        print('dgpamd_gradmom_tiles, %d paths, M = %d, K = 1, Dx = %d: %.1f us; J is %.1f MB, read once at %.1f TB/s in %.1f us '
+              '-> %.2f of the kernel time (partial sums written: %.1f MB; read + written %.2f TB/s)'
+              % (P, M, Dx, 1e3 * ms, read / 1e6, HBM / 1e12, 1e6 * read / HBM, 1e3 * read / HBM / ms, wrote / 1e6,
+                 (read + wrote) / ms / 1e9))
+
+
 def vecchia_arm(emu, xs, N, J, m, rng):
     from dgp_amd import gp, kernel
     P, F = N * J, 2048
@@ -174,6 +220,8 @@ def main():
         return grad_arm(emu, e, xs, N, J, n, rng)
     if '--vecchia' in sys.argv:
         return vecchia_arm(emu, xs, N, J, m, rng)
+    if '--gradmom' in sys.argv:
+        return gradmom_arm(emu, e, xs, N, J, rng)
     pfs = {}
     for F in ((2048,) if big_only else (2048, 8192)):
         for label in ('first', 'second'):
