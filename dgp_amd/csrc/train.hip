@@ -946,28 +946,54 @@ __device__ __forceinline__ double lik_logaddexp(double a, double b) {   // numpy
 }
 __device__ __forceinline__ double lik_log_ndtr(double x) {   // scipy.special.log_ndtr
     if (x > 0.0) return log1p(-0.5 * erfc(x * 0.7071067811865476));
-    if (x > -20.0) return log(0.5 * erfc(-x * 0.7071067811865476));
+    // log(erfc / 2) down to -35: erfc stays a normal double to x = -37, and the five-term series below is off by its next term,
+    // 10395 / x^12 -- 55 ulps of the answer at x = -20, 0.05 at x = -35
+    if (x > -35.0) return log(0.5 * erfc(-x * 0.7071067811865476));
     const double r = 1.0 / (x * x);   // asymptotic series of the Mills ratio
     const double ser = 1.0 + r * (-1.0 + r * (3.0 + r * (-15.0 + r * (105.0 + r * (-945.0)))));
     return -0.5 * x * x - log(-x) - 0.9189385332046727 + log(ser);
 }
+// log Gamma(y + size) - log Gamma(size) without the cancellation of two gammaln values of order size log size, which makes the
+// reference's expression noise (+-10^3 at size = 1e16) when a slice-sampling proposal drives the dispersion latent far negative; a
+// chain fed that noise gets trapped on spuriously high values.  Whole counts up to 64: sum_{j<y} log(size + j).  Beyond, size >= 64:
+// the difference of the two Stirling series, (size + y - 1/2) log1p(y / size) + y log(size) - y plus the difference of the
+// corrections 1/(12x) - 1/(360x^3) + 1/(1260x^5) (the next one is below 1.2e-16 from x = 64 on) -- no term larger than
+// y log(size) + lgamma(y + 1), at a cost that does not grow with y.  Beyond, size < 64: the plain difference, where lgamma(size) is
+// no larger than those terms.  Against exact values both forms stay within 2.5 units of 2^-53 (y log(size) + lgamma(y + 1)) for
+// size between 33 and 400; the plain difference leaves that from size = 3000 on (27 units, 4.8e15 at size = e^40), the series
+// below size = 20 (10 units).
+__device__ __forceinline__ double lik_stirling_corr(double x) {
+    const double r = 1.0 / (x * x);
+    return (1.0 / 12.0 - (1.0 / 360.0 - (1.0 / 1260.0) * r) * r) / x;
+}
+__device__ __forceinline__ double lik_lgamma_rise(double y, double size) {
+    if (y >= 0.0 && y <= 64.0 && y == floor(y)) {
+        double lg = 0.0;
+        for (double j = 0.0; j < y; j += 1.0) lg += log(size + j);
+        return lg;
+    }
+    if (size >= 64.0) {
+        const double x2 = size + y;
+        return (x2 - 0.5) * log1p(y / size) - y + y * log(size) + (lik_stirling_corr(x2) - lik_stirling_corr(size));
+    }
+    return lgamma(y + size) - lgamma(size);
+}
 // NegBin._logpmf (likelihood_class.py:245-292): gammaln(y + size) - gammaln(size) - gammaln(y + 1) + y a - (y + size) logaddexp(0, a),
-// size = exp(-f2), a = f1 + f2.  For counts up to 64 the first difference is evaluated as sum_{j<y} log(size + j) -- the same
-// number, without the cancellation of two gammaln values of order size log size that makes the expression noise (+-10^3 at
-// size = 1e16) when a slice-sampling proposal drives the dispersion latent far negative; a chain fed that noise gets trapped on
-// spuriously high values.  Where the reference's expression is well conditioned the two agree to rounding.
+// size = exp(-f2), a = f1 + f2, the first difference by lik_lgamma_rise.  Where the reference's expression is well conditioned the
+// two agree to rounding.
 __device__ __forceinline__ double lik_negbin(double y, double f1, double f2) {
     const double size = exp(-f2), a = f1 + f2;
-    double lg;
-    if (y >= 0.0 && y <= 64.0 && y == floor(y)) {
-        lg = 0.0;
-        for (double j = 0.0; j < y; j += 1.0) lg += log(size + j);
-    } else {
-        lg = lgamma(y + size) - lgamma(size);
-    }
-    return lg - lgamma(y + 1.0) + y * a - (y + size) * lik_logaddexp(0.0, a);
+    return lik_lgamma_rise(y, size) - lgamma(y + 1.0) + y * a - (y + size) * lik_logaddexp(0.0, a);
 }
-__device__ __forceinline__ double lik_expit(double x) { return 1.0 / (1.0 + exp(-x)); }
+// log(pi + (1 - pi) e^p) of a zero-inflated count model at y = 0: pi = expit(f), p <= 0 the base model's log-probability of a zero.
+// With q = (1 - pi)(1 - e^p), the probability of a count above zero: log1p(-q) while q < 1/2 -- there the logaddexp below is the
+// difference of two numbers that may be far larger than the answer -- and logaddexp(log pi, log(1 - pi) + p) beyond.
+// log pi = -logaddexp(0, -f) and log(1 - pi) = -logaddexp(0, f): log1p(-expit(f)) loses e^f ulps and is -inf from f = 37 on.
+__device__ __forceinline__ double lik_zero_inflated(double f, double p) {
+    const double q = -expm1(p) / (1.0 + exp(f));
+    if (q < 0.5) return log1p(-q);
+    return lik_logaddexp(-lik_logaddexp(0.0, -f), -lik_logaddexp(0.0, f) + p);
+}
 __device__ double lik_point(const LikArgs &a, const double *f, double y) {
     const int *c = a.cols;
     switch (a.kind) {
@@ -978,14 +1004,14 @@ __device__ double lik_point(const LikArgs &a, const double *f, double y) {
     case DGPAMD_LIK_NEGBIN:
         return lik_negbin(y, f[c[0]], f[c[1]]);
     case DGPAMD_LIK_ZIP: {
-        const double fl = f[c[0]], lam = exp(fl), pi = lik_expit(f[c[1]]);
-        if (y == 0.0) return lik_logaddexp(log(pi), log1p(-pi) - lam);
-        return log1p(-pi) - lam + y * fl - lgamma(y + 1.0);
+        const double fl = f[c[0]], lam = exp(fl);
+        if (y == 0.0) return lik_zero_inflated(f[c[1]], -lam);
+        return -lik_logaddexp(0.0, f[c[1]]) - lam + y * fl - lgamma(y + 1.0);
     }
     case DGPAMD_LIK_ZINB: {
-        const double nb = lik_negbin(y, f[c[0]], f[c[1]]), pi = lik_expit(f[c[2]]);
-        if (y == 0.0) return lik_logaddexp(log(pi), log1p(-pi) + nb);
-        return log1p(-pi) + nb;
+        const double nb = lik_negbin(y, f[c[0]], f[c[1]]);
+        if (y == 0.0) return lik_zero_inflated(f[c[2]], nb);
+        return -lik_logaddexp(0.0, f[c[2]]) + nb;
     }
     case DGPAMD_LIK_BIN_LOGIT: {
         const double v = f[c[0]];
@@ -1004,7 +1030,7 @@ __device__ double lik_point(const LikArgs &a, const double *f, double y) {
             if (v != v) { best = k; nan = true; }
             else if (v > top) { top = v; best = k; }
         }
-        return best == (int)y ? log(1.0 - a.par) : log(a.par / (a.classes - 1));
+        return best == (int)y ? log1p(-a.par) : log(a.par / (a.classes - 1));
     }
     default: {   // DGPAMD_LIK_SOFTMAX
         double top = f[c[0]];

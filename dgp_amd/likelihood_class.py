@@ -67,13 +67,21 @@ class NegBin(_CountLikelihood):
 
     @staticmethod
     def _lgamma_rise(y, size):
-        """log Gamma(y + size) - log Gamma(size).  For whole counts up to 64 as sum_{j<y} log(size + j), the form the device
-        log-density uses (csrc/train.hip lik_negbin): the difference of two gammaln values loses every digit once size is
-        huge (size = exp(-f2) with a wild proposal), and the host path (DGPAMD_LIK_HOST=1, plugins, pllik) must take the same
-        accept decisions as the device path."""
+        """log Gamma(y + size) - log Gamma(size) in the forms the device log-density uses (csrc/train.hip lik_lgamma_rise):
+        the difference of two gammaln values loses every digit once size is huge (size = exp(-f2) with a wild proposal), and
+        the host path (DGPAMD_LIK_HOST=1, plugins, pllik) must take the same accept decisions as the device path.  Whole counts
+        up to 64: sum_{j<y} log(size + j).  Beyond, size >= 64: the difference of the two Stirling series,
+        (size + y - 1/2) log1p(y / size) + y log(size) - y plus that of the corrections 1/(12x) - 1/(360x^3) + 1/(1260x^5) (the
+        next one is below 1.2e-16 from x = 64 on).  Beyond, size < 64: the plain difference.  The switch: against exact values
+        both forms stay within 2.5 units of 2^-53 (y log(size) + lgamma(y + 1)) for size between 33 and 400; the plain
+        difference leaves that from size = 3000 on, the series below size = 20."""
         from scipy.special import gammaln
         y, size = np.broadcast_arrays(np.asarray(y, dtype=float), np.asarray(size, dtype=float))
-        out = gammaln(y + size) - gammaln(size)
+        x2 = size + y
+        corr = lambda x: (1.0 / 12.0 - (1.0 / 360.0 - (1.0 / 1260.0) / (x * x)) / (x * x)) / x
+        with np.errstate(all='ignore'):
+            stirling = (x2 - 0.5) * np.log1p(y / size) - y + y * np.log(size) + (corr(x2) - corr(size))
+        out = np.where(size >= 64.0, stirling, gammaln(x2) - gammaln(size))
         small = (y >= 0.0) & (y <= 64.0) & (y == np.floor(y))
         if small.any():
             acc = np.zeros(y.shape)
@@ -109,6 +117,31 @@ class NegBin(_CountLikelihood):
         return np.random.negative_binomial(size, p).flatten()
 
 
+def _zero_inflated(f_pi, p):
+    """log(pi + (1 - pi) e^p) of a zero-inflated count model at y = 0 (csrc/train.hip lik_zero_inflated): pi = expit(f_pi),
+    p <= 0 the base model's log-probability of a zero.  With q = (1 - pi)(1 - e^p), the probability of a count above zero:
+    log1p(-q) while q < 1/2 -- there the logaddexp is the difference of two numbers that may be far larger than the answer --
+    and logaddexp(log pi, log(1 - pi) + p) beyond, with log pi = -logaddexp(0, -f_pi) and log(1 - pi) = -logaddexp(0, f_pi)
+    (log1p(-expit(f)) loses e^f ulps and is -inf from f = 37 on)."""
+    q = -np.expm1(p) / (1.0 + np.exp(f_pi))
+    return np.where(q < 0.5, np.log1p(-q), np.logaddexp(-np.logaddexp(0.0, -f_pi), -np.logaddexp(0.0, f_pi) + p))
+
+
+def _log_ndtr(x):
+    """log ncdf(x) as the device evaluates it (csrc/train.hip lik_log_ndtr): log1p(-erfc / 2) above 0, log(erfc / 2) down to
+    x = -35, the five-term asymptotic series of the Mills ratio below (its next term, 10395 / x^12, is 0.05 ulps of the
+    answer there and 55 at x = -20)."""
+    from scipy.special import erfc
+    x = np.asarray(x, dtype=float)
+    with np.errstate(all='ignore'):
+        r = 1.0 / (x * x)
+        ser = 1.0 + r * (-1.0 + r * (3.0 + r * (-15.0 + r * (105.0 + r * (-945.0)))))
+        tail = -0.5 * x * x - np.log(-x) - 0.9189385332046727 + np.log(ser)
+        mid = np.log(0.5 * erfc(-x * 0.7071067811865476))
+        up = np.log1p(-0.5 * erfc(x * 0.7071067811865476))
+    return np.where(x > 0.0, up, np.where(x > -35.0, mid, tail))
+
+
 class ZIP(_CountLikelihood):
     """Zero-inflated Poisson (likelihood_class.py:470-621): with probability pi = logistic(f1) a structural zero, else
     Poisson(exp(f0)); two feeding GP nodes."""
@@ -116,11 +149,11 @@ class ZIP(_CountLikelihood):
 
     @staticmethod
     def _logpmf(y, f_lam, f_pi):
-        from scipy.special import gammaln, expit
+        from scipy.special import gammaln
         with np.errstate(over='ignore', invalid='ignore', divide='ignore'):
-            lam, pi = np.exp(f_lam), expit(f_pi)
-            zero = np.logaddexp(np.log(pi), np.log1p(-pi) - lam)                       # structural or Poisson zero
-            pos = np.log1p(-pi) - lam + y * f_lam - gammaln(y + 1.0)
+            lam = np.exp(f_lam)
+            zero = _zero_inflated(f_pi, -lam)                                          # structural or Poisson zero
+            pos = -np.logaddexp(0.0, f_pi) - lam + y * f_lam - gammaln(y + 1.0)
             return np.where(y == 0, zero, pos)
 
     def llik(self):
@@ -158,11 +191,9 @@ class ZINB(_CountLikelihood):
 
     @staticmethod
     def _logpmf(y, f1, f2, f_pi):
-        from scipy.special import expit
         with np.errstate(over='ignore', invalid='ignore', divide='ignore'):
             nb = NegBin._logpmf(y, f1, f2)
-            pi = expit(f_pi)
-            return np.where(y == 0, np.logaddexp(np.log(pi), np.log1p(-pi) + nb), np.log1p(-pi) + nb)
+            return np.where(y == 0, _zero_inflated(f_pi, nb), -np.logaddexp(0.0, f_pi) + nb)
 
     def llik(self):
         return np.sum(self._logpmf(np.asarray(self.output).flatten(), self.input[:, 0], self.input[:, 1], self.input[:, 2]))
@@ -217,17 +248,16 @@ class Categorical(TrackedInputs):
 
     def _logp(self, y, f, axis):
         """log P(y | f); f has the classes (or the single latent) along `axis`, y holds class indices."""
-        from scipy.special import log_ndtr
         with np.errstate(over='ignore', invalid='ignore'):
             if self.num_classes == 2:
                 if self.link == 'logit':
                     return y * f - np.logaddexp(0, f)
-                return y * log_ndtr(f) + (1 - y) * log_ndtr(-f)
+                return y * _log_ndtr(f) + (1 - y) * _log_ndtr(-f)
             yi = np.asarray(y).astype(int)
             if self.link == 'robustmax':
                 K, eps = self.num_classes, self.robustmax_eps
                 hit = np.argmax(f, axis=axis) == yi
-                return np.where(hit, np.log(1.0 - eps), np.log(eps / (K - 1)))
+                return np.where(hit, np.log1p(-eps), np.log(eps / (K - 1)))
             top = np.max(f, axis=axis, keepdims=True)
             lse = np.log(np.sum(np.exp(f - top), axis=axis)) + np.squeeze(top, axis=axis)
             return np.squeeze(np.take_along_axis(f, np.expand_dims(yi, axis), axis=axis), axis=axis) - lse
