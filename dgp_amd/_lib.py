@@ -131,6 +131,9 @@ SIGNATURES = {
     'dgpamd_gradmom_tiles': (_i, [_p, _l, _l, _i, _i, _p, _p, _p, _p]),
     'dgpamd_boxmin_workspace': (_z, [_l, _i, _i]),
     'dgpamd_boxmin_step': (_i, [_p, _l, _i, _i, _i, _d, _p, _p, _p, _p, _p, _p, _i, _i, _i, _d, _d, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'dgpamd_boxmala_workspace': (_z, [_l, _i]),
+    'dgpamd_boxmala_step': (_i, [_p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _d, _d, _d, _d, _d, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p,
+                                 _p, _p, _p]),
 }
 
 MISSING = []

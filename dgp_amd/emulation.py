@@ -537,6 +537,14 @@ class emulator:
         res = self.sample_functions(J, n_features).minimize(bounds, output=output, maximize=maximize, **minimize_kw)
         return optimize.thompson_rows(res, batch_size, self.N, J), res
 
+    def calibrate(self, y, obs_sd, bounds, sample_size=10, n_features=2048, **calibrate_kw):
+        """Bayesian calibration: the posterior of the input x over the box bounds (Dx, 2) given an observation y of the
+        last layer's outputs with error sd obs_sd (calibrate, DESIGN I.19): draws sample_size functions per imputation
+        (sample_functions, with its refusals), samples every draw's p(x | y, f) on the device (paths.calibrate(y, obs_sd,
+        bounds, **calibrate_kw)) and returns the calibrate.PathPosterior of the N * sample_size draws; its pooled() samples
+        are the modular posterior of x (Liu, Bayarri and Berger 2009)."""
+        return self.sample_functions(sample_size, n_features).calibrate(y, obs_sd, bounds, **calibrate_kw)
+
     def sample_paths_vecchia(self, x, sample_size=50, full_layer=False, m=50):
         """sample_paths by the Vecchia factorisation of each node's joint predictive distribution (vpaths, DESIGN I.11):
         the same container and column layout, for dense and Vecchia emulators and any number of rows.  The rows of x are

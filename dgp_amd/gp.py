@@ -286,6 +286,13 @@ class gp:
         res = self.sample_functions(batch_size, n_features).minimize(bounds, output=output, maximize=maximize, **minimize_kw)
         return optimize.thompson_rows(res, batch_size, 1, batch_size), res
 
+    def calibrate(self, y, obs_sd, bounds, sample_size=10, n_features=2048, **calibrate_kw):
+        """Bayesian calibration: the posterior of the input x over the box bounds (Dx, 2) given an observation y of the
+        output with error sd obs_sd (calibrate, DESIGN I.19): draws sample_size functions (sample_functions, with its
+        refusals), samples every draw's p(x | y, f) on the device (paths.calibrate(y, obs_sd, bounds, **calibrate_kw)) and
+        returns the calibrate.PathPosterior; its pooled() samples are the modular posterior of x."""
+        return self.sample_functions(sample_size, n_features).calibrate(y, obs_sd, bounds, **calibrate_kw)
+
     def sample_paths_vecchia(self, x, sample_size=50, m=50):
         """Joint posterior draws of the GP at the rows of x by the Vecchia factorisation of the joint predictive distribution
         (vpaths): (M, sample_size) as sample_paths, for dense and Vecchia-mode models and any M.  The rows are drawn in the

@@ -21,29 +21,29 @@ from .ops import Engine
 STATUS = Engine.BOXMIN
 
 
-def check_bounds(bounds, Dx):
-    """bounds (Dx, 2) = [[low, high], ...] as (lo, hi); low == high fixes a column."""
+def check_bounds(bounds, Dx, what='minimize'):
+    """bounds (Dx, 2) = [[low, high], ...] as (lo, hi); low == high fixes a column.  what: the caller named in a refusal."""
     bounds = np.asarray(bounds, dtype=np.float64)
     if bounds.ndim != 2 or bounds.shape[1] != 2 or bounds.shape[0] < 1:
-        raise ValueError('minimize: bounds must be (Dx, 2), one [low, high] per input')
+        raise ValueError(what + ': bounds must be (Dx, 2), one [low, high] per input')
     if Dx is not None and bounds.shape[0] != Dx:
-        raise ValueError('minimize: bounds has %d rows, the draws have %d inputs' % (bounds.shape[0], Dx))
+        raise ValueError(what + ': bounds has %d rows, the draws have %d inputs' % (bounds.shape[0], Dx))
     if not np.all(np.isfinite(bounds)) or np.any(bounds[:, 1] < bounds[:, 0]):
-        raise ValueError('minimize: every bound must be finite with low <= high')
+        raise ValueError(what + ': every bound must be finite with low <= high')
     if bounds.shape[0] > 64:
-        raise ValueError('minimize: at most 64 inputs')
+        raise ValueError(what + ': at most 64 inputs')
     return np.ascontiguousarray(bounds[:, 0]), np.ascontiguousarray(bounds[:, 1])
 
 
-def candidates(lo, hi, n, seed=None, qmc=False):
+def candidates(lo, hi, n, seed=None, qmc=False, what='minimize'):
     """n rows in the box: np.random.default_rng(seed).uniform(size=(n, Dx)), or with qmc the first n points (a power of two)
     of scipy's scrambled Sobol' sequence, as sensitivity.saltelli_design takes its base samples."""
     n, D = int(n), len(lo)
     if n < 1:
-        raise ValueError('minimize: n_candidates must be at least 1')
+        raise ValueError(what + ': n_candidates must be at least 1')
     if qmc:
         if n & (n - 1):
-            raise ValueError('minimize: qmc=True needs n_candidates a power of two, got %d' % n)
+            raise ValueError(what + ': qmc=True needs n_candidates a power of two, got %d' % n)
         from scipy.stats import qmc as _qmc
         u = _qmc.Sobol(d=D, scramble=True, seed=seed).random_base2(n.bit_length() - 1)
     else:

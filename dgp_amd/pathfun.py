@@ -28,6 +28,9 @@ and Jacobian, feeds a batched projected L-BFGS on the device (optimize.minimize,
 
 paths.active_subspace(X) (DESIGN I.18) contracts the same walk's Jacobian at the rows of a design into every draw's
 E_x[grad f grad f^T] on the device (sensitivity.gradient_moments, dgpamd_gradmom_tiles): the Jacobian never visits the host.
+
+paths.calibrate(y, obs_sd, bounds) (DESIGN I.19) samples every draw's posterior of the input given an observation: the walk at
+per-path rows feeds batched MALA chains on the device (calibrate.calibrate, dgpamd_boxmala_step).
 """
 import copy
 
@@ -339,15 +342,44 @@ class PathFunctions:
         bounds, output or n_starts; NotImplementedError for draws made by sample_functions_vecchia (they are only
         piecewise differentiable: use sample_functions)."""
         from . import optimize
+        return optimize.minimize(*self._lane_problem(bounds, 'minimize'), bounds, n_starts, n_candidates, output, maximize, x0,
+                                 seed, qmc, maxiter, gtol, ftol, history, check_every, max_eval)
+
+    def calibrate(self, y, obs_sd, bounds, n_chains=4, n_samples=500, warmup=500, thin=1, n_candidates=2048, x0=None, seed=None,
+                  qmc=False, step=0.1, scale=None, prior=None, target_accept=0.574):
+        """The posterior of the input x given an observation of the outputs, for every draw, on the device (calibrate,
+        DESIGN I.19): a calibrate.PathPosterior with x (P, R, S, Dx), logp (P, R, S), P = N * sample_size draws, R =
+        n_chains chains, S = n_samples samples.  Draw p's chains sample p(x | y, f_p) proportional to prior(x) N(y; f_p(x),
+        obs_sd^2) on the box bounds (Dx, 2); result.pooled() weighs all draws equally, which is the MODULAR (cut) posterior
+        of Liu, Bayarri and Berger (2009): the emulator's uncertainty enters the calibration, the observation does not
+        re-train the emulator.  y: (K,) one value per output of the last layer, or (T, K) replicates at the same unknown x;
+        NaN marks an unobserved entry.  obs_sd: a positive scalar or (K,).  prior: None (uniform on the box) or (mean (Dx,),
+        sd (Dx,)), independent normals truncated to the box, an infinite sd flat.  The sampler is MALA with the diagonal
+        preconditioner scale (Dx,) (default high - low) and a step per chain, `step` at first, adapted over `warmup` rounds
+        towards the acceptance rate target_accept and fixed from then on; every thin-th round after warm-up is kept.  A
+        proposal outside the box is rejected.  Starts: x0 (R, Dx) shared or (P, R, Dx), projected into the box; else per draw
+        the n_chains rows of highest posterior density among n_candidates rows in the box (as minimize draws them), ties to
+        the lower row.  The normal and uniform draws come from np.random.SeedSequence(seed): the same arguments give the
+        same bits, and chain (p, r) does not depend on the chains beside it.  result.rhat and result.ess (P, Dx) are the
+        split R-hat and the effective sample size per draw; result.summary() the pooled mean and interval.  Raises
+        ValueError for an emulator with a likelihood node or a Categorical top and for bad bounds, y, obs_sd or counts;
+        NotImplementedError for draws made by sample_functions_vecchia."""
+        from . import calibrate
+        return calibrate.calibrate(*self._lane_problem(bounds, 'calibrate'), y, obs_sd, bounds, n_chains, n_samples, warmup, thin,
+                                   n_candidates, x0, seed, qmc, step, scale, prior, target_accept)
+
+    def _lane_problem(self, bounds, what):
+        """What minimize and calibrate hand to their drivers after their common refusals: (engine, P, K, Dx, values,
+        value_and_jac, width), the closures over the shared-rows walk and the walk at per-path rows."""
         self._check_differentiable()
-        _check_smooth(self.nodes.values())
+        _check_smooth(self.nodes.values(), what)
         e, P = self.engine, self.N * self.sample_size
         K, D = max(len(layer) for layer in self.layers), max(nf.Omega.shape[1] for nf in self.nodes.values())
         Dx = np.asarray(bounds).shape[0] if np.ndim(bounds) == 2 else None
         read = max(int(np.max(c)) for l, layer in enumerate(self.layers) for nd in layer
                    for c in ((nd.input_dim if l == 0 else []), ([] if nd.connect is None else nd.connect)) if len(c))
         if Dx is not None and Dx <= read:
-            raise ValueError('minimize: bounds has %d rows, the emulator reads column %d of its input' % (Dx, read))
+            raise ValueError('%s: bounds has %d rows, the emulator reads column %d of its input' % (what, Dx, read))
 
         def values(xd):
             for cur, _ in self._walk(xd):
@@ -358,8 +390,7 @@ class PathFunctions:
             for cur, J in self._walk(xt, jacobians='last'):
                 pass
             return cur, J
-        return optimize.minimize(e, P, len(self.layers[-1]), Dx, values, value_and_jac, 4 * K + 3 * D + 4, bounds, n_starts,
-                                 n_candidates, output, maximize, x0, seed, qmc, maxiter, gtol, ftol, history, check_every, max_eval)
+        return e, P, len(self.layers[-1]), Dx, values, value_and_jac, 4 * K + 3 * D + 4
 
     def active_subspace(self, X, bounds=None):
         """The second moment of every draw's input gradient over the rows of X (M, Dx), a host array, M >= 2, Dx <= 64
@@ -505,7 +536,22 @@ class GpPaths:
         """The minimum of every draw over the box bounds (Dx, 2): PathFunctions.minimize for the sample_size draws of a gp
         model (P = sample_size, one output); a column of x that the GP does not read keeps its start."""
         from . import optimize
-        _check_smooth([self.node])
+        return optimize.minimize(*self._lane_problem(bounds, 'minimize'), bounds, n_starts, n_candidates, output, maximize, x0,
+                                 seed, qmc, maxiter, gtol, ftol, history, check_every, max_eval)
+
+    def calibrate(self, y, obs_sd, bounds, n_chains=4, n_samples=500, warmup=500, thin=1, n_candidates=2048, x0=None, seed=None,
+                  qmc=False, step=0.1, scale=None, prior=None, target_accept=0.574):
+        """The posterior of the input x given an observation y (a number, (1,) or (T, 1) replicates) of the GP's output, for
+        every draw: PathFunctions.calibrate for the sample_size draws of a gp model (P = sample_size, one output), the
+        modular posterior when pooled; a column of x that the GP does not read is sampled from its prior."""
+        from . import calibrate
+        return calibrate.calibrate(*self._lane_problem(bounds, 'calibrate'), np.reshape(y, (-1, 1)) if np.ndim(y) < 2 else y,
+                                   obs_sd, bounds, n_chains, n_samples, warmup, thin, n_candidates, x0, seed, qmc, step, scale,
+                                   prior, target_accept)
+
+    def _lane_problem(self, bounds, what):
+        """PathFunctions._lane_problem for the one node of a gp model."""
+        _check_smooth([self.node], what)
         e, J = self.engine, self.sample_size
         cols = torch.as_tensor(self.columns, device=e.device)
 
@@ -519,9 +565,8 @@ class GpPaths:
             return f[:, :, None], jac[:, :, None]
         Dx = np.asarray(bounds).shape[0] if np.ndim(bounds) == 2 else None
         if Dx is not None and Dx <= int(np.max(self.columns)):
-            raise ValueError('minimize: bounds has %d rows, the model reads column %d' % (Dx, int(np.max(self.columns))))
-        return optimize.minimize(e, J, 1, Dx, values, value_and_jac, 2 + len(self.columns), bounds, n_starts, n_candidates, output,
-                                 maximize, x0, seed, qmc, maxiter, gtol, ftol, history, check_every, max_eval)
+            raise ValueError('%s: bounds has %d rows, the model reads column %d' % (what, Dx, int(np.max(self.columns))))
+        return e, J, 1, Dx, values, value_and_jac, 2 + len(self.columns)
 
     def active_subspace(self, X, bounds=None):
         """PathFunctions.active_subspace for the sample_size draws of a gp model: a sensitivity.ActiveSubspaceResult without

@@ -757,6 +757,49 @@ int dgpamd_boxmin_step(dgpamd_ctx *ctx, int64_t Q, int D, int K, int k, double s
                        int max_eval, double gtol, double ftol, int first, void *work, double *x_trial, double *x, double *fun,
                        int32_t *status, int32_t *n_iter, int32_t *n_eval, int32_t *running);
 
+/* ---- batched MALA over a box: the input posterior of function-valued draws (DESIGN I.19) ----
+ * Q independent Metropolis-adjusted Langevin chains, q = p R + r, D <= DGPAMD_MAXD columns, driven by reverse communication:
+ * a call takes the walk's values and Jacobian at the current trial points, decides every chain's pending proposal and writes
+ * the next trial points.  Nothing goes to the host; no atomics, no cross-lane operation.  The target of a chain, on the box:
+ *   lp(x) = -1/2 sum_k w_k (ybar_k - f_k(x))^2 - 1/2 sum_d pv_d (x_d - pm_d)^2
+ *   g_d   = sum_k w_k (ybar_k - f_k) J_kd - pv_d (x_d - pm_d)
+ * f (Q x K), J (Q x K x D, D fastest): device doubles, as the walk leaves them.  par: 2 K + 5 D device doubles, w (K), ybar (K),
+ * pv (D), pm (D), s (D), lo (D), hi (D) in this order; par_h: a host copy, for the checks below.  An output with w_k = 0 and a
+ * column with pv_d = 0 are not read (their f, J, ybar, pm may hold NaN).  z (Q x D) standard normal and logu (Q) log-uniform
+ * draws of this call, device doubles: the kernel has no generator.  work: dgpamd_boxmala_workspace(Q, D) bytes (a host-side
+ * formula, no GPU; 0 for sizes the step refuses), opaque, kept between the calls of one run.  x_trial (Q x D): read as the point
+ * just evaluated, overwritten with the next one; on the first call it holds the starts, which must lie in the box.
+ * State the caller may read: h (Q) the steps, logr (Q) the log acceptance ratio of the last decision, status (Q) int32
+ * DGPAMD_BOXMALA_*, n_prop, n_acc (Q) int32 decisions and acceptances.  xs (n_slots x D x Q), lps (n_slots x Q): the samples,
+ * chain fastest.  Per chain and call, in this order (tests/boxmala_ref.py restates it):
+ *   TARGET   (lp', g') at x_trial, the sums in index order, a product rounded before it enters a sum:
+ *            a += (w_k r_k) r_k, r_k = ybar_k - f_k; b += (pv_d e_d) e_d, e_d = x'_d - pm_d; lp' = -0.5 a - 0.5 b;
+ *            c_d += (w_k r_k) J_kd over k, then g'_d = c_d - pv_d e_d.
+ *   INIT     (first != 0) (x, lp, g) <- trial's; h <- h0; counts 0; lp' or g' not finite: status NAN, else OK.
+ *   DECIDE   (else; chains with status OK) the out-of-box flag set: logr = -inf; else lp' or g' not finite: logr = NaN; else
+ *            logr = (lp' - lp) + (0.5 qf - 0.5 qb), qf = sum_d u_d^2, qb = sum_d v_d^2 over the free columns,
+ *            u_d = ((x'_d - x_d) - c_d g_d) / (h s_d), v_d = ((x_d - x'_d) - c_d g'_d) / (h s_d), c_d = (0.5 (h h)) (s_d s_d).
+ *            Accept if logu < logr (a NaN comparison rejects): (x, lp, g) <- trial's.  n_prop += 1, n_acc += accepted.
+ *            adapt != 0: h <- min(max(h (accepted ? up : down), hmin), hmax).
+ *   STORE    slot >= 0: xs[slot, :, q] = x, lps[slot, q] = lp.
+ *   PROPOSE  (status OK) x'_d = (x_d + c_d g_d) + (h s_d) z_d on the free columns, x'_d = x_d on a fixed one (s_d = 0 or
+ *            lo_d = hi_d, which also leaves qf and qb); any x'_d outside [lo_d, hi_d] or not finite: the flag is set and
+ *            x_trial = x, so that the walk evaluates a finite point and the next call rejects it.  A chain with status NAN
+ *            writes x_trial = x and changes nothing more.
+ * A proposal outside the box has target density zero: rejecting it is a valid Metropolis-Hastings step for a target supported
+ * on the box (no reflection, no projection).  One lane per chain: any slice of the chains, run alone with its slice of z and
+ * logu, gives the same bits.  Products are not fused into sums (the file is built without contraction).  DGPAMD_BAD_ARG before
+ * any launch: Q < 1, D < 1 or D > DGPAMD_MAXD, K < 1, a null pointer, lo > hi or a NaN bound, a negative or NaN w, pv or s,
+ * h0, hmin, hmax, up or down not positive and finite, hmin > hmax, slot outside -1 .. n_slots - 1. */
+#define DGPAMD_BOXMALA_OK 0
+#define DGPAMD_BOXMALA_NAN 1
+#define DGPAMD_BOXMALA_COUNT 2
+size_t dgpamd_boxmala_workspace(int64_t Q, int D);
+int dgpamd_boxmala_step(dgpamd_ctx *ctx, int64_t Q, int D, int K, const double *f, const double *J, const double *par,
+                        const double *par_h, const double *z, const double *logu, double h0, double hmin, double hmax, double up,
+                        double down, int adapt, int first, int slot, int n_slots, void *work, double *x_trial, double *h,
+                        double *logr, double *xs, double *lps, int32_t *status, int32_t *n_prop, int32_t *n_acc);
+
 #ifdef __cplusplus
 }
 #endif
