@@ -134,6 +134,9 @@ SIGNATURES = {
     'dgpamd_boxmala_workspace': (_z, [_l, _i]),
     'dgpamd_boxmala_step': (_i, [_p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _d, _d, _d, _d, _d, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p,
                                  _p, _p, _p]),
+    'dgpamd_boxhmc_workspace': (_z, [_l, _i]),
+    'dgpamd_boxhmc_step': (_i, [_p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _d, _d, _d, _d, _d, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p,
+                                _p, _p, _p, _p]),
 }
 
 MISSING = []

@@ -11,6 +11,8 @@ evaluates every chain's trial point through the layer walk at per-path rows (P, 
 dgpamd_boxmala_step (one lane per chain) decides the proposals, adapts the steps during warm-up, stores the samples and writes
 the next trial points.  The normal and uniform draws come from numpy generators, uploaded in blocks of rounds; nothing visits
 the host until the end.  The starts are the best of n_candidates rows in the box, screened through the shared-rows walk.
+method='hmc' (DESIGN I.20) runs the same loop with dgpamd_boxhmc_step: an iteration is a trajectory of L leapfrog steps, one
+round each, with the walls of the box reflecting; L is n_leapfrog, or with jitter uniform on 1 .. n_leapfrog per iteration.
 """
 import warnings
 
@@ -22,6 +24,7 @@ from .ops import Engine
 
 STATUS = Engine.BOXMALA
 HMIN, HMAX = 1e-10, 1e2       # the clamp of a chain's step, in units of `scale`
+TARGET_ACCEPT = dict(mala=0.574, hmc=0.8)      # what target_accept=None means
 GAIN_DECAY = 0.6              # gamma_w = (w + 1)^-GAIN_DECAY: sum gamma = inf, sum gamma^2 < inf (Robbins and Monro)
 UPLOAD_BYTES = 1 << 25        # the normal and uniform draws of one upload
 
@@ -76,6 +79,15 @@ def check_counts(n_chains, n_samples, warmup, thin):
     if n_chains < 1 or n_samples < 1 or thin < 1 or warmup < 0:
         raise ValueError('calibrate: need n_chains >= 1, n_samples >= 1, thin >= 1 and warmup >= 0')
     return n_chains, n_samples, warmup, thin
+
+
+def trajectory_lengths(seed, iterations, n_leapfrog, jitter):
+    """(iterations,) int: the leapfrog steps of every HMC iteration, shared by all chains.  With jitter uniform on
+    1 .. n_leapfrog, from the third child of np.random.SeedSequence(seed).spawn(3), whose first two are Streams'; else
+    n_leapfrog."""
+    if not jitter:
+        return np.full(iterations, n_leapfrog, dtype=np.int64)
+    return np.random.default_rng(np.random.SeedSequence(seed).spawn(3)[2]).integers(1, n_leapfrog + 1, iterations)
 
 
 class Streams:
@@ -155,13 +167,16 @@ class PathPosterior:
     """The input posteriors of P function-valued draws, R chains of S samples each.  x (P, R, S, Dx), logp (P, R, S): the
     samples and their log posterior density up to a constant, -1/2 sum_k w_k (ybar_k - f_k(x))^2 + the log prior.
     accept_rate, step, status (P, R): the acceptance rate after warm-up, the adapted step in units of `scale`, and the
-    numbers of calibrate.STATUS (= Engine.BOXMALA, DGPAMD_BOXMALA_*): ok 0; nan 1 the start's value or gradient was not
-    finite (the chain repeats its start).  x0 (P, R, Dx): the starts.  rounds: the evaluations of the lock-step loop.
+    numbers of calibrate.STATUS (= Engine.BOXMALA, DGPAMD_BOXMALA_*; Engine.BOXHMC carries the same): ok 0; nan 1 the start's
+    value or gradient was not finite (the chain repeats its start).  x0 (P, R, Dx): the starts.  rounds: the evaluations of
+    the lock-step loop.  method 'mala' or 'hmc'; n_leapfrog: the (largest) trajectory length of 'hmc', 1 for 'mala';
+    evaluations: the walk evaluations of the run (None: rounds).
     rhat, ess (P, Dx): the split R-hat over a draw's R chains and the effective sample size of a draw's posterior mean.
     Row p is path p of the draws' container (s * sample_size + j for an emulator)."""
 
-    def __init__(self, x, logp, accept_rate, step, status, x0, rounds):
+    def __init__(self, x, logp, accept_rate, step, status, x0, rounds, method='mala', n_leapfrog=1, evaluations=None):
         self.x, self.logp, self.accept_rate, self.step, self.status, self.x0, self.rounds = x, logp, accept_rate, step, status, x0, rounds
+        self.method, self.n_leapfrog, self.evaluations = method, n_leapfrog, rounds if evaluations is None else evaluations
         self._rhat = self._ess = None
 
     @property
@@ -197,9 +212,17 @@ class PathPosterior:
 
 
 def calibrate(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, n_chains=4, n_samples=500, warmup=500, thin=1,
-              n_candidates=2048, x0=None, seed=None, qmc=False, step=0.1, scale=None, prior=None, target_accept=0.574):
+              n_candidates=2048, x0=None, seed=None, qmc=False, step=0.1, scale=None, prior=None, target_accept=None, method='mala',
+              n_leapfrog=8, jitter=True):
     """The driver behind PathFunctions.calibrate and GpPaths.calibrate; values, value_and_jac and width as in
     optimize.minimize."""
+    if method not in TARGET_ACCEPT:
+        raise ValueError("calibrate: method must be 'mala' or 'hmc'")
+    n_leapfrog = int(n_leapfrog)
+    if n_leapfrog < 1:
+        raise ValueError('calibrate: need n_leapfrog >= 1')
+    if target_accept is None:
+        target_accept = TARGET_ACCEPT[method]
     lo, hi = optimize.check_bounds(bounds, Dx, 'calibrate')
     Dx = len(lo)
     ybar, w = observation(y, obs_sd, K)
@@ -231,6 +254,9 @@ def calibrate(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, n_ch
         R = x0.shape[1]
     Q = P * R
     xt = e.tensor(np.ascontiguousarray(x0))
+    if method == 'hmc':
+        return _hmc(e, P, R, S, Dx, value_and_jac, xt, x0, (w, ybar, lo, hi, scale, pv, pm), warmup, thin, seed, step, target_accept,
+                    n_leapfrog, jitter)
     state = e.boxmala_state(Q, Dx, w, ybar, lo, hi, scale, pv, pm, n_slots=S)
     streams = Streams(seed, P, R, Dx)
     total = 1 + warmup + S * thin
@@ -247,9 +273,42 @@ def calibrate(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, n_ch
                            first=c == 0, slot=j // thin - 1 if j >= 1 and j % thin == 0 else -1)
             if c == warmup:
                 before = state['n_prop'].clone(), state['n_acc'].clone()
+    return _result(state, before, P, R, S, Dx, x0, total)
+
+
+def _result(state, before, P, R, S, Dx, x0, rounds, **kw):
     host = {k: state[k].cpu().numpy() for k in ('xs', 'lps', 'h', 'status', 'n_prop', 'n_acc')}
     n_prop, n_acc = host['n_prop'] - before[0].cpu().numpy(), host['n_acc'] - before[1].cpu().numpy()
     return PathPosterior(np.ascontiguousarray(host['xs'].reshape(S, Dx, P, R).transpose(2, 3, 0, 1)),
                          np.ascontiguousarray(host['lps'].reshape(S, P, R).transpose(1, 2, 0)),
                          (n_acc / np.maximum(n_prop, 1)).reshape(P, R), host['h'].reshape(P, R), host['status'].reshape(P, R),
-                         np.array(x0), total)
+                         np.array(x0), rounds, **kw)
+
+
+def _hmc(e, P, R, S, Dx, value_and_jac, xt, x0, target, warmup, thin, seed, step, target_accept, n_leapfrog, jitter):
+    """The lock-step loop of method='hmc'.  Iteration 0 is INIT; iteration i = 1 .. warmup + S thin is a trajectory of
+    lengths[i - 1] rounds, the last of which decides it with log u_i, adapts during warm-up and starts the next trajectory
+    with the momenta z_i (INIT: z_0): the streams are read once per iteration, in MALA's order."""
+    w, ybar, lo, hi, scale, pv, pm = target
+    state = e.boxhmc_state(P * R, Dx, w, ybar, lo, hi, scale, pv, pm, n_slots=S)
+    streams = Streams(seed, P, R, Dx)
+    total = 1 + warmup + S * thin
+    lengths = trajectory_lengths(seed, total - 1, n_leapfrog, jitter)
+    block = _rounds_per_upload(P * R, Dx)
+    before, rounds = None, 0
+    for c0 in range(0, total, block):
+        zb, ub = map(e.tensor, streams.block(min(block, total - c0)))
+        for i in range(len(zb)):
+            c = c0 + i
+            adapt, j = 1 <= c <= warmup, c - warmup
+            up, down = gain(c - 1, target_accept) if adapt else (1.0, 1.0)
+            L = 1 if c == 0 else int(lengths[c - 1])
+            for l in range(1, L + 1):
+                f, J = value_and_jac(xt)
+                last = l == L
+                e.boxhmc_step(state, f, J, xt, zb[i], ub[i], h0=step, hmin=HMIN, hmax=HMAX, up=up, down=down, adapt=adapt and last,
+                              first=c == 0, last=last, slot=j // thin - 1 if last and j >= 1 and j % thin == 0 else -1)
+            rounds += L
+            if c == warmup:
+                before = state['n_prop'].clone(), state['n_acc'].clone()
+    return _result(state, before, P, R, S, Dx, x0, rounds, method='hmc', n_leapfrog=n_leapfrog, evaluations=rounds)

@@ -30,7 +30,7 @@ paths.active_subspace(X) (DESIGN I.18) contracts the same walk's Jacobian at the
 E_x[grad f grad f^T] on the device (sensitivity.gradient_moments, dgpamd_gradmom_tiles): the Jacobian never visits the host.
 
 paths.calibrate(y, obs_sd, bounds) (DESIGN I.19) samples every draw's posterior of the input given an observation: the walk at
-per-path rows feeds batched MALA chains on the device (calibrate.calibrate, dgpamd_boxmala_step).
+per-path rows feeds batched MALA or HMC chains on the device (calibrate.calibrate, dgpamd_boxmala_step, dgpamd_boxhmc_step).
 """
 import copy
 
@@ -346,7 +346,7 @@ class PathFunctions:
                                  seed, qmc, maxiter, gtol, ftol, history, check_every, max_eval)
 
     def calibrate(self, y, obs_sd, bounds, n_chains=4, n_samples=500, warmup=500, thin=1, n_candidates=2048, x0=None, seed=None,
-                  qmc=False, step=0.1, scale=None, prior=None, target_accept=0.574):
+                  qmc=False, step=0.1, scale=None, prior=None, target_accept=None, method='mala', n_leapfrog=8, jitter=True):
         """The posterior of the input x given an observation of the outputs, for every draw, on the device (calibrate,
         DESIGN I.19): a calibrate.PathPosterior with x (P, R, S, Dx), logp (P, R, S), P = N * sample_size draws, R =
         n_chains chains, S = n_samples samples.  Draw p's chains sample p(x | y, f_p) proportional to prior(x) N(y; f_p(x),
@@ -357,8 +357,11 @@ class PathFunctions:
         sd (Dx,)), independent normals truncated to the box, an infinite sd flat.  The sampler is MALA with the diagonal
         preconditioner scale (Dx,) (default high - low) and a step per chain, `step` at first, adapted over `warmup` rounds
         towards the acceptance rate target_accept and fixed from then on; every thin-th round after warm-up is kept.  A
-        proposal outside the box is rejected.  Starts: x0 (R, Dx) shared or (P, R, Dx), projected into the box; else per draw
-        the n_chains rows of highest posterior density among n_candidates rows in the box (as minimize draws them), ties to
+        proposal outside the box is rejected.  target_accept None: 0.574 for 'mala', 0.8 for 'hmc'.  method='hmc' (DESIGN
+        I.20) samples by Hamiltonian Monte Carlo instead: an iteration is a trajectory of n_leapfrog leapfrog steps (with
+        jitter, of a length drawn uniformly from 1 .. n_leapfrog per iteration and shared by the chains), one walk
+        evaluation each, with the walls of the box reflecting; result.evaluations counts the walk evaluations.
+        Starts: x0 (R, Dx) shared or (P, R, Dx), projected into the box; else per draw the n_chains rows of highest posterior density among n_candidates rows in the box (as minimize draws them), ties to
         the lower row.  The normal and uniform draws come from np.random.SeedSequence(seed): the same arguments give the
         same bits, and chain (p, r) does not depend on the chains beside it.  result.rhat and result.ess (P, Dx) are the
         split R-hat and the effective sample size per draw; result.summary() the pooled mean and interval.  Raises
@@ -366,7 +369,8 @@ class PathFunctions:
         NotImplementedError for draws made by sample_functions_vecchia."""
         from . import calibrate
         return calibrate.calibrate(*self._lane_problem(bounds, 'calibrate'), y, obs_sd, bounds, n_chains, n_samples, warmup, thin,
-                                   n_candidates, x0, seed, qmc, step, scale, prior, target_accept)
+                                   n_candidates, x0, seed, qmc, step, scale, prior, target_accept, method, n_leapfrog,
+                                   jitter)
 
     def _lane_problem(self, bounds, what):
         """What minimize and calibrate hand to their drivers after their common refusals: (engine, P, K, Dx, values,
@@ -540,14 +544,14 @@ class GpPaths:
                                  seed, qmc, maxiter, gtol, ftol, history, check_every, max_eval)
 
     def calibrate(self, y, obs_sd, bounds, n_chains=4, n_samples=500, warmup=500, thin=1, n_candidates=2048, x0=None, seed=None,
-                  qmc=False, step=0.1, scale=None, prior=None, target_accept=0.574):
+                  qmc=False, step=0.1, scale=None, prior=None, target_accept=None, method='mala', n_leapfrog=8, jitter=True):
         """The posterior of the input x given an observation y (a number, (1,) or (T, 1) replicates) of the GP's output, for
         every draw: PathFunctions.calibrate for the sample_size draws of a gp model (P = sample_size, one output), the
         modular posterior when pooled; a column of x that the GP does not read is sampled from its prior."""
         from . import calibrate
         return calibrate.calibrate(*self._lane_problem(bounds, 'calibrate'), np.reshape(y, (-1, 1)) if np.ndim(y) < 2 else y,
                                    obs_sd, bounds, n_chains, n_samples, warmup, thin, n_candidates, x0, seed, qmc, step, scale,
-                                   prior, target_accept)
+                                   prior, target_accept, method, n_leapfrog, jitter)
 
     def _lane_problem(self, bounds, what):
         """PathFunctions._lane_problem for the one node of a gp model."""

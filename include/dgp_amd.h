@@ -800,6 +800,49 @@ int dgpamd_boxmala_step(dgpamd_ctx *ctx, int64_t Q, int D, int K, const double *
                         double down, int adapt, int first, int slot, int n_slots, void *work, double *x_trial, double *h,
                         double *logr, double *xs, double *lps, int32_t *status, int32_t *n_prop, int32_t *n_acc);
 
+/* ---- batched HMC over a box with reflecting walls (DESIGN I.20) ----
+ * Q independent Hamiltonian Monte Carlo chains on the target, the gradient, par, par_h, f, J, z, logu, the outputs and the
+ * "not read" rule of the MALA step above, unchanged.  A trajectory of L leapfrog steps takes L calls, of which only the L-th
+ * has last != 0; a run is one call with first != 0 and then the calls of its trajectories, 1 + sum L walk evaluations.  z and
+ * logu are read only by a call that starts a trajectory (z: INIT, DECIDE) or closes one (logu: DECIDE).  The walls of the box
+ * reflect (Neal 2011, 5.5.1): the map of a trajectory stays reversible and volume preserving.  A FIXED column (s_d = 0 or
+ * lo_d = hi_d) keeps x_d, has momentum 0 and is left out of every sum over d below; the others are free.  work:
+ * dgpamd_boxhmc_workspace(Q, D) = Q (8 (4 D + 2) + 4) bytes -- x, g, g', p (D x Q doubles each), lp, H0 (Q doubles), the int32
+ * flag `bad` (Q); 0 for sizes the step refuses.  Per chain and call, in this order (tests/boxhmc_ref.py restates it):
+ *   TARGET   (lp', g') at x_trial with the roundings of the MALA step's TARGET.  (chains with status OK, or first != 0)
+ *   INIT     (first != 0; last is not read) (x, lp, g) <- trial's; h <- h0; logr 0; counts 0; lp' or g' not finite: status
+ *            NAN, else OK.  Then STORE and START.
+ *   else     lp' or g' not finite and bad = 0: bad <- NONFINITE.
+ *   MID      (first = 0, last = 0) bad = 0: on every free column p_d <- p_d + (h s_d) g'_d, then DRIFT from y = x_trial.
+ *            bad != 0 (before or after): x_trial = x.  Then STORE; nothing more.
+ *   DECIDE   (first = 0, last != 0) bad = WALL: logr = -inf; bad = NONFINITE: logr = NaN; else
+ *            ke += p'_d p'_d over the free columns in index order, p'_d = p_d + (0.5 (h s_d)) g'_d;
+ *            logr = (lp' - 0.5 ke) - H0.  Accept if logu < logr (a NaN comparison rejects): (x, lp, g) <- trial's.
+ *            n_prop += 1, n_acc += accepted.  adapt != 0: h <- min(max(h (accepted ? up : down), hmin), hmax).
+ *            Then STORE and START.
+ *   STORE    slot >= 0: xs[slot, :, q] = x, lps[slot, q] = lp (in any call).
+ *   START    (status OK) with the chain's h as it is now, which every call of the trajectory uses: bad <- 0; on a free column
+ *            kz += z_d z_d, p_d <- z_d + (0.5 (h s_d)) g_d, then DRIFT from y = x; p_d = 0 on a fixed one.
+ *            H0 = lp - 0.5 kz.  bad != 0: x_trial = x.
+ *   DRIFT    of a free column: y_d <- y_d + (h s_d) p_d; then at most DGPAMD_BOXHMC_NREFL times, while y_d lies outside:
+ *            y_d > hi_d: y_d <- hi_d - (y_d - hi_d), p_d <- -p_d; else y_d < lo_d: y_d <- lo_d + (lo_d - y_d), p_d <- -p_d.
+ *            y_d then outside [lo_d, hi_d] or not finite: bad <- WALL.  Else x_trial_d = y_d.
+ * A chain with status NAN writes x_trial = x and stores; it changes nothing more.  With bad set the walk evaluates x, a finite
+ * point, and the remaining calls of the trajectory change nothing but x_trial = x; DECIDE rejects it.  A drift reflects as often
+ * forwards as backwards, so the cap keeps detailed balance.  With L = 1 (every call DECIDE + START) the proposal and the
+ * acceptance ratio are the MALA step's in exact arithmetic.  One lane per chain: any slice of the chains, run alone with its
+ * slice of z and logu, gives the same bits.  Products are not fused into sums (the file is built without contraction).
+ * DGPAMD_BAD_ARG before any launch: the MALA step's cases; first and last together are accepted. */
+#define DGPAMD_BOXHMC_OK 0
+#define DGPAMD_BOXHMC_NAN 1
+#define DGPAMD_BOXHMC_COUNT 2
+#define DGPAMD_BOXHMC_NREFL 8
+size_t dgpamd_boxhmc_workspace(int64_t Q, int D);
+int dgpamd_boxhmc_step(dgpamd_ctx *ctx, int64_t Q, int D, int K, const double *f, const double *J, const double *par,
+                       const double *par_h, const double *z, const double *logu, double h0, double hmin, double hmax, double up,
+                       double down, int adapt, int first, int last, int slot, int n_slots, void *work, double *x_trial, double *h,
+                       double *logr, double *xs, double *lps, int32_t *status, int32_t *n_prop, int32_t *n_acc);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,13 @@ Arms alternate; three rounds after a warm-up of each; medians.  Also: the share 
 events around every call of one more run; the cost of drawing and uploading the random numbers; acceptance rates, steps, split
 R-hat and ess of (a); the pooled mean of (a) against (b)'s on the paths (b) ran.
 With --long: arm (a) alone at 500 + 500 (the defaults) and 500 + 2000 rounds, its time and diagnostics, appended to the file.
-Usage: python tools/gpu_calibrate_bench.py [--long] [file that also receives the lines]"""
+With --hmc (profiles/calibrate_hmc_bench.txt; DESIGN I.20): method='hmc' beside method='mala' on the same model, starts and
+seed, at EQUAL numbers of walk evaluations -- the HMC arm's warm-up and sample iterations are the most whose trajectories fit
+into MALA's warm-up and sampling rounds.  Timing: the two arms alternate at 100 + 100 rounds, three rounds after a warm-up of
+each, medians, per walk evaluation; the step kernel's share of the HMC arm by device events.  Mixing: one run of each at
+500 + 2000 rounds (the runs are deterministic): acceptance, adapted steps, split R-hat, ess per draw and ESS PER WALK
+EVALUATION, and the ratio of the two methods' medians.
+Usage: python tools/gpu_calibrate_bench.py [--long | --hmc] [file that also receives the lines]"""
 import os
 import sys
 import time
@@ -23,7 +29,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 LONG = '--long' in sys.argv[1:]
-FILES = [a for a in sys.argv[1:] if a != '--long']
+HMC = '--hmc' in sys.argv[1:]
+FILES = [a for a in sys.argv[1:] if a not in ('--long', '--hmc')]
 LOG = open(FILES[0], 'a' if LONG else 'w') if FILES else None
 WARMUP, SAMPLES = 100, 100
 
@@ -80,6 +87,75 @@ def host_mala(pf, y, sd, bounds, x0, paths, seed=0):
     return out, calls
 
 
+def hmc_counts(seed, warm_rounds, sample_rounds, n_leapfrog=8):
+    """(warm-up iterations, sample iterations) of the HMC arm: the most whose trajectories fit into warm_rounds and then
+    sample_rounds walk evaluations."""
+    from dgp_amd import calibrate
+    spent = np.cumsum(calibrate.trajectory_lengths(seed, warm_rounds + sample_rounds, n_leapfrog, True))
+    warm = int(np.searchsorted(spent, warm_rounds, 'right'))
+    return warm, int(np.searchsorted(spent, spent[warm - 1] + sample_rounds, 'right')) - warm
+
+
+def diagnostics(name, res, ms=None):
+    per_eval = res.ess / res.evaluations
+    say('%s: %d walk evaluations, %d samples per chain%s; acceptance %.2f .. %.2f (median %.2f); steps %.3g .. %.3g (median %.3g)'
+        % (name, res.evaluations, res.x.shape[2], '' if ms is None else ', %.1f ms' % ms, res.accept_rate.min(), res.accept_rate.max(),
+           np.median(res.accept_rate), res.step.min(), res.step.max(), np.median(res.step)))
+    say('%s: split R-hat median %.3f, max %.3f; ess per draw and input (of %d samples) median %.0f, min %.0f; ess per walk evaluation '
+        'median %.4f, min %.4f' % (name, np.nanmedian(res.rhat), np.nanmax(res.rhat), res.x.shape[1] * res.x.shape[2],
+                                   np.nanmedian(res.ess), np.nanmin(res.ess), np.nanmedian(per_eval), np.nanmin(per_eval)))
+    return per_eval
+
+
+def hmc_arm(pf, e, y, sd, bounds, x0, seed=3):
+    """The --hmc report."""
+    def mala(warm, samples):
+        return pf.calibrate(y, sd, bounds, x0=x0, seed=seed, warmup=warm, n_samples=samples)
+
+    def hmc(warm, samples):
+        w, s = hmc_counts(seed, warm, samples)
+        return pf.calibrate(y, sd, bounds, x0=x0, seed=seed, warmup=w, n_samples=s, method='hmc')
+    legs = [('mala', lambda: mala(WARMUP, SAMPLES)), ('hmc', lambda: hmc(WARMUP, SAMPLES))]
+    evals = [f().evaluations for _, f in legs]                    # warm both
+    say('timing at %d + %d rounds: mala %d walk evaluations, hmc %d (%d + %d iterations of 1 .. 8 leapfrog steps)'
+        % ((WARMUP, SAMPLES, evals[0], evals[1]) + hmc_counts(seed, WARMUP, SAMPLES)))
+    ms = np.zeros((3, 2))
+    for rnd in range(3):
+        for a, (name, f) in enumerate(legs):
+            _, ms[rnd, a] = timed(f)
+            say('round %d: %-5s %10.1f ms, %.3f ms per walk evaluation' % (rnd + 1, name, ms[rnd, a], ms[rnd, a] / evals[a]))
+    med = np.median(ms, 0)
+    say('medians per walk evaluation: mala %.3f ms, hmc %.3f ms; hmc / mala = %.4f' % (med[0] / evals[0], med[1] / evals[1],
+                                                                                     med[1] / evals[1] * evals[0] / med[0]))
+    spans = []
+    step = e.boxhmc_step
+
+    def wrapped(*args, **kw):
+        ev0, ev1 = e.event(), e.event()
+        e.record(ev0)
+        out = step(*args, **kw)
+        e.record(ev1)
+        spans.append((ev0, ev1))
+        return out
+    e.boxhmc_step = wrapped
+    _, whole = timed(legs[1][1])
+    del e.boxhmc_step
+    inside = sum(e.elapsed_ms(a, c) for a, c in spans)
+    say('hmc with events: %.1f ms; %d calls of boxhmc_step: %.3f ms, %.2f %% of the run (the rest: the walk at (P, R, Dx) rows)'
+        % (whole, len(spans), inside, 100.0 * inside / whole))
+    for warm, samples in ((500, 500), (500, 2000)):
+        say('mixing at %d + %d rounds, hmc %d + %d iterations:' % ((warm, samples) + hmc_counts(seed, warm, samples)))
+        a, ms_a = timed(lambda: mala(warm, samples))
+        b, ms_b = timed(lambda: hmc(warm, samples))
+        pa, pb = diagnostics('mala', a, ms_a), diagnostics('hmc ', b, ms_b)
+        say('ess per walk evaluation, hmc / mala: of the medians %.3f, of the minima %.3f; per draw and input: median %.3f, '
+            'quartiles %.3f .. %.3f, hmc ahead in %d of %d' % ((np.nanmedian(pb) / np.nanmedian(pa), np.nanmin(pb) / np.nanmin(pa),
+                                                               np.nanmedian(pb / pa)) + tuple(np.nanquantile(pb / pa, [0.25, 0.75]))
+                                                              + (int(np.sum(pb > pa)), pa.size)))
+        say('pooled means: mala %s, hmc %s' % (np.round(a.summary()['mean'], 3), np.round(b.summary()['mean'], 3)))
+    say('not measured: hardware counters, other n_leapfrog, jitter off, other D or chain counts, thin > 1, a prior')
+
+
 def main():
     import bench
     from dgp_amd import calibrate, emulator, optimize
@@ -97,6 +173,10 @@ def main():
     pf.calibrate(y, sd, bounds, n_candidates=NC, **dict(kw, n_samples=1, warmup=0))       # (warm)
     screen, t_screen = timed(lambda: pf.calibrate(y, sd, bounds, n_candidates=NC, **dict(kw, n_samples=1, warmup=0)))
     x0 = screen.x0
+    if HMC:
+        say('n = %d, d = %d, %d paths, F = %d, %d chains per path (%d chains), box = the range of X, y = %.4g, obs_sd = %.4g'
+            % (n, d, P, F, R, P * R, y, sd))
+        return hmc_arm(pf, e, y, sd, bounds, x0)
     if LONG:
         for warm, samples in ((500, 500), (500, 2000)):
             long, ms_long = timed(lambda: pf.calibrate(y, sd, bounds, x0=x0, **dict(kw, warmup=warm, n_samples=samples)))
