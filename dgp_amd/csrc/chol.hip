@@ -219,7 +219,9 @@ __device__ __forceinline__ void store_acc(const d4 (&acc)[4], double *C, int64_t
         for (int r = 0; r < 4; ++r) C[(int64_t)(crow + 4 * r) * ld + 16 * t + ccol] = acc[t][r];
 }
 // acc = (C ? C : 0) + sign * sum over nkb consecutive 64-blocks  L_kb R_kb^T.  Software pipelined: the global loads of
-// the next half tile are in flight (registers) while the MFMAs of the current one run.  In the 64-block number
+// the next half tile are in flight (registers) while the MFMAs of the current one run.  The products of each half tile are
+// summed from zero and added to acc once (tile.hpp, FROM_ZERO; the look-ahead tasks of the one-launch kernel do the same, so
+// the two modes stay equal bit for bit).  In the 64-block number
 // mask_kb (relative to the first) the columns >= klim of both operands read as zero.
 // SC1: every global load bypasses L1 (operands handed over inside a launch: the one-launch kernel).
 // KEEP: acc is carried over from an earlier call (the panels of a visit applied in two runs, see the one-launch kernel's workers).
@@ -278,8 +280,8 @@ __device__ __forceinline__ void tile_update(d4 (&acc)[4], const double *C, const
         __syncthreads();
         // (AHEAD: the one-launch kernel's workers, two waves per SIMD -- the operand fragments requested two k-steps ahead gave
         //  the fused inverse 1-2.5 % at 6-12 matrices; the per-step kernel's four waves per SIMD hide the LDS latency themselves)
-        if (AHEAD) mfma_tile_ahead<OP_MK, OP_MK>(As, Bs, acc, wave, lane, sign);
-        else mfma_tile<OP_MK, OP_MK>(As, Bs, acc, wave, lane, sign);
+        if (AHEAD) mfma_tile_ahead<OP_MK, OP_MK, true>(As, Bs, acc, wave, lane, sign);
+        else mfma_tile<OP_MK, OP_MK, true>(As, Bs, acc, wave, lane, sign);
     }
 }
 // The pivot chain's diagonal tile in the COLUMN-BLOCK layout of diagfac.hpp (wave w: acc[t][r] = S[16t + lu + 4r][16w + lm]),
@@ -1353,7 +1355,7 @@ __global__ __launch_bounds__(256, 2) void potrf_mega_kernel(MegaArgs g) {
                         for (int r = 0; r < 4; ++r) As[(crow + 4 * r) * LDM + 16 * t + ccol] = out[2 * h + t][r];
                     commit_mk(h == 0 ? p0 : p1, Bs, tid);
                     __syncthreads();
-                    mfma_tile_ahead<OP_MK, OP_MK>(As, Bs, qt.v, wave, lane, -1.0);
+                    mfma_tile_ahead<OP_MK, OP_MK, true>(As, Bs, qt.v, wave, lane, -1.0);
                 }
                 store_acc_sc1(qt.v, Qg, ld, crow, ccol);
                 pull_next();
@@ -1383,7 +1385,7 @@ __global__ __launch_bounds__(256, 2) void potrf_mega_kernel(MegaArgs g) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) As[(crow + 4 * r) * LDM + 16 * t + ccol] = out[2 * h + t][r];
                     __syncthreads();
-                    mfma_tile_ahead<OP_MK, OP_MK>(As, As, d.v, wave, lane, -1.0);
+                    mfma_tile_ahead<OP_MK, OP_MK, true>(As, As, d.v, wave, lane, -1.0);
                 }
                 store_acc_sc1(d.v, Dg, ld, crow, ccol);
                 pull_next();

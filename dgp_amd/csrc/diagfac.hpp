@@ -207,8 +207,11 @@ __device__ __forceinline__ void diag_wave(d4 (&X)[4], d4 (&Y)[4], DiagShared &sh
                     const double nzj = -zz * rp;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const double m = (lu + 4 * r > j) ? f[(lu + 4 * r) * 17 + j] : 0.0;
-                        zv[r] = fma(m, nzj, zv[r]);
+                        // (rows <= j are final and are left alone, not updated with a zero multiplier: behind a zero or NaN
+                        //  pivot nzj is NaN, and 0 * NaN would turn the EARLIER pivots of this 16-block into NaN as well --
+                        //  info then named the block's first pivot instead of the one that failed)
+                        const double m = f[(lu + 4 * r) * 17 + j];
+                        zv[r] = (lu + 4 * r > j) ? fma(m, nzj, zv[r]) : zv[r];
                     }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) f[(lu + 4 * r) * 17 + lm] = zv[r];

@@ -102,11 +102,20 @@ __device__ __forceinline__ void commit_km(const HalfTile &f, double *__restrict_
 typedef volatile double __attribute__((address_space(3))) vlds_double;
 
 // acc[t] += sign * A(16w.., :) * B(:, 16t..)   over the KC-deep staged half tiles
-template <int OPA, int OPB>
+// FROM_ZERO: the KC products are summed from zero and added to acc once (the f64 MFMA rounds at its accumulator's magnitude
+// after every product: summed onto a tile of a trailing update whose products cancel, that is one rounding at |a_ij| per
+// product and a residual ||A - L L^T|| that grows like 0.25 sqrt(n) u; summed from zero it is one per half tile, LAPACK's
+// GEMM order -- DESIGN.md, accuracy of the factorisation).  The factorisation's updates take it in both modes alike.
+template <int OPA, int OPB, bool FROM_ZERO = false>
 __device__ __forceinline__ void mfma_tile(const double *As_, const double *Bs_, d4 acc[4], int wave, int lane,
                                           double sign) {
     const vlds_double *As = (const vlds_double *)As_, *Bs = (const vlds_double *)Bs_;
     const int m = lane & 15, kk = lane >> 4;
+    d4 part[4];
+    if (FROM_ZERO) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) part[t] = (d4){0.0, 0.0, 0.0, 0.0};
+    }
 #pragma unroll
     for (int k0 = 0; k0 < KC; k0 += 4) {
         double av = (OPA == OP_MK) ? As[(16 * wave + m) * LDM + k0 + kk] : As[(k0 + kk) * LDK + 16 * wave + m];
@@ -114,20 +123,30 @@ __device__ __forceinline__ void mfma_tile(const double *As_, const double *Bs_, 
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             double bv = (OPB == OP_MK) ? Bs[(16 * t + m) * LDM + k0 + kk] : Bs[(k0 + kk) * LDK + 16 * t + m];
-            acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[t], 0, 0, 0);
+            if (FROM_ZERO) part[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, part[t], 0, 0, 0);
+            else acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[t], 0, 0, 0);
         }
+    }
+    if (FROM_ZERO) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[t] += part[t];
     }
 }
 
 // The same product with the operand fragments requested two k-steps ahead of their MFMAs (a ring of three steps, held in
 // place by scheduling barriers): for code that runs alone on its SIMD, where a fragment read waited for in front of its
 // MFMA exposes the LDS latency.  Same operations in the same order as mfma_tile: the same bits.
-template <int OPA, int OPB>
+template <int OPA, int OPB, bool FROM_ZERO = false>
 __device__ __forceinline__ void mfma_tile_ahead(const double *As_, const double *Bs_, d4 acc[4], int wave, int lane,
                                                 double sign) {
     const vlds_double *As = (const vlds_double *)As_, *Bs = (const vlds_double *)Bs_;
     const int m = lane & 15, kk = lane >> 4;
     double av[3], bv[3][4];
+    d4 part[4];
+    if (FROM_ZERO) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) part[t] = (d4){0.0, 0.0, 0.0, 0.0};
+    }
     auto rd = [&](int s) {
         const int k0 = 4 * s, o = s % 3;
         av[o] = (OPA == OP_MK) ? As[(16 * wave + m) * LDM + k0 + kk] : As[(k0 + kk) * LDK + 16 * wave + m];
@@ -142,8 +161,15 @@ __device__ __forceinline__ void mfma_tile_ahead(const double *As_, const double 
         __builtin_amdgcn_sched_barrier(0);
         const double a = av[s % 3] * sign;
 #pragma unroll
-        for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv[s % 3][t], acc[t], 0, 0, 0);
+        for (int t = 0; t < 4; ++t) {
+            if (FROM_ZERO) part[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv[s % 3][t], part[t], 0, 0, 0);
+            else acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv[s % 3][t], acc[t], 0, 0, 0);
+        }
         __builtin_amdgcn_sched_barrier(0);
+    }
+    if (FROM_ZERO) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) acc[t] += part[t];
     }
 }
 
