@@ -254,47 +254,16 @@ def calibrate(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, n_ch
         R = x0.shape[1]
     Q = P * R
     xt = e.tensor(np.ascontiguousarray(x0))
-    if method == 'hmc':
-        return _hmc(e, P, R, S, Dx, value_and_jac, xt, x0, (w, ybar, lo, hi, scale, pv, pm), warmup, thin, seed, step, target_accept,
-                    n_leapfrog, jitter)
-    state = e.boxmala_state(Q, Dx, w, ybar, lo, hi, scale, pv, pm, n_slots=S)
+    # The lock-step loop.  Iteration 0 is INIT; iterations 1 .. warmup adapt; every thin-th one after them is saved.  An
+    # iteration reads the streams once, z_c and log u_c, and takes L_c rounds: 1 for 'mala'; for 'hmc' L_0 = 1 and then the
+    # trajectory's lengths[c - 1], of which the last round decides it with log u_c, adapts, saves and starts the next
+    # trajectory with the momenta z_c.
+    hmc = method == 'hmc'
+    state = (e.boxhmc_state if hmc else e.boxmala_state)(Q, Dx, w, ybar, lo, hi, scale, pv, pm, n_slots=S)
     streams = Streams(seed, P, R, Dx)
     total = 1 + warmup + S * thin
+    lengths = trajectory_lengths(seed, total - 1, n_leapfrog, jitter) if hmc else None
     block = _rounds_per_upload(Q, Dx)
-    before = None
-    for c0 in range(0, total, block):
-        zb, ub = map(e.tensor, streams.block(min(block, total - c0)))
-        for i in range(len(zb)):
-            c = c0 + i                              # call 0 is INIT; calls 1 .. warmup adapt; then thin calls per sample
-            f, J = value_and_jac(xt)
-            adapt, j = 1 <= c <= warmup, c - warmup
-            up, down = gain(c - 1, target_accept) if adapt else (1.0, 1.0)
-            e.boxmala_step(state, f, J, xt, zb[i], ub[i], h0=step, hmin=HMIN, hmax=HMAX, up=up, down=down, adapt=adapt,
-                           first=c == 0, slot=j // thin - 1 if j >= 1 and j % thin == 0 else -1)
-            if c == warmup:
-                before = state['n_prop'].clone(), state['n_acc'].clone()
-    return _result(state, before, P, R, S, Dx, x0, total)
-
-
-def _result(state, before, P, R, S, Dx, x0, rounds, **kw):
-    host = {k: state[k].cpu().numpy() for k in ('xs', 'lps', 'h', 'status', 'n_prop', 'n_acc')}
-    n_prop, n_acc = host['n_prop'] - before[0].cpu().numpy(), host['n_acc'] - before[1].cpu().numpy()
-    return PathPosterior(np.ascontiguousarray(host['xs'].reshape(S, Dx, P, R).transpose(2, 3, 0, 1)),
-                         np.ascontiguousarray(host['lps'].reshape(S, P, R).transpose(1, 2, 0)),
-                         (n_acc / np.maximum(n_prop, 1)).reshape(P, R), host['h'].reshape(P, R), host['status'].reshape(P, R),
-                         np.array(x0), rounds, **kw)
-
-
-def _hmc(e, P, R, S, Dx, value_and_jac, xt, x0, target, warmup, thin, seed, step, target_accept, n_leapfrog, jitter):
-    """The lock-step loop of method='hmc'.  Iteration 0 is INIT; iteration i = 1 .. warmup + S thin is a trajectory of
-    lengths[i - 1] rounds, the last of which decides it with log u_i, adapts during warm-up and starts the next trajectory
-    with the momenta z_i (INIT: z_0): the streams are read once per iteration, in MALA's order."""
-    w, ybar, lo, hi, scale, pv, pm = target
-    state = e.boxhmc_state(P * R, Dx, w, ybar, lo, hi, scale, pv, pm, n_slots=S)
-    streams = Streams(seed, P, R, Dx)
-    total = 1 + warmup + S * thin
-    lengths = trajectory_lengths(seed, total - 1, n_leapfrog, jitter)
-    block = _rounds_per_upload(P * R, Dx)
     before, rounds = None, 0
     for c0 in range(0, total, block):
         zb, ub = map(e.tensor, streams.block(min(block, total - c0)))
@@ -302,13 +271,22 @@ def _hmc(e, P, R, S, Dx, value_and_jac, xt, x0, target, warmup, thin, seed, step
             c = c0 + i
             adapt, j = 1 <= c <= warmup, c - warmup
             up, down = gain(c - 1, target_accept) if adapt else (1.0, 1.0)
-            L = 1 if c == 0 else int(lengths[c - 1])
+            L = int(lengths[c - 1]) if hmc and c > 0 else 1
             for l in range(1, L + 1):
                 f, J = value_and_jac(xt)
                 last = l == L
-                e.boxhmc_step(state, f, J, xt, zb[i], ub[i], h0=step, hmin=HMIN, hmax=HMAX, up=up, down=down, adapt=adapt and last,
-                              first=c == 0, last=last, slot=j // thin - 1 if last and j >= 1 and j % thin == 0 else -1)
+                kw = dict(h0=step, hmin=HMIN, hmax=HMAX, up=up, down=down, adapt=adapt and last, first=c == 0,
+                          slot=j // thin - 1 if last and j >= 1 and j % thin == 0 else -1)
+                if hmc:
+                    e.boxhmc_step(state, f, J, xt, zb[i], ub[i], last=last, **kw)
+                else:
+                    e.boxmala_step(state, f, J, xt, zb[i], ub[i], **kw)
             rounds += L
             if c == warmup:
                 before = state['n_prop'].clone(), state['n_acc'].clone()
-    return _result(state, before, P, R, S, Dx, x0, rounds, method='hmc', n_leapfrog=n_leapfrog, evaluations=rounds)
+    host = {k: state[k].cpu().numpy() for k in ('xs', 'lps', 'h', 'status', 'n_prop', 'n_acc')}
+    n_prop, n_acc = host['n_prop'] - before[0].cpu().numpy(), host['n_acc'] - before[1].cpu().numpy()
+    return PathPosterior(np.ascontiguousarray(host['xs'].reshape(S, Dx, P, R).transpose(2, 3, 0, 1)),
+                         np.ascontiguousarray(host['lps'].reshape(S, P, R).transpose(1, 2, 0)),
+                         (n_acc / np.maximum(n_prop, 1)).reshape(P, R), host['h'].reshape(P, R), host['status'].reshape(P, R),
+                         np.array(x0), rounds, method, n_leapfrog if hmc else 1, rounds)

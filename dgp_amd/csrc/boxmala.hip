@@ -1,178 +1,82 @@
 // Batched Metropolis-adjusted Langevin chains over one box, driven by reverse communication (DESIGN I.19), f64, for gfx950.
 //
-// Q independent chains, each sampling x in lo <= x <= hi, D <= 64 columns, from
-//   lp(x) = -1/2 sum_k w_k (ybar_k - f_k(x))^2 - 1/2 sum_d pv_d (x_d - pm_d)^2.
 // A call takes the walk's values (Q, K) and Jacobian (Q, K, D) at the trial points, decides every chain's pending proposal,
 // adapts its step, stores a sample and writes the next trial points from the caller's normal draws z.  Nothing goes to the host.
-// One lane per chain, workgroups of one wave.  Every state field lies (field..., Q), chain fastest: the lanes of a wave read
-// and write consecutive doubles.  The loops over D and K run over global memory -- a per-lane array with a runtime index
-// would live in scratch.  No LDS, no cross-lane operation, no atomics: a chain's iterates are one fixed sequence of operations
-// on its own inputs, whatever shares its wave.
-// The file is compiled with -ffp-contract=off (csrc/Makefile): every product is rounded before it enters a sum, every sum
-// runs in index order, and the kernel uses + - * / and comparisons alone, so it performs the operations of its numpy
-// restatement (tests/boxmala_ref.py) one for one.
-#include <math.h>
+// The target, the layout of par and of the workspace, the steps this kernel shares with boxhmc.hip and the roundings that
+// hold it to its numpy restatement (tests/boxmala_ref.py) are boxchain.hpp's.  Its own: the log ratio of the two proposal
+// densities, and PROPOSE.
+#include "boxchain.hpp"
 
-#include "common.hpp"
+// 0.5 qf - 0.5 qb of DECIDE: the trial was proposed from x with the step hq, and x would be proposed from the trial with it
+__device__ __forceinline__ double boxmala_proposal_ratio(const BoxchainLane &c, double hq) {
+    double qf = 0.0, qb = 0.0;
+    for (int d = 0; d < c.D; ++d) {
+        const double sd = c.sc[d];
+        if (boxchain_fixed(c, d)) continue;
+        const double e = (0.5 * (hq * hq)) * (sd * sd), hs = hq * sd, x = c.X[d * c.Q], t = c.xt[d];
+        const double u = ((t - x) - e * c.G[d * c.Q]) / hs, v = ((x - t) - e * c.GT[d * c.Q]) / hs;
+        qf = qf + u * u;
+        qb = qb + v * v;
+    }
+    return 0.5 * qf - 0.5 * qb;
+}
 
-struct BoxmalaArgs {
-    int64_t Q;
-    int D, K, first, adapt, slot;
-    double h0, hmin, hmax, up, down;
-    const double *f, *J, *par, *z, *logu;
-    double *ws, *x_trial, *h, *logr, *xs, *lps;
-    int32_t *status, *n_prop, *n_acc;
-};
-
-static size_t boxmala_ws_bytes(int64_t Q, int D) { return (size_t)Q * (8 * ((size_t)3 * D + 1) + 4); }
-
-__global__ __launch_bounds__(64) void boxmala_step_kernel(BoxmalaArgs a) {
+__global__ __launch_bounds__(64) void boxmala_step_kernel(BoxchainArgs a) {
     const int64_t q = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (q >= a.Q) return;
-    const int64_t Q = a.Q;
-    const int D = a.D, K = a.K;
-    // par: w (K), ybar (K), pv (D), pm (D), s (D), lo (D), hi (D)
-    const double *w = a.par, *yb = w + K, *pv = yb + K, *pm = pv + D, *sc = pm + D, *lo = sc + D, *hi = lo + D;
-    // the state of chain q inside the workspace; dgpamd_boxmala_workspace is the sum of these fields
-    double *X = a.ws + q, *G = X + (int64_t)D * Q, *GT = G + (int64_t)D * Q, *LP = GT + (int64_t)D * Q;
-    int32_t *FLAG = (int32_t *)(a.ws + ((int64_t)3 * D + 1) * Q) + q;
-    double *xt = a.x_trial + q * D;
-    const double *fq = a.f + q * K, *Jq = a.J + q * K * D;
-    bool live = a.first || a.status[q] == DGPAMD_BOXMALA_OK;
+    const BoxchainLane c = boxchain_lane<3, 1>(a, q);       // x, g, g'; lp; the flag: the pending proposal left the box
+    bool live = a.first || a.status[q] == BOXCHAIN_OK;
 
     if (live) {
-        // the target and its gradient at the trial point; an output with w_k = 0 and a column with pv_d = 0 are not read
-        double sa = 0.0, sb = 0.0;
-        for (int k = 0; k < K; ++k) {
-            const double wk = w[k];
-            if (wk > 0.0) {
-                const double r = yb[k] - fq[k];
-                sa = sa + (wk * r) * r;
-            }
-        }
-        for (int d = 0; d < D; ++d) {
-            const double p = pv[d];
-            if (p > 0.0) {
-                const double e = xt[d] - pm[d];
-                sb = sb + (p * e) * e;
-            }
-        }
-        const double lpt = -0.5 * sa - 0.5 * sb;
-        bool finite = isfinite(lpt);
-        for (int d = 0; d < D; ++d) {
-            double c = 0.0;
-            for (int k = 0; k < K; ++k) {
-                const double wk = w[k];
-                if (wk > 0.0) c = c + (wk * (yb[k] - fq[k])) * Jq[k * D + d];
-            }
-            const double p = pv[d];
-            if (p > 0.0) c = c - p * (xt[d] - pm[d]);
-            GT[d * Q] = c;
-            finite = finite && isfinite(c);
-        }
+        double lpt;
+        const bool finite = boxchain_target(c, lpt);
         if (a.first) {
-            // INIT
-            for (int d = 0; d < D; ++d) X[d * Q] = xt[d], G[d * Q] = GT[d * Q];
-            *LP = lpt;
-            *FLAG = 0;
-            a.h[q] = a.h0;
-            a.logr[q] = 0.0;
-            a.n_prop[q] = 0, a.n_acc[q] = 0;
-            a.status[q] = finite ? DGPAMD_BOXMALA_OK : DGPAMD_BOXMALA_NAN;
-            live = finite;
+            live = boxchain_init(a, c, lpt, finite);
         } else {
             // DECIDE: the trial was proposed with the step h the chain still holds
             const double hq = a.h[q];
             double lr;
             bool acc = false;
-            if (*FLAG) {
+            if (*c.FLAG) {
                 lr = -INFINITY;                       // outside the box: target density zero
             } else if (!finite) {
                 lr = NAN;
             } else {
-                double qf = 0.0, qb = 0.0;
-                for (int d = 0; d < D; ++d) {
-                    const double sd = sc[d];
-                    if (sd == 0.0 || lo[d] == hi[d]) continue;
-                    const double c = (0.5 * (hq * hq)) * (sd * sd), hs = hq * sd, x = X[d * Q], t = xt[d];
-                    const double u = ((t - x) - c * G[d * Q]) / hs, v = ((x - t) - c * GT[d * Q]) / hs;
-                    qf = qf + u * u;
-                    qb = qb + v * v;
-                }
-                lr = (lpt - *LP) + (0.5 * qf - 0.5 * qb);
+                const double lq = boxmala_proposal_ratio(c, hq);      // (before lp is loaded: two VGPRs fewer across the loop)
+                lr = (lpt - *c.LP) + lq;
                 acc = a.logu[q] < lr;                 // (a NaN comparison is a rejection)
             }
-            if (acc) {
-                for (int d = 0; d < D; ++d) X[d * Q] = xt[d], G[d * Q] = GT[d * Q];
-                *LP = lpt;
-            }
-            a.logr[q] = lr;
-            a.n_prop[q] = a.n_prop[q] + 1;
-            a.n_acc[q] = a.n_acc[q] + (acc ? 1 : 0);
-            if (a.adapt) a.h[q] = fmin(fmax(hq * (acc ? a.up : a.down), a.hmin), a.hmax);
+            if (acc) boxchain_commit(c, lpt);
+            boxchain_tally(a, c, hq, lr, acc);
         }
     }
-    if (a.slot >= 0) {
-        double *xs = a.xs + (int64_t)a.slot * D * Q + q;
-        for (int d = 0; d < D; ++d) xs[d * Q] = X[d * Q];
-        a.lps[(int64_t)a.slot * Q + q] = *LP;
-    }
+    boxchain_store(a, c);
     if (!live) {                                      // status NAN: the walk keeps evaluating the start
-        for (int d = 0; d < D; ++d) xt[d] = X[d * Q];
+        boxchain_hold(c);
         return;
     }
     // PROPOSE
     const double hq = a.h[q];
-    const double *zq = a.z + q * D;
+    const double *zq = a.z + q * c.D;
     int flag = 0;
-    for (int d = 0; d < D; ++d) {
-        const double sd = sc[d], l = lo[d], u = hi[d], x = X[d * Q];
+    for (int d = 0; d < c.D; ++d) {
+        const double sd = c.sc[d], l = c.lo[d], u = c.hi[d], x = c.X[d * c.Q];
         double xp = x;
-        if (!(sd == 0.0 || l == u)) xp = (x + ((0.5 * (hq * hq)) * (sd * sd)) * G[d * Q]) + (hq * sd) * zq[d];
+        if (!boxchain_fixed(c, d)) xp = (x + ((0.5 * (hq * hq)) * (sd * sd)) * c.G[d * c.Q]) + (hq * sd) * zq[d];
         if (!(xp >= l && xp <= u)) flag = 1;          // (a NaN is outside)
-        xt[d] = xp;
+        c.xt[d] = xp;
     }
-    if (flag)
-        for (int d = 0; d < D; ++d) xt[d] = X[d * Q];
-    *FLAG = flag;
+    if (flag) boxchain_hold(c);
+    *c.FLAG = flag;
 }
 
-extern "C" size_t dgpamd_boxmala_workspace(int64_t Q, int D) {
-    if (Q < 1 || Q > 0x7fffffffLL || D < 1 || D > DGPAMD_MAXD) return 0;
-    return boxmala_ws_bytes(Q, D);
-}
-
-static bool positive_finite(double v) { return v > 0.0 && v <= 1.79769313486231570815e308; }
+extern "C" size_t dgpamd_boxmala_workspace(int64_t Q, int D) { return boxchain_workspace<3, 1>(Q, D); }
 
 extern "C" int dgpamd_boxmala_step(dgpamd_ctx *ctx, int64_t Q, int D, int K, const double *f, const double *J, const double *par,
                                    const double *par_h, const double *z, const double *logu, double h0, double hmin, double hmax,
                                    double up, double down, int adapt, int first, int slot, int n_slots, void *work,
                                    double *x_trial, double *h, double *logr, double *xs, double *lps, int32_t *status,
                                    int32_t *n_prop, int32_t *n_acc) {
-    if (!ctx) return DGPAMD_BAD_ARG;
-    if (Q < 1 || Q > 0x7fffffffLL) BAD_ARG(ctx, "need 1 <= Q < 2^31");
-    if (D < 1 || D > DGPAMD_MAXD) BAD_ARG(ctx, "need 1 <= D <= DGPAMD_MAXD");
-    if (K < 1) BAD_ARG(ctx, "need K >= 1");
-    if (!f || !J || !par || !par_h || !z || !logu || !work || !x_trial || !h || !logr || !xs || !lps || !status || !n_prop || !n_acc)
-        BAD_ARG(ctx, "null pointer");
-    if (!positive_finite(h0) || !positive_finite(hmin) || !positive_finite(hmax) || !positive_finite(up) || !positive_finite(down))
-        BAD_ARG(ctx, "h0, hmin, hmax, up and down must be positive and finite");
-    if (hmin > hmax) BAD_ARG(ctx, "need hmin <= hmax");
-    if (n_slots < 0 || slot < -1 || slot >= n_slots) BAD_ARG(ctx, "need -1 <= slot < n_slots");
-    const double *w_h = par_h, *pv_h = par_h + 2 * K, *s_h = pv_h + 2 * D, *lo_h = s_h + D, *hi_h = lo_h + D;
-    for (int k = 0; k < K; ++k)
-        if (!(w_h[k] >= 0.0)) BAD_ARG(ctx, "every weight w must be a number >= 0");
-    for (int i = 0; i < D; ++i) {
-        if (!(pv_h[i] >= 0.0) || !(s_h[i] >= 0.0)) BAD_ARG(ctx, "every pv and s must be a number >= 0");
-        if (!(lo_h[i] <= hi_h[i])) BAD_ARG(ctx, "every bound must be a number with lo <= hi");
-    }
-    BoxmalaArgs a;
-    a.Q = Q, a.D = D, a.K = K, a.first = first ? 1 : 0, a.adapt = adapt ? 1 : 0, a.slot = slot;
-    a.h0 = h0, a.hmin = hmin, a.hmax = hmax, a.up = up, a.down = down;
-    a.f = f, a.J = J, a.par = par, a.z = z, a.logu = logu;
-    a.ws = (double *)work, a.x_trial = x_trial, a.h = h, a.logr = logr, a.xs = xs, a.lps = lps;
-    a.status = status, a.n_prop = n_prop, a.n_acc = n_acc;
-    hipLaunchKernelGGL(boxmala_step_kernel, dim3((unsigned)((Q + 63) / 64)), dim3(64), 0, ctx->stream, a);
-    LAUNCH_CHECK(ctx);
-    return DGPAMD_OK;
+    return boxchain_step(ctx, __func__, boxmala_step_kernel, Q, D, K, f, J, par, par_h, z, logu, h0, hmin, hmax, up, down, adapt,
+                         first, 0, slot, n_slots, work, x_trial, h, logr, xs, lps, status, n_prop, n_acc);
 }

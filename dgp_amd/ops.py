@@ -787,26 +787,18 @@ class Engine:
             _dp(state['n_eval']), _dp(state['running'])))
         return x_trial
 
-    # --------------------------------------------------------------- MALA over a box (csrc/boxmala.hip)
+    # --------------------------------------------------------------- chains over a box (csrc/boxchain.hpp: boxmala.hip, boxhmc.hip)
     BOXMALA = dict(ok=0, nan=1)
+    BOXHMC = BOXMALA
 
     @staticmethod
-    def boxmala_workspace(Q, D):
-        """Bytes of the state workspace of boxmala_step for Q chains of D columns (dgpamd_boxmala_workspace: a host-side
-        formula); sizes that the step refuses raise ValueError."""
-        nbytes = int(lib.dgpamd_boxmala_workspace(int(Q), int(D)))
+    def _chain_workspace(what, Q, D):
+        nbytes = int(getattr(lib, 'dgpamd_%s_workspace' % what)(int(Q), int(D)))
         if nbytes == 0:
-            raise ValueError('boxmala: need Q >= 1 and 1 <= D <= %d' % _lib.MAXD)
+            raise ValueError('%s: need Q >= 1 and 1 <= D <= %d' % (what, _lib.MAXD))
         return nbytes
 
-    def boxmala_state(self, Q, D, w, ybar, lo, hi, scale, prior_prec=None, prior_mean=None, n_slots=0):
-        """What one run keeps between its boxmala_step calls: the opaque workspace; par, the target and the proposal on the
-        device -- w (K), ybar (K), prior_prec (D, None: 0, the uniform prior), prior_mean (D), scale (D), lo (D), hi (D) -- and
-        par_h, its host copy; h, logr (Q) and status, n_prop, n_acc (Q) int32; the samples xs (n_slots, D, Q) and lps
-        (n_slots, Q), chain fastest."""
-        return self._chain_state('boxmala', self.boxmala_workspace, Q, D, w, ybar, lo, hi, scale, prior_prec, prior_mean, n_slots)
-
-    def _chain_state(self, what, workspace, Q, D, w, ybar, lo, hi, scale, prior_prec, prior_mean, n_slots):
+    def _chain_state(self, what, Q, D, w, ybar, lo, hi, scale, prior_prec, prior_mean, n_slots):
         w, ybar, lo, hi, scale = _f64(w), _f64(ybar), _f64(lo), _f64(hi), _f64(scale)
         pv = np.zeros(D) if prior_prec is None else _f64(prior_prec)
         pm = np.zeros(D) if prior_mean is None else _f64(prior_mean)
@@ -814,28 +806,24 @@ class Engine:
         if K < 1 or ybar.size != K or any(a.size != D for a in (lo, hi, scale, pv, pm)) or n_slots < 0:
             raise ValueError('%s: w and ybar must hold K >= 1 entries; lo, hi, scale and the prior D = %d' % (what, D))
         par = np.concatenate([w, ybar, pv, pm, scale, lo, hi])
-        return dict(work=torch.empty(workspace(Q, D), dtype=torch.uint8, device=self.device), K=K,
+        return dict(work=torch.empty(self._chain_workspace(what, Q, D), dtype=torch.uint8, device=self.device), K=K,
                     n_slots=int(n_slots), par_h=par, par=self.tensor(par), h=self.empty(Q), logr=self.empty(Q),
                     status=self.zeros(Q, dtype=torch.int32), n_prop=self.zeros(Q, dtype=torch.int32),
                     n_acc=self.zeros(Q, dtype=torch.int32), xs=self.empty(max(int(n_slots), 1), D, Q),
                     lps=self.empty(max(int(n_slots), 1), Q))
 
-    def boxmala_step(self, state, f, J, x_trial, z, logu, h0=0.1, hmin=1e-10, hmax=1e2, up=1.0, down=1.0, adapt=False,
-                     first=False, slot=-1):
-        """One call of every chain's MALA state machine (dgpamd_boxmala_step).  state: boxmala_state's; f (Q, K) or (P, R, K)
-        and J (Q, K, D) or (P, R, K, D): the walk's values and Jacobian at x_trial (Q, D) or (P, R, D); z (Q, D) or (P, R, D)
-        and logu (Q,) or (P, R): this call's draws; all contiguous float64 device tensors.  x_trial is overwritten with the
-        next trial points.  first: initialise the state from x_trial, the steps to h0.  adapt: multiply a chain's step by up
-        after an acceptance and by down after a rejection, clamped to [hmin, hmax].  slot >= 0: store the sample."""
-        Q, D, K = self._chain_shapes('boxmala', self.boxmala_workspace, state, f, J, x_trial, z, logu)
-        self._chk(self._enter() or lib.dgpamd_boxmala_step(
+    def _chain_step(self, what, state, f, J, x_trial, z, logu, h0, hmin, hmax, up, down, adapt, first, slot, last=None):
+        """dgpamd_boxmala_step or dgpamd_boxhmc_step: the one call; last is the argument that the HMC step alone takes."""
+        Q, D, K = self._chain_shapes(what, state, f, J, x_trial, z, logu)
+        flags = (1 if adapt else 0, 1 if first else 0) + (() if last is None else (1 if last else 0,))
+        self._chk(self._enter() or getattr(lib, 'dgpamd_%s_step' % what)(
             self.h, Q, D, K, _dp(f), _dp(J), _dp(state['par']), _hp(state['par_h']), _dp(z), _dp(logu), float(h0), float(hmin),
-            float(hmax), float(up), float(down), 1 if adapt else 0, 1 if first else 0, int(slot), state['n_slots'],
-            _dp(state['work']), _dp(x_trial), _dp(state['h']), _dp(state['logr']), _dp(state['xs']), _dp(state['lps']),
-            _dp(state['status']), _dp(state['n_prop']), _dp(state['n_acc'])))
+            float(hmax), float(up), float(down), *flags, int(slot), state['n_slots'], _dp(state['work']), _dp(x_trial),
+            _dp(state['h']), _dp(state['logr']), _dp(state['xs']), _dp(state['lps']), _dp(state['status']), _dp(state['n_prop']),
+            _dp(state['n_acc'])))
         return x_trial
 
-    def _chain_shapes(self, what, workspace, state, f, J, x_trial, z, logu):
+    def _chain_shapes(self, what, state, f, J, x_trial, z, logu):
         """(Q, D, K) of a chain step's tensors after the checks that boxmala_step and boxhmc_step share."""
         if x_trial.dim() not in (2, 3) or f.dim() != x_trial.dim() or J.dim() != x_trial.dim() + 1:
             raise ValueError('%s: x_trial must be (Q, D) or (P, R, D), f (..., K) and J (..., K, D) beside it' % what)
@@ -848,26 +836,44 @@ class Engine:
                                  '(..., K, D), (..., D), (...)' % what)
         sizes = dict(h=Q, logr=Q, status=Q, n_prop=Q, n_acc=Q, xs=max(state['n_slots'], 1) * D * Q, lps=max(state['n_slots'], 1) * Q,
                      par=2 * K + 5 * D)
-        if state['work'].numel() < workspace(Q, D) or state['K'] != K or state['par_h'].size != 2 * K + 5 * D or \
+        if state['work'].numel() < self._chain_workspace(what, Q, D) or state['K'] != K or state['par_h'].size != 2 * K + 5 * D or \
                 any(state[name].numel() != count for name, count in sizes.items()):
             raise ValueError('%s: the state was made for another Q, D or K' % what)
         return Q, D, K
 
-    # --------------------------------------------------------------- HMC over a box, reflecting walls (csrc/boxhmc.hip)
-    BOXHMC = dict(ok=0, nan=1)
+    # MALA (csrc/boxmala.hip)
+    @staticmethod
+    def boxmala_workspace(Q, D):
+        """Bytes of the state workspace of boxmala_step for Q chains of D columns (dgpamd_boxmala_workspace: a host-side
+        formula); sizes that the step refuses raise ValueError."""
+        return Engine._chain_workspace('boxmala', Q, D)
 
+    def boxmala_state(self, Q, D, w, ybar, lo, hi, scale, prior_prec=None, prior_mean=None, n_slots=0):
+        """What one run keeps between its boxmala_step calls: the opaque workspace; par, the target and the proposal on the
+        device -- w (K), ybar (K), prior_prec (D, None: 0, the uniform prior), prior_mean (D), scale (D), lo (D), hi (D) -- and
+        par_h, its host copy; h, logr (Q) and status, n_prop, n_acc (Q) int32; the samples xs (n_slots, D, Q) and lps
+        (n_slots, Q), chain fastest."""
+        return self._chain_state('boxmala', Q, D, w, ybar, lo, hi, scale, prior_prec, prior_mean, n_slots)
+
+    def boxmala_step(self, state, f, J, x_trial, z, logu, h0=0.1, hmin=1e-10, hmax=1e2, up=1.0, down=1.0, adapt=False,
+                     first=False, slot=-1):
+        """One call of every chain's MALA state machine (dgpamd_boxmala_step).  state: boxmala_state's; f (Q, K) or (P, R, K)
+        and J (Q, K, D) or (P, R, K, D): the walk's values and Jacobian at x_trial (Q, D) or (P, R, D); z (Q, D) or (P, R, D)
+        and logu (Q,) or (P, R): this call's draws; all contiguous float64 device tensors.  x_trial is overwritten with the
+        next trial points.  first: initialise the state from x_trial, the steps to h0.  adapt: multiply a chain's step by up
+        after an acceptance and by down after a rejection, clamped to [hmin, hmax].  slot >= 0: store the sample."""
+        return self._chain_step('boxmala', state, f, J, x_trial, z, logu, h0, hmin, hmax, up, down, adapt, first, slot)
+
+    # HMC, reflecting walls (csrc/boxhmc.hip)
     @staticmethod
     def boxhmc_workspace(Q, D):
         """Bytes of the state workspace of boxhmc_step for Q chains of D columns (dgpamd_boxhmc_workspace: a host-side
         formula); sizes that the step refuses raise ValueError."""
-        nbytes = int(lib.dgpamd_boxhmc_workspace(int(Q), int(D)))
-        if nbytes == 0:
-            raise ValueError('boxhmc: need Q >= 1 and 1 <= D <= %d' % _lib.MAXD)
-        return nbytes
+        return Engine._chain_workspace('boxhmc', Q, D)
 
     def boxhmc_state(self, Q, D, w, ybar, lo, hi, scale, prior_prec=None, prior_mean=None, n_slots=0):
         """What one run keeps between its boxhmc_step calls: boxmala_state's fields with the workspace of the HMC step."""
-        return self._chain_state('boxhmc', self.boxhmc_workspace, Q, D, w, ybar, lo, hi, scale, prior_prec, prior_mean, n_slots)
+        return self._chain_state('boxhmc', Q, D, w, ybar, lo, hi, scale, prior_prec, prior_mean, n_slots)
 
     def boxhmc_step(self, state, f, J, x_trial, z, logu, h0=0.1, hmin=1e-10, hmax=1e2, up=1.0, down=1.0, adapt=False,
                     first=False, last=False, slot=-1):
@@ -876,13 +882,7 @@ class Engine:
         to h0, and start a trajectory from the momenta z.  last: this call closes the trajectory -- the energy test against
         logu, the step's adaptation (adapt), then the start of the next trajectory from z.  Otherwise z and logu are not
         read.  slot >= 0: store the sample."""
-        Q, D, K = self._chain_shapes('boxhmc', self.boxhmc_workspace, state, f, J, x_trial, z, logu)
-        self._chk(self._enter() or lib.dgpamd_boxhmc_step(
-            self.h, Q, D, K, _dp(f), _dp(J), _dp(state['par']), _hp(state['par_h']), _dp(z), _dp(logu), float(h0), float(hmin),
-            float(hmax), float(up), float(down), 1 if adapt else 0, 1 if first else 0, 1 if last else 0, int(slot),
-            state['n_slots'], _dp(state['work']), _dp(x_trial), _dp(state['h']), _dp(state['logr']), _dp(state['xs']),
-            _dp(state['lps']), _dp(state['status']), _dp(state['n_prop']), _dp(state['n_acc'])))
-        return x_trial
+        return self._chain_step('boxhmc', state, f, J, x_trial, z, logu, h0, hmin, hmax, up, down, adapt, first, slot, bool(last))
 
     # --------------------------------------------------------------- vecchia
     def nn_ordered(self, x, m):

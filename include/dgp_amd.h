@@ -757,40 +757,50 @@ int dgpamd_boxmin_step(dgpamd_ctx *ctx, int64_t Q, int D, int K, int k, double s
                        int max_eval, double gtol, double ftol, int first, void *work, double *x_trial, double *x, double *fun,
                        int32_t *status, int32_t *n_iter, int32_t *n_eval, int32_t *running);
 
-/* ---- batched MALA over a box: the input posterior of function-valued draws (DESIGN I.19) ----
- * Q independent Metropolis-adjusted Langevin chains, q = p R + r, D <= DGPAMD_MAXD columns, driven by reverse communication:
- * a call takes the walk's values and Jacobian at the current trial points, decides every chain's pending proposal and writes
- * the next trial points.  Nothing goes to the host; no atomics, no cross-lane operation.  The target of a chain, on the box:
+/* ---- batched chains over a box: the input posterior of function-valued draws (DESIGN I.19, I.20) ----
+ * What dgpamd_boxmala_step and dgpamd_boxhmc_step below share (csrc/boxchain.hpp holds it once for both kernels).
+ * Q independent chains, q = p R + r, D <= DGPAMD_MAXD columns, driven by reverse communication: a call takes the walk's values
+ * and Jacobian at the current trial points, advances every chain's state machine and writes the next trial points.  Nothing
+ * goes to the host; no atomics, no cross-lane operation.  The target of a chain, on the box lo <= x <= hi:
  *   lp(x) = -1/2 sum_k w_k (ybar_k - f_k(x))^2 - 1/2 sum_d pv_d (x_d - pm_d)^2
  *   g_d   = sum_k w_k (ybar_k - f_k) J_kd - pv_d (x_d - pm_d)
  * f (Q x K), J (Q x K x D, D fastest): device doubles, as the walk leaves them.  par: 2 K + 5 D device doubles, w (K), ybar (K),
  * pv (D), pm (D), s (D), lo (D), hi (D) in this order; par_h: a host copy, for the checks below.  An output with w_k = 0 and a
  * column with pv_d = 0 are not read (their f, J, ybar, pm may hold NaN).  z (Q x D) standard normal and logu (Q) log-uniform
- * draws of this call, device doubles: the kernel has no generator.  work: dgpamd_boxmala_workspace(Q, D) bytes (a host-side
+ * draws of this call, device doubles: the kernels have no generator.  work: dgpamd_box*_workspace(Q, D) bytes (a host-side
  * formula, no GPU; 0 for sizes the step refuses), opaque, kept between the calls of one run.  x_trial (Q x D): read as the point
  * just evaluated, overwritten with the next one; on the first call it holds the starts, which must lie in the box.
- * State the caller may read: h (Q) the steps, logr (Q) the log acceptance ratio of the last decision, status (Q) int32
- * DGPAMD_BOXMALA_*, n_prop, n_acc (Q) int32 decisions and acceptances.  xs (n_slots x D x Q), lps (n_slots x Q): the samples,
- * chain fastest.  Per chain and call, in this order (tests/boxmala_ref.py restates it):
- *   TARGET   (lp', g') at x_trial, the sums in index order, a product rounded before it enters a sum:
- *            a += (w_k r_k) r_k, r_k = ybar_k - f_k; b += (pv_d e_d) e_d, e_d = x'_d - pm_d; lp' = -0.5 a - 0.5 b;
- *            c_d += (w_k r_k) J_kd over k, then g'_d = c_d - pv_d e_d.
- *   INIT     (first != 0) (x, lp, g) <- trial's; h <- h0; counts 0; lp' or g' not finite: status NAN, else OK.
- *   DECIDE   (else; chains with status OK) the out-of-box flag set: logr = -inf; else lp' or g' not finite: logr = NaN; else
+ * State the caller may read: h (Q) the steps, logr (Q) the log acceptance ratio of the last decision, status (Q) int32 (the
+ * two steps' DGPAMD_BOX*_OK and _NAN are the same numbers), n_prop, n_acc (Q) int32 decisions and acceptances.  xs (n_slots x
+ * D x Q), lps (n_slots x Q): the samples, chain fastest.  A FIXED column (s_d = 0 or lo_d = hi_d) keeps x_d and is left out of
+ * every sum over d of a step's own phases; the others are free.  The phases both steps run, per chain:
+ *   TARGET   (chains with status OK, or first != 0) (lp', g') at x_trial, the sums in index order, a product rounded before it
+ *            enters a sum: a += (w_k r_k) r_k, r_k = ybar_k - f_k; b += (pv_d e_d) e_d, e_d = x'_d - pm_d;
+ *            lp' = -0.5 a - 0.5 b; c_d += (w_k r_k) J_kd over k, then g'_d = c_d - pv_d e_d.
+ *   INIT     (first != 0) (x, lp, g) <- trial's; h <- h0; logr 0; counts 0; lp' or g' not finite: status NAN, else OK.
+ *   TALLY    of a decision: accept if logu < logr (a NaN comparison rejects): (x, lp, g) <- trial's.  n_prop += 1,
+ *            n_acc += accepted.  adapt != 0: h <- min(max(h (accepted ? up : down), hmin), hmax), h the step decided with.
+ *   STORE    slot >= 0: xs[slot, :, q] = x, lps[slot, q] = lp (in any call).
+ * A chain with status NAN writes x_trial = x, so that the walk evaluates a finite point, stores, and changes nothing more.
+ * One lane per chain: any slice of the chains, run alone with its slice of z and logu, gives the same bits.  Products are not
+ * fused into sums (both files are built without contraction).  DGPAMD_BAD_ARG before any launch: Q < 1, D < 1 or
+ * D > DGPAMD_MAXD, K < 1, a null pointer, lo > hi or a NaN bound, a negative or NaN w, pv or s, h0, hmin, hmax, up or down not
+ * positive and finite, hmin > hmax, slot outside -1 .. n_slots - 1.
+ *
+ * ---- batched MALA over a box (DESIGN I.19) ----
+ * Metropolis-adjusted Langevin chains: a call decides every chain's pending proposal and proposes the next.  work:
+ * dgpamd_boxmala_workspace(Q, D) = Q (8 (3 D + 1) + 4) bytes -- x, g, g' (D x Q doubles each), lp (Q doubles), the int32
+ * out-of-box flag (Q).  Per chain and call, in this order (tests/boxmala_ref.py restates it): TARGET; INIT or DECIDE; STORE;
+ * PROPOSE.
+ *   DECIDE   (first = 0; chains with status OK) the out-of-box flag set: logr = -inf; else lp' or g' not finite: logr = NaN; else
  *            logr = (lp' - lp) + (0.5 qf - 0.5 qb), qf = sum_d u_d^2, qb = sum_d v_d^2 over the free columns,
  *            u_d = ((x'_d - x_d) - c_d g_d) / (h s_d), v_d = ((x_d - x'_d) - c_d g'_d) / (h s_d), c_d = (0.5 (h h)) (s_d s_d).
- *            Accept if logu < logr (a NaN comparison rejects): (x, lp, g) <- trial's.  n_prop += 1, n_acc += accepted.
- *            adapt != 0: h <- min(max(h (accepted ? up : down), hmin), hmax).
- *   STORE    slot >= 0: xs[slot, :, q] = x, lps[slot, q] = lp.
- *   PROPOSE  (status OK) x'_d = (x_d + c_d g_d) + (h s_d) z_d on the free columns, x'_d = x_d on a fixed one (s_d = 0 or
- *            lo_d = hi_d, which also leaves qf and qb); any x'_d outside [lo_d, hi_d] or not finite: the flag is set and
- *            x_trial = x, so that the walk evaluates a finite point and the next call rejects it.  A chain with status NAN
- *            writes x_trial = x and changes nothing more.
+ *            Then TALLY.
+ *   PROPOSE  (status OK) x'_d = (x_d + c_d g_d) + (h s_d) z_d on the free columns, x'_d = x_d on a fixed one; any x'_d outside
+ *            [lo_d, hi_d] or not finite: the flag is set and x_trial = x, so that the walk evaluates a finite point and the
+ *            next call rejects it.
  * A proposal outside the box has target density zero: rejecting it is a valid Metropolis-Hastings step for a target supported
- * on the box (no reflection, no projection).  One lane per chain: any slice of the chains, run alone with its slice of z and
- * logu, gives the same bits.  Products are not fused into sums (the file is built without contraction).  DGPAMD_BAD_ARG before
- * any launch: Q < 1, D < 1 or D > DGPAMD_MAXD, K < 1, a null pointer, lo > hi or a NaN bound, a negative or NaN w, pv or s,
- * h0, hmin, hmax, up or down not positive and finite, hmin > hmax, slot outside -1 .. n_slots - 1. */
+ * on the box (no reflection, no projection). */
 #define DGPAMD_BOXMALA_OK 0
 #define DGPAMD_BOXMALA_NAN 1
 #define DGPAMD_BOXMALA_COUNT 2
@@ -801,38 +811,30 @@ int dgpamd_boxmala_step(dgpamd_ctx *ctx, int64_t Q, int D, int K, const double *
                         double *logr, double *xs, double *lps, int32_t *status, int32_t *n_prop, int32_t *n_acc);
 
 /* ---- batched HMC over a box with reflecting walls (DESIGN I.20) ----
- * Q independent Hamiltonian Monte Carlo chains on the target, the gradient, par, par_h, f, J, z, logu, the outputs and the
- * "not read" rule of the MALA step above, unchanged.  A trajectory of L leapfrog steps takes L calls, of which only the L-th
- * has last != 0; a run is one call with first != 0 and then the calls of its trajectories, 1 + sum L walk evaluations.  z and
- * logu are read only by a call that starts a trajectory (z: INIT, DECIDE) or closes one (logu: DECIDE).  The walls of the box
- * reflect (Neal 2011, 5.5.1): the map of a trajectory stays reversible and volume preserving.  A FIXED column (s_d = 0 or
- * lo_d = hi_d) keeps x_d, has momentum 0 and is left out of every sum over d below; the others are free.  work:
- * dgpamd_boxhmc_workspace(Q, D) = Q (8 (4 D + 2) + 4) bytes -- x, g, g', p (D x Q doubles each), lp, H0 (Q doubles), the int32
- * flag `bad` (Q); 0 for sizes the step refuses.  Per chain and call, in this order (tests/boxhmc_ref.py restates it):
- *   TARGET   (lp', g') at x_trial with the roundings of the MALA step's TARGET.  (chains with status OK, or first != 0)
- *   INIT     (first != 0; last is not read) (x, lp, g) <- trial's; h <- h0; logr 0; counts 0; lp' or g' not finite: status
- *            NAN, else OK.  Then STORE and START.
+ * Hamiltonian Monte Carlo chains on the shared contract above.  A trajectory of L leapfrog steps takes L calls, of which only
+ * the L-th has last != 0; a run is one call with first != 0 and then the calls of its trajectories, 1 + sum L walk evaluations.
+ * z and logu are read only by a call that starts a trajectory (z: INIT, DECIDE) or closes one (logu: DECIDE).  The walls of
+ * the box reflect (Neal 2011, 5.5.1): the map of a trajectory stays reversible and volume preserving.  A fixed column has
+ * momentum 0.  work: dgpamd_boxhmc_workspace(Q, D) = Q (8 (4 D + 2) + 4) bytes -- x, g, g', p (D x Q doubles each), lp, H0
+ * (Q doubles), the int32 flag `bad` (Q).  Per chain and call, in this order (tests/boxhmc_ref.py restates it): TARGET; INIT,
+ * MID or DECIDE; STORE; after INIT and DECIDE, START.
+ *   INIT     (first != 0; last is not read) as above.
  *   else     lp' or g' not finite and bad = 0: bad <- NONFINITE.
  *   MID      (first = 0, last = 0) bad = 0: on every free column p_d <- p_d + (h s_d) g'_d, then DRIFT from y = x_trial.
  *            bad != 0 (before or after): x_trial = x.  Then STORE; nothing more.
  *   DECIDE   (first = 0, last != 0) bad = WALL: logr = -inf; bad = NONFINITE: logr = NaN; else
  *            ke += p'_d p'_d over the free columns in index order, p'_d = p_d + (0.5 (h s_d)) g'_d;
- *            logr = (lp' - 0.5 ke) - H0.  Accept if logu < logr (a NaN comparison rejects): (x, lp, g) <- trial's.
- *            n_prop += 1, n_acc += accepted.  adapt != 0: h <- min(max(h (accepted ? up : down), hmin), hmax).
- *            Then STORE and START.
- *   STORE    slot >= 0: xs[slot, :, q] = x, lps[slot, q] = lp (in any call).
+ *            logr = (lp' - 0.5 ke) - H0.  Then TALLY, STORE and START.
  *   START    (status OK) with the chain's h as it is now, which every call of the trajectory uses: bad <- 0; on a free column
  *            kz += z_d z_d, p_d <- z_d + (0.5 (h s_d)) g_d, then DRIFT from y = x; p_d = 0 on a fixed one.
  *            H0 = lp - 0.5 kz.  bad != 0: x_trial = x.
  *   DRIFT    of a free column: y_d <- y_d + (h s_d) p_d; then at most DGPAMD_BOXHMC_NREFL times, while y_d lies outside:
  *            y_d > hi_d: y_d <- hi_d - (y_d - hi_d), p_d <- -p_d; else y_d < lo_d: y_d <- lo_d + (lo_d - y_d), p_d <- -p_d.
  *            y_d then outside [lo_d, hi_d] or not finite: bad <- WALL.  Else x_trial_d = y_d.
- * A chain with status NAN writes x_trial = x and stores; it changes nothing more.  With bad set the walk evaluates x, a finite
- * point, and the remaining calls of the trajectory change nothing but x_trial = x; DECIDE rejects it.  A drift reflects as often
- * forwards as backwards, so the cap keeps detailed balance.  With L = 1 (every call DECIDE + START) the proposal and the
- * acceptance ratio are the MALA step's in exact arithmetic.  One lane per chain: any slice of the chains, run alone with its
- * slice of z and logu, gives the same bits.  Products are not fused into sums (the file is built without contraction).
- * DGPAMD_BAD_ARG before any launch: the MALA step's cases; first and last together are accepted. */
+ * With bad set the walk evaluates x, a finite point, and the remaining calls of the trajectory change nothing but
+ * x_trial = x; DECIDE rejects it.  A drift reflects as often forwards as backwards, so the cap keeps detailed balance.  With
+ * L = 1 (every call DECIDE + START) the proposal and the acceptance ratio are the MALA step's in exact arithmetic.
+ * DGPAMD_BAD_ARG before any launch: the shared cases; first and last together are accepted. */
 #define DGPAMD_BOXHMC_OK 0
 #define DGPAMD_BOXHMC_NAN 1
 #define DGPAMD_BOXHMC_COUNT 2

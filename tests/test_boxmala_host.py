@@ -166,5 +166,5 @@ def test_status_numbers_and_workspace_match_the_header():
     for Q, D in ((0, 5), (4, 0), (4, 65), (1 << 31, 5)):
         with pytest.raises(ValueError):
             Engine.boxmala_workspace(Q, D)
-    # the other host-side checks are exercised by tools/boxmala_args_check.cpp under the sanitizers
+    # the other host-side checks are exercised by tools/boxchain_args_check.cpp under the sanitizers
     assert _lib.lib.dgpamd_boxmala_step(None, 1, 1, 1, *[None] * 6, 0.1, 1e-10, 1e2, 1.0, 1.0, 0, 1, -1, 0, *[None] * 9) == _lib.BAD_ARG
