@@ -94,7 +94,7 @@ __global__ __launch_bounds__(256) void linkprobe_kernel(int64_t count, const dou
         r = matern_Jd(X1, X2, m, v, l);
     } else if (FN == DGPAMD_LINK_JD0) {
         r = matern_Jd0(X1, m, v, l);
-    } else {   // the separable form as the pair kernels combine it (predict.hip's record layout); JSEP0: both roles on one point
+    } else {   // the separable form as the pair kernels combine it (the record layout of linkgp.hpp's REC); JSEP0: both roles on one point
         const double lo = FN == DGPAMD_LINK_JSEP ? fmin(X1, X2) : X1, hi = FN == DGPAMD_LINK_JSEP ? fmax(X1, X2) : X1;
         MaternDimConst kc;
         matern_dim_const(m, v, l, kc);

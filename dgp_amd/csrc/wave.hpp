@@ -1,5 +1,5 @@
 // Wave-level helpers shared by the one-wave-per-item kernels (the vecchia_*.hip units, train.hip,
-// predict.hip).  Everything here is forced inline: a kernel that uses one compiles to what it did with a copy of its own.
+// linkgp.hpp).  Everything here is forced inline: a kernel that uses one compiles to what it did with a copy of its own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

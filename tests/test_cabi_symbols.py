@@ -34,7 +34,7 @@ def test_library_exports_every_declared_symbol():
 
 def test_linkgp_workspace_covers_a_launch_of_the_pair_kernels(monkeypatch):
     """dgpamd_linkgp_workspace (a host-side size formula: no GPU) holds the per-tile partial sums of a workspace chunk plus the records of ONE launch
-    of the record-based pair kernels (csrc/predict.hip pair_chunk): as many test points as make 32 rounds of workgroups on 512 slots, at least
+    of the record-based pair kernels (csrc/linkgp_plan.hpp pair_chunk): as many test points as make 32 rounds of workgroups on 512 slots, at least
     256, records <= 4 GiB -- 1024 points at the bench's n = 2000, 256 at cfg3's n = 5000, all of a small call; never less than round 4's 256."""
     for v in ('DGPAMD_JSEP_TCH', 'DGPAMD_PAIR_CHUNK'):
         monkeypatch.delenv(v, raising=False)

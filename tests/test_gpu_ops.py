@@ -1110,7 +1110,7 @@ def test_linkgp_sexp_mfma_equals_direct_across_chunks(eng):
 
 @pytest.mark.parametrize('kind,n,M,Dw,Dz', [('matern2.5', 130, 4500, 3, 1), ('matern2.5', 700, 1100, 5, 0), ('sexp', 130, 4500, 3, 1)])
 def test_linkgp_launch_geometry_does_not_change_a_bit(eng, kind, n, M, Dw, Dz):
-    """Round 5: the record-based pair kernels take as many test points per launch as make >= 32 rounds of workgroups (csrc/predict.hip
+    """Round 5: the record-based pair kernels take as many test points per launch as make >= 32 rounds of workgroups (csrc/linkgp_plan.hpp
     pair_chunk; 256 before), the Matern kernel's records of a step are requested between its column tiles instead of behind the
     step's barrier, with scalar addresses.  None of that touches a pair's arithmetic: the earlier geometry (DGPAMD_PAIR_CHUNK=256,
     DGPAMD_JSEP_PIPE=0), other points per workgroup (DGPAMD_JSEP_TCH, DGPAMD_JSEXP_TCH) and a chunk that is no multiple of the workgroup's points
