@@ -137,6 +137,10 @@ SIGNATURES = {
     'dgpamd_boxhmc_workspace': (_z, [_l, _i]),
     'dgpamd_boxhmc_step': (_i, [_p, _l, _i, _i, _p, _p, _p, _p, _p, _p, _d, _d, _d, _d, _d, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p,
                                 _p, _p, _p, _p]),
+    'dgpamd_boxsmc_workspace': (_z, [_l, _l, _i]),
+    'dgpamd_boxsmc_move': (_i, [_p, _l, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _d, _d, _d, _d, _i, _i, _i, _p, _p, _p, _p, _p, _p,
+                                _p, _p, _p, _p]),
+    'dgpamd_boxsmc_temper': (_i, [_p, _l, _l, _i, _d, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
 }
 
 MISSING = []

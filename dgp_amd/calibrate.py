@@ -13,6 +13,9 @@ the next trial points.  The normal and uniform draws come from numpy generators,
 the host until the end.  The starts are the best of n_candidates rows in the box, screened through the shared-rows walk.
 method='hmc' (DESIGN I.20) runs the same loop with dgpamd_boxhmc_step: an iteration is a trajectory of L leapfrog steps, one
 round each, with the walls of the box reflecting; L is n_leapfrog, or with jitter uniform on 1 .. n_leapfrog per iteration.
+calibrate_smc (DESIGN I.21) samples the same posteriors by adaptive likelihood tempering: R particles per draw from the prior,
+reweighted, resampled (dgpamd_boxsmc_temper) and moved (dgpamd_boxsmc_move) until beta = 1; the product of the mean incremental
+weights is the draw's evidence, and ParticlePosterior can weigh the draws by it.
 """
 import warnings
 
@@ -290,3 +293,212 @@ def calibrate(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, n_ch
                          np.ascontiguousarray(host['lps'].reshape(S, P, R).transpose(1, 2, 0)),
                          (n_acc / np.maximum(n_prop, 1)).reshape(P, R), host['h'].reshape(P, R), host['status'].reshape(P, R),
                          np.array(x0), rounds, method, n_leapfrog if hmc else 1, rounds)
+
+
+# ------------------------------------------------------------------------- tempered SMC with per-draw evidence (DESIGN I.21)
+SMC_STATUS = Engine.BOXSMC
+MAX_PARTICLES = Engine.BOXSMC_MAXR
+
+
+def log_norm(y, obs_sd, K):
+    """The constant that observation's sufficient statistics drop from log N(y; f, obs_sd^2):
+    -sum_k T_k / 2 log(2 pi sd_k^2) - 1/2 sum_k sum_t (y_tk - ybar_k)^2 / sd_k^2 over the finite entries of y."""
+    ybar, w = observation(y, obs_sd, K)
+    y = np.atleast_1d(np.asarray(y, dtype=np.float64))
+    y = y[None] if y.ndim == 1 else y
+    seen = ~np.isnan(y)
+    sd2 = np.broadcast_to(np.asarray(obs_sd, dtype=np.float64), (K,)) ** 2
+    T = seen.sum(0)
+    within = np.where(seen, (np.where(seen, y, 0.0) - ybar) ** 2, 0.0).sum(0)
+    return float(-0.5 * np.sum(T * np.log(2.0 * np.pi * sd2)) - 0.5 * np.sum(within / sd2))
+
+
+def prior_draws(u, lo, hi, pv, pm):
+    """x (..., Dx) in the box with the prior's distribution from uniforms u (..., Dx) in [0, 1), by the inverse cdf: a flat
+    column (pv_d = 0) is lo + u (hi - lo); another one is N(pm_d, 1 / pv_d) truncated to [lo_d, hi_d]; lo_d = hi_d keeps it."""
+    from scipy.special import ndtr, ndtri
+    x = lo + u * (hi - lo)
+    for d in np.nonzero((pv > 0.0) & (hi > lo))[0]:
+        sd = 1.0 / np.sqrt(pv[d])
+        a, b = ndtr((lo[d] - pm[d]) / sd), ndtr((hi[d] - pm[d]) / sd)
+        x[..., d] = pm[d] + sd * ndtri(a + u[..., d] * (b - a))
+    return np.minimum(np.maximum(x, lo), hi)
+
+
+def stage_gain(stage, rate, target_accept):
+    """The factor on a draw's step after stage `stage` whose moves were accepted at `rate`: exp(rate - target_accept).  The
+    step is held fixed within a stage and is one number per draw, set from the acceptance of all the draw's particles: every
+    move is then invariant for its pi_beta.  (Adapting a slot's step after each of its own decisions, as the chains' warm-up
+    does, is not: over the 10 to 20 moves of a run the gain does not get small, the step follows the particle's own last
+    outcome, and the restatement's particle variance came out 5 % low on the line case of DESIGN I.21.)  The gain does not
+    decay: every stage has another target."""
+    return float(np.exp(rate - target_accept))
+
+
+class SmcStreams:
+    """The random numbers of an SMC run, children of np.random.SeedSequence(seed) by spawn key: (0, r) the prior uniforms of
+    particle slot r, (P, Dx); (1, r, t) and (2, r, t) the normal and the uniform draws of slot r in stage t, (P, rounds, Dx)
+    and (P, rounds), path first; (3, t) the resampling uniforms of stage t, (P,).  A generator is read path by path, so
+    path p's numbers do not depend on P, nor a slot's on R."""
+
+    def __init__(self, seed, P, R, Dx):
+        self.entropy = np.random.SeedSequence(seed).entropy
+        self.P, self.R, self.Dx, self.t = P, R, Dx, 0
+
+    def _rng(self, *key):
+        return np.random.default_rng(np.random.SeedSequence(self.entropy, spawn_key=key))
+
+    def prior_uniforms(self):
+        """(P, R, Dx) uniforms in [0, 1)."""
+        return np.stack([self._rng(0, r).random((self.P, self.Dx)) for r in range(self.R)], 1)
+
+    def stage(self, rounds):
+        """(u (P,), z (rounds, P, R, Dx), log u (rounds, P, R)) of the next stage."""
+        t, self.t = self.t, self.t + 1
+        z = np.stack([self._rng(1, r, t).standard_normal((self.P, rounds, self.Dx)) for r in range(self.R)], 1)
+        with np.errstate(divide='ignore'):
+            logu = np.log(np.stack([self._rng(2, r, t).random((self.P, rounds)) for r in range(self.R)], 1))
+        return self._rng(3, t).random(self.P), np.ascontiguousarray(z.transpose(2, 0, 1, 3)), np.ascontiguousarray(logu.transpose(2, 0, 1))
+
+
+def _weighted_quantile(v, wt, q):
+    """The q-quantile of the columns of v (n, Dx) under the weights wt (n,): the smallest value whose cumulative weight
+    reaches q."""
+    out = np.empty(v.shape[1])
+    for d in range(v.shape[1]):
+        order = np.argsort(v[:, d], kind='stable')
+        c = np.cumsum(wt[order])
+        out[d] = v[order[min(np.searchsorted(c, q * c[-1]), len(order) - 1)], d]
+    return out
+
+
+class ParticlePosterior:
+    """The input posteriors of P function-valued draws as R weighted-equal particles each, with every draw's evidence
+    (calibrate_smc, DESIGN I.21).  x (P, R, Dx): the particles at beta = 1, equally weighted samples of p(x | y, f_p);
+    loglik, logp (P, R): ll = -1/2 sum_k w_k (ybar_k - f_k(x))^2 and ll + the unnormalised log prior (PathPosterior.logp's
+    quantity).  log_evidence (P,): the estimate of log of the integral of prior(x) exp(ll_p(x)) over the box, prior the
+    NORMALISED prior on the box; log_norm: the constant the sufficient statistics drop, so that log_evidence + log_norm
+    estimates log p(y | f_p).  betas, stage_ess, accept_rate (P, T): per stage the temperature reached, the effective sample
+    size of the incremental weights and the mean acceptance of the moves; after a draw reached beta = 1, betas is 1 and
+    stage_ess NaN.  step (P, R): the adapted steps.  status (P,): calibrate.SMC_STATUS (= Engine.BOXSMC): ok 0; nan 1 no
+    particle had a finite likelihood; max_stages 2 the draw ended below beta = 1 (its particles sample pi_beta, its
+    evidence is partial).  n_stages; evaluations: the walk evaluations of the stages, n_stages (n_moves + 1) -- the one of
+    the prior particles comes on top.
+    Evidence weighting: draw_weights() is the softmax of log_evidence over the ok draws.  The draws f_p are P samples of the
+    emulator's prior-predictive functions, so weighting them by p(y | f_p) is a self-normalised importance estimate of the
+    posterior that feeds the observation back to the emulator -- over P functions only.  draw_ess = 1 / sum W^2 says how
+    many of them carry it: when it is small, the weighted answer rests on few draws and more of them are needed; pooled()
+    with equal weights stays the modular (cut) posterior."""
+
+    def __init__(self, x, loglik, logp, log_evidence, log_norm, betas, stage_ess, accept_rate, step, status, n_stages, evaluations):
+        self.x, self.loglik, self.logp, self.log_evidence, self.log_norm = x, loglik, logp, log_evidence, log_norm
+        self.betas, self.stage_ess, self.accept_rate, self.step, self.status = betas, stage_ess, accept_rate, step, status
+        self.n_stages, self.evaluations = n_stages, evaluations
+
+    def draw_weights(self):
+        """(P,): softmax of log_evidence over the draws with status ok, 0 elsewhere (all 0 if there is none)."""
+        good = (self.status == SMC_STATUS['ok']) & np.isfinite(self.log_evidence)
+        W = np.zeros(len(self.status))
+        if good.any():
+            e = np.exp(self.log_evidence[good] - self.log_evidence[good].max())
+            W[good] = e / e.sum()
+        return W
+
+    @property
+    def draw_ess(self):
+        W = self.draw_weights()
+        return 1.0 / np.sum(W * W) if W.any() else 0.0
+
+    def pooled(self):
+        """(P R, Dx): every particle of every draw with equal weight, the modular posterior of x."""
+        return self.x.reshape(-1, self.x.shape[-1])
+
+    def per_draw(self):
+        """(P, R, Dx): the particles of each draw's own posterior p(x | y, f_p)."""
+        return self.x
+
+    def pooled_weights(self, kind='evidence'):
+        """(P R,): the weights of pooled()'s rows, summing to 1: 'evidence' W_p / R, 'equal' 1 / (P R)."""
+        P, R = self.x.shape[:2]
+        if kind not in ('evidence', 'equal'):
+            raise ValueError("weights must be 'evidence' or 'equal'")
+        return np.repeat(self.draw_weights() if kind == 'evidence' else np.full(P, 1.0 / P), R) / R
+
+    def resample(self, n, seed=None, weights='evidence'):
+        """(n, Dx): rows of pooled() drawn with replacement under pooled_weights(weights)."""
+        wt = self.pooled_weights(weights)
+        if not wt.any():
+            raise ValueError('resample: no draw with status ok')
+        return self.pooled()[np.random.default_rng(seed).choice(len(wt), size=int(n), p=wt / wt.sum())]
+
+    def summary(self, level=0.95, weights='equal'):
+        """{'mean', 'lower', 'upper', 'draw_sd'} (Dx,) each: the mean and the equal-tailed interval of probability `level` of
+        the pooled particles under pooled_weights(weights), and the (weighted) standard deviation over the draws of their
+        own posterior means."""
+        if not 0.0 < level < 1.0:
+            raise ValueError('summary: level must lie in (0, 1)')
+        tail = 0.5 * (1.0 - level)
+        pooled, means = self.pooled(), self.x.mean(1)
+        if weights == 'equal':
+            return {'mean': pooled.mean(0), 'lower': np.quantile(pooled, tail, axis=0), 'upper': np.quantile(pooled, 1.0 - tail, axis=0),
+                    'draw_sd': means.std(0, ddof=1) if len(means) > 1 else np.zeros(means.shape[1])}
+        wt, W = self.pooled_weights(weights), self.draw_weights()
+        if not wt.any():
+            raise ValueError('summary: no draw with status ok')
+        mean = wt @ pooled
+        return {'mean': mean, 'lower': _weighted_quantile(pooled, wt, tail), 'upper': _weighted_quantile(pooled, wt, 1.0 - tail),
+                'draw_sd': np.sqrt(W @ (means - mean) ** 2)}
+
+
+def calibrate_smc(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, n_particles=1024, n_moves=4, ess_frac=0.5,
+                  max_stages=100, seed=None, step=0.1, scale=None, prior=None, target_accept=0.574):
+    """The driver behind PathFunctions.calibrate_smc and GpPaths.calibrate_smc: adaptive likelihood tempering (Del Moral,
+    Doucet and Jasra 2006).  A stage is dgpamd_boxsmc_temper, then n_moves + 1 walk evaluations with dgpamd_boxsmc_move
+    behind each: the start of the stage at the resampled particles, then n_moves decisions.  Only the count of draws below
+    beta = 1 visits the host, once per stage."""
+    lo, hi = optimize.check_bounds(bounds, Dx, 'calibrate_smc')
+    Dx = len(lo)
+    ybar, w = observation(y, obs_sd, K)
+    pv, pm = check_prior(prior, Dx)
+    R, n_moves, max_stages = int(n_particles), int(n_moves), int(max_stages)
+    if not 1 <= R <= MAX_PARTICLES:
+        raise ValueError('calibrate_smc: need 1 <= n_particles <= %d' % MAX_PARTICLES)
+    if n_moves < 1 or max_stages < 1:
+        raise ValueError('calibrate_smc: need n_moves >= 1 and max_stages >= 1')
+    if not 0.0 < ess_frac < 1.0:
+        raise ValueError('calibrate_smc: ess_frac must lie in (0, 1)')
+    scale = hi - lo if scale is None else np.asarray(scale, dtype=np.float64)
+    if scale.shape != (Dx,) or not np.all(np.isfinite(scale)) or np.any(scale < 0.0):
+        raise ValueError('calibrate_smc: scale must be (%d,) finite numbers >= 0' % Dx)
+    if not (np.isfinite(step) and HMIN <= step <= HMAX) or not 0.0 < target_accept < 1.0:
+        raise ValueError('calibrate_smc: need %g <= step <= %g and 0 < target_accept < 1' % (HMIN, HMAX))
+    streams = SmcStreams(seed, P, R, Dx)
+    xt = e.tensor(np.ascontiguousarray(prior_draws(streams.prior_uniforms(), lo, hi, pv, pm)))
+    state = e.boxsmc_state(P, R, Dx, w, ybar, lo, hi, scale, pv, pm, h0=step)
+    # the likelihood of the prior particles: a stage's start under beta = 0 that ends at once (z and log u are not read)
+    f, J = value_and_jac(xt)
+    e.boxsmc_move(state, f, J, xt, e.zeros(P, R, Dx), e.zeros(P, R), HMIN, HMAX, first=True, last=True)
+    betas, stage_ess, accept = [], [], []
+    for stage in range(max_stages):
+        u, zb, ub = map(e.tensor, streams.stage(n_moves + 1))
+        e.boxsmc_temper(state, xt, u, ess_frac)
+        betas.append(state['beta'].clone())
+        stage_ess.append(state['stage_ess'].clone())
+        for i in range(n_moves + 1):
+            f, J = value_and_jac(xt)
+            e.boxsmc_move(state, f, J, xt, zb[i], ub[i], HMIN, HMAX, first=i == 0, last=i == n_moves)
+        # the draw's step for the next stage, from this stage's acceptance over all its particles (see stage_gain)
+        rate = state['n_acc'].view(P, R).sum(1).double() / state['n_prop'].view(P, R).sum(1).clamp(min=1).double()
+        accept.append(rate)
+        state['h'].view(P, R).mul_(torch.exp(rate - target_accept)[:, None]).clamp_(HMIN, HMAX)
+        if int(state['running'].item()) == 0:
+            break
+    host = {k: state[k].cpu().numpy() for k in ('x', 'll', 'lprior', 'h', 'beta', 'log_evidence', 'draw_status')}
+    status = host['draw_status'].copy()
+    status[(status == SMC_STATUS['ok']) & (host['beta'] < 1.0)] = SMC_STATUS['max_stages']
+    T = len(betas)
+    stack = lambda ts: np.ascontiguousarray(torch.stack(ts, 1).cpu().numpy())
+    ll = host['ll'].reshape(P, R)
+    return ParticlePosterior(np.ascontiguousarray(host['x'].reshape(Dx, P, R).transpose(1, 2, 0)), ll,
+                             ll + host['lprior'].reshape(P, R), host['log_evidence'], log_norm(y, obs_sd, K), stack(betas),
+                             stack(stage_ess), stack(accept), host['h'].reshape(P, R), status, T, T * (n_moves + 1))

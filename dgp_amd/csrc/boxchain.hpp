@@ -2,6 +2,7 @@
 // once: the arguments of a call, the layout of par and of a chain's state inside the workspace, the target and its gradient at
 // the trial point, INIT, the commit of an accepted trial, the tally of a decision with the step's adaptation, the sample
 // store, the hold of a chain that does not move, and on the host the argument checks and the launch.
+// boxsmc.hip (DESIGN I.21) builds its tempered move on the lane, the commit, the tally, the hold and the argument checks.
 //
 // Q independent chains, each sampling x in lo <= x <= hi, D <= 64 columns, from
 //   lp(x) = -1/2 sum_k w_k (ybar_k - f_k(x))^2 - 1/2 sum_d pv_d (x_d - pm_d)^2.
@@ -149,8 +150,9 @@ __device__ __forceinline__ void boxchain_hold(const BoxchainLane &c) {
 
 static bool positive_finite(double v) { return v > 0.0 && v <= 1.79769313486231570815e308; }
 
-// The host side of a step: every refusal (under the name `who` of the entry point), the arguments, the launch
-static int boxchain_step(dgpamd_ctx *ctx, const char *who, void (*kernel)(BoxchainArgs), int64_t Q, int D, int K, const double *f,
+// The host side of a step before its launch: every refusal (under the name `who` of the entry point), then the arguments into a
+// (boxsmc.hip launches a kernel with arguments of its own behind them)
+static int boxchain_args(dgpamd_ctx *ctx, const char *who, BoxchainArgs &a, int64_t Q, int D, int K, const double *f,
                          const double *J, const double *par, const double *par_h, const double *z, const double *logu, double h0,
                          double hmin, double hmax, double up, double down, int adapt, int first, int last, int slot, int n_slots,
                          void *work, double *x_trial, double *h, double *logr, double *xs, double *lps, int32_t *status,
@@ -178,12 +180,24 @@ static int boxchain_step(dgpamd_ctx *ctx, const char *who, void (*kernel)(Boxcha
         if (!(lo_h[i] <= hi_h[i])) BOXCHAIN_BAD("every bound must be a number with lo <= hi");
     }
 #undef BOXCHAIN_BAD
-    BoxchainArgs a;
     a.Q = Q, a.D = D, a.K = K, a.first = first ? 1 : 0, a.last = last ? 1 : 0, a.adapt = adapt ? 1 : 0, a.slot = slot;
     a.h0 = h0, a.hmin = hmin, a.hmax = hmax, a.up = up, a.down = down;
     a.f = f, a.J = J, a.par = par, a.z = z, a.logu = logu;
     a.ws = (double *)work, a.x_trial = x_trial, a.h = h, a.logr = logr, a.xs = xs, a.lps = lps;
     a.status = status, a.n_prop = n_prop, a.n_acc = n_acc;
+    return DGPAMD_OK;
+}
+
+// The host side of a step: the refusals, the arguments, the launch
+static int boxchain_step(dgpamd_ctx *ctx, const char *who, void (*kernel)(BoxchainArgs), int64_t Q, int D, int K, const double *f,
+                         const double *J, const double *par, const double *par_h, const double *z, const double *logu, double h0,
+                         double hmin, double hmax, double up, double down, int adapt, int first, int last, int slot, int n_slots,
+                         void *work, double *x_trial, double *h, double *logr, double *xs, double *lps, int32_t *status,
+                         int32_t *n_prop, int32_t *n_acc) {
+    BoxchainArgs a;
+    const int rc = boxchain_args(ctx, who, a, Q, D, K, f, J, par, par_h, z, logu, h0, hmin, hmax, up, down, adapt, first, last, slot,
+                                 n_slots, work, x_trial, h, logr, xs, lps, status, n_prop, n_acc);
+    if (rc != DGPAMD_OK) return rc;
     hipLaunchKernelGGL(kernel, dim3((unsigned)((Q + 63) / 64)), dim3(64), 0, ctx->stream, a);
     LAUNCH_CHECK(ctx);
     return DGPAMD_OK;

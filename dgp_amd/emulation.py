@@ -545,6 +545,12 @@ class emulator:
         are the modular posterior of x (Liu, Bayarri and Berger 2009)."""
         return self.sample_functions(sample_size, n_features).calibrate(y, obs_sd, bounds, **calibrate_kw)
 
+    def calibrate_smc(self, y, obs_sd, bounds, sample_size=10, n_features=2048, **smc_kw):
+        """calibrate by tempered sequential Monte Carlo (DESIGN I.21): draws sample_size functions per imputation and
+        returns the calibrate.ParticlePosterior of paths.calibrate_smc(y, obs_sd, bounds, **smc_kw): every draw's
+        particles and evidence; draw_weights() weighs the draws by it, pooled() is the modular posterior."""
+        return self.sample_functions(sample_size, n_features).calibrate_smc(y, obs_sd, bounds, **smc_kw)
+
     def sample_paths_vecchia(self, x, sample_size=50, full_layer=False, m=50):
         """sample_paths by the Vecchia factorisation of each node's joint predictive distribution (vpaths, DESIGN I.11):
         the same container and column layout, for dense and Vecchia emulators and any number of rows.  The rows of x are

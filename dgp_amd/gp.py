@@ -293,6 +293,12 @@ class gp:
         returns the calibrate.PathPosterior; its pooled() samples are the modular posterior of x."""
         return self.sample_functions(sample_size, n_features).calibrate(y, obs_sd, bounds, **calibrate_kw)
 
+    def calibrate_smc(self, y, obs_sd, bounds, sample_size=10, n_features=2048, **smc_kw):
+        """calibrate by tempered sequential Monte Carlo (DESIGN I.21): draws sample_size functions and returns the
+        calibrate.ParticlePosterior of paths.calibrate_smc(y, obs_sd, bounds, **smc_kw): every draw's particles and
+        evidence."""
+        return self.sample_functions(sample_size, n_features).calibrate_smc(y, obs_sd, bounds, **smc_kw)
+
     def sample_paths_vecchia(self, x, sample_size=50, m=50):
         """Joint posterior draws of the GP at the rows of x by the Vecchia factorisation of the joint predictive distribution
         (vpaths): (M, sample_size) as sample_paths, for dense and Vecchia-mode models and any M.  The rows are drawn in the

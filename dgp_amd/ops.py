@@ -884,6 +884,84 @@ class Engine:
         read.  slot >= 0: store the sample."""
         return self._chain_step('boxhmc', state, f, J, x_trial, z, logu, h0, hmin, hmax, up, down, adapt, first, slot, bool(last))
 
+    # tempered SMC (csrc/boxsmc.hip)
+    BOXSMC = dict(ok=0, nan=1, max_stages=2)
+    BOXSMC_MAXR = 8192
+
+    @staticmethod
+    def boxsmc_workspace(P, R, D):
+        """Bytes of the workspace of boxsmc_move for P draws of R particles of D columns (dgpamd_boxsmc_workspace: a
+        host-side formula); sizes that the calls refuse raise ValueError."""
+        nbytes = int(lib.dgpamd_boxsmc_workspace(int(P), int(R), int(D)))
+        if nbytes == 0:
+            raise ValueError('boxsmc: need P >= 1, 1 <= R <= %d and 1 <= D <= %d' % (Engine.BOXSMC_MAXR, _lib.MAXD))
+        return nbytes
+
+    def boxsmc_state(self, P, R, D, w, ybar, lo, hi, scale, prior_prec=None, prior_mean=None, h0=0.1):
+        """What one run keeps between its boxsmc_move and boxsmc_temper calls: the move's opaque workspace, par and par_h as
+        boxmala_state; per particle x (D, Q) particle fastest, ll, lprior, h (filled with h0), logr (Q) and status, n_prop,
+        n_acc (Q) int32, Q = P R; per draw beta (zeros), dbeta, log_evidence (zeros), stage_ess (P), draw_status (P) int32,
+        anc (P, R) int32; running (1,) int32."""
+        w, ybar, lo, hi, scale = _f64(w), _f64(ybar), _f64(lo), _f64(hi), _f64(scale)
+        pv = np.zeros(D) if prior_prec is None else _f64(prior_prec)
+        pm = np.zeros(D) if prior_mean is None else _f64(prior_mean)
+        K, Q = w.size, int(P) * int(R)
+        if K < 1 or ybar.size != K or any(a.size != D for a in (lo, hi, scale, pv, pm)):
+            raise ValueError('boxsmc: w and ybar must hold K >= 1 entries; lo, hi, scale and the prior D = %d' % D)
+        par = np.concatenate([w, ybar, pv, pm, scale, lo, hi])
+        return dict(work=torch.empty(self.boxsmc_workspace(P, R, D), dtype=torch.uint8, device=self.device), K=K, P=int(P),
+                    R=int(R), par_h=par, par=self.tensor(par), x=self.zeros(D, Q), ll=self.zeros(Q), lprior=self.zeros(Q),
+                    h=torch.full((Q,), float(h0), dtype=torch.float64, device=self.device), logr=self.zeros(Q),
+                    status=self.zeros(Q, dtype=torch.int32), n_prop=self.zeros(Q, dtype=torch.int32),
+                    n_acc=self.zeros(Q, dtype=torch.int32), beta=self.zeros(P), dbeta=self.zeros(P), log_evidence=self.zeros(P),
+                    stage_ess=self.zeros(P), draw_status=self.zeros(P, dtype=torch.int32),
+                    anc=self.zeros(P, R, dtype=torch.int32), running=self.zeros(1, dtype=torch.int32))
+
+    def _boxsmc_sizes(self, state, x_trial):
+        if x_trial.dim() != 3 or x_trial.dtype != torch.float64 or not x_trial.is_contiguous():
+            raise ValueError('boxsmc: x_trial must be a contiguous float64 tensor (P, R, D)')
+        P, R, D = x_trial.shape
+        Q = P * R
+        sizes = dict(x=Q * D, ll=Q, lprior=Q, h=Q, logr=Q, status=Q, n_prop=Q, n_acc=Q, beta=P, dbeta=P, log_evidence=P,
+                     stage_ess=P, draw_status=P, anc=Q, running=1, par=2 * state['K'] + 5 * D)
+        if state['P'] != P or state['R'] != R or state['work'].numel() < self.boxsmc_workspace(P, R, D) or \
+                state['par_h'].size != 2 * state['K'] + 5 * D or any(state[name].numel() != n for name, n in sizes.items()):
+            raise ValueError('boxsmc: the state was made for another P, R, D or K')
+        return P, R, D
+
+    def boxsmc_move(self, state, f, J, x_trial, z, logu, hmin=1e-10, hmax=1e2, up=1.0, down=1.0, adapt=False, first=False,
+                    last=False):
+        """One call of every particle's tempered MALA state machine (dgpamd_boxsmc_move).  state: boxsmc_state's; f
+        (P, R, K), J (P, R, K, D): the walk's values and Jacobian at x_trial (P, R, D); z (P, R, D), logu (P, R): this call's
+        draws; all contiguous float64 device tensors.  first: a stage starts -- the state comes from x_trial under the
+        draw's beta.  last: the stage ends -- x_trial <- x instead of a proposal.  adapt: as boxmala_step.  x_trial is
+        overwritten with the next points to evaluate."""
+        P, R, D = self._boxsmc_sizes(state, x_trial)
+        K = state['K']
+        for t, shape in ((f, (P, R, K)), (J, (P, R, K, D)), (z, (P, R, D)), (logu, (P, R))):
+            if t.shape != shape or t.dtype != torch.float64 or not t.is_contiguous():
+                raise ValueError('boxsmc: f, J, z, logu must be contiguous float64 tensors (P, R, K), (P, R, K, D), (P, R, D), '
+                                 '(P, R) beside x_trial (P, R, D)')
+        self._chk(self._enter() or lib.dgpamd_boxsmc_move(
+            self.h, P, R, D, K, _dp(f), _dp(J), _dp(state['par']), _hp(state['par_h']), _dp(state['beta']), _dp(z), _dp(logu),
+            float(hmin), float(hmax), float(up), float(down), 1 if adapt else 0, 1 if first else 0, 1 if last else 0,
+            _dp(state['work']), _dp(x_trial), _dp(state['x']), _dp(state['ll']), _dp(state['lprior']), _dp(state['h']),
+            _dp(state['logr']), _dp(state['status']), _dp(state['n_prop']), _dp(state['n_acc'])))
+        return x_trial
+
+    def boxsmc_temper(self, state, x_trial, u, ess_frac=0.5):
+        """One tempering step of every draw (dgpamd_boxsmc_temper): from state's ll, x and beta and the uniforms u (P,), a
+        float64 device tensor, the step of beta that keeps ESS >= ess_frac R_live; updates beta, dbeta, log_evidence,
+        stage_ess, draw_status, anc and running in place and gathers the resampled particles into x_trial (P, R, D)."""
+        P, R, D = self._boxsmc_sizes(state, x_trial)
+        if u.shape != (P,) or u.dtype != torch.float64 or not u.is_contiguous():
+            raise ValueError('boxsmc: u must be a contiguous float64 tensor (P,)')
+        self._chk(self._enter() or lib.dgpamd_boxsmc_temper(
+            self.h, P, R, D, float(ess_frac), _dp(state['ll']), _dp(state['x']), _dp(u), _dp(state['beta']), _dp(state['dbeta']),
+            _dp(state['log_evidence']), _dp(state['stage_ess']), _dp(state['draw_status']), _dp(state['anc']), _dp(x_trial),
+            _dp(state['running'])))
+        return x_trial
+
     # --------------------------------------------------------------- vecchia
     def nn_ordered(self, x, m):
         n, D = x.shape

@@ -31,6 +31,8 @@ E_x[grad f grad f^T] on the device (sensitivity.gradient_moments, dgpamd_gradmom
 
 paths.calibrate(y, obs_sd, bounds) (DESIGN I.19) samples every draw's posterior of the input given an observation: the walk at
 per-path rows feeds batched MALA or HMC chains on the device (calibrate.calibrate, dgpamd_boxmala_step, dgpamd_boxhmc_step).
+paths.calibrate_smc (DESIGN I.21) feeds the same walk to tempered SMC particles, which also give every draw's evidence
+(calibrate.calibrate_smc, dgpamd_boxsmc_temper, dgpamd_boxsmc_move).
 """
 import copy
 
@@ -372,6 +374,24 @@ class PathFunctions:
                                    n_candidates, x0, seed, qmc, step, scale, prior, target_accept, method, n_leapfrog,
                                    jitter)
 
+    def calibrate_smc(self, y, obs_sd, bounds, n_particles=1024, n_moves=4, ess_frac=0.5, max_stages=100, seed=None, step=0.1,
+                      scale=None, prior=None, target_accept=0.574):
+        """calibrate's posteriors by tempered sequential Monte Carlo, with every draw's evidence, on the device (DESIGN
+        I.21): a calibrate.ParticlePosterior with x (P, n_particles, Dx) and log_evidence (P,), the estimate of log of the
+        integral of prior(x) exp(ll_p(x)) over the box under the normalised prior.  y, obs_sd, bounds, prior, scale, step
+        and target_accept as in calibrate.  Draw p's particles start from the prior on the box; its likelihood is switched
+        on in steps of beta in [0, 1], each the largest that keeps the effective sample size of the incremental weights at
+        ess_frac of the live particles; a step reweights, resamples systematically and moves every particle by n_moves
+        MALA steps under prior(x) exp(beta ll_p(x)), with one step size per draw, `step` at first, set after every stage
+        from the stage's acceptance rate towards target_accept.  The particles do not start in a
+        mode, so a multimodal posterior keeps its modes in proportion.  At most max_stages steps: a draw still below
+        beta = 1 has status max_stages.  n_particles <= calibrate.MAX_PARTICLES.  The random numbers come from
+        np.random.SeedSequence(seed); draw p's do not depend on the draws beside it.  result.draw_weights() weighs the draws
+        by their evidence; result.pooled() stays the modular posterior.  Raises as calibrate does."""
+        from . import calibrate
+        return calibrate.calibrate_smc(*self._lane_problem(bounds, 'calibrate_smc'), y, obs_sd, bounds, n_particles, n_moves,
+                                       ess_frac, max_stages, seed, step, scale, prior, target_accept)
+
     def _lane_problem(self, bounds, what):
         """What minimize and calibrate hand to their drivers after their common refusals: (engine, P, K, Dx, values,
         value_and_jac, width), the closures over the shared-rows walk and the walk at per-path rows."""
@@ -552,6 +572,15 @@ class GpPaths:
         return calibrate.calibrate(*self._lane_problem(bounds, 'calibrate'), np.reshape(y, (-1, 1)) if np.ndim(y) < 2 else y,
                                    obs_sd, bounds, n_chains, n_samples, warmup, thin, n_candidates, x0, seed, qmc, step, scale,
                                    prior, target_accept, method, n_leapfrog, jitter)
+
+    def calibrate_smc(self, y, obs_sd, bounds, n_particles=1024, n_moves=4, ess_frac=0.5, max_stages=100, seed=None, step=0.1,
+                      scale=None, prior=None, target_accept=0.574):
+        """PathFunctions.calibrate_smc for the sample_size draws of a gp model (P = sample_size, one output; y as in
+        calibrate): tempered SMC particles of every draw's posterior and its evidence."""
+        from . import calibrate
+        return calibrate.calibrate_smc(*self._lane_problem(bounds, 'calibrate_smc'), np.reshape(y, (-1, 1)) if np.ndim(y) < 2 else y,
+                                       obs_sd, bounds, n_particles, n_moves, ess_frac, max_stages, seed, step, scale, prior,
+                                       target_accept)
 
     def _lane_problem(self, bounds, what):
         """PathFunctions._lane_problem for the one node of a gp model."""

@@ -845,6 +845,55 @@ int dgpamd_boxhmc_step(dgpamd_ctx *ctx, int64_t Q, int D, int K, const double *f
                        double down, int adapt, int first, int last, int slot, int n_slots, void *work, double *x_trial, double *h,
                        double *logr, double *xs, double *lps, int32_t *status, int32_t *n_prop, int32_t *n_acc);
 
+/* ---- tempered sequential Monte Carlo over a box: evidence and multimodal input posteriors (DESIGN I.21) ----
+ * P draws with R particles each, 1 <= R <= DGPAMD_BOXSMC_MAXR, lane q = p R + r, P R < 2^31.  Draw p's particles sample
+ * pi_beta(x) proportional to prior(x) exp(beta_p ll(x)) on the box, ll(x) = -1/2 sum_k w_k (ybar_k - f_k(x))^2 and
+ * lprior(x) = -1/2 sum_d pv_d (x_d - pm_d)^2, the two parts of the chains' lp above; only the likelihood is tempered.
+ * f, J, par, par_h, z, logu, x_trial, h, logr, n_prop, n_acc and the fixed columns: as for the chains.  State tensors the
+ * caller owns and may read: x (D x Q, particle fastest), ll, lprior (Q), status (Q) int32 per particle (DGPAMD_BOXSMC_OK,
+ * _NAN); beta (P), and h (Q), which no call resets: the caller fills it before the first one.
+ *
+ * dgpamd_boxsmc_move: one call of every particle's tempered MALA state machine, one lane per particle, beta read from
+ * beta[q / R].  work: dgpamd_boxsmc_workspace(P, R, D) = P R (16 D + 4) bytes -- g, g' (D x Q doubles each) and the int32
+ * out-of-box flag (Q); 0 for sizes the calls refuse.  Per particle and call, in this order (tests/boxsmc_ref.py restates it):
+ *   TARGET   (status OK, or first != 0) the chains' sums in their order: ll' = -0.5 a, lprior' = -0.5 b,
+ *            g'_d = beta c_d, then g'_d - pv_d e_d where pv_d > 0.
+ *   INIT     (first != 0: a stage starts at the gathered particles) (x, g, ll, lprior) <- the trial's under this beta; logr 0;
+ *            counts 0; the flag down; ll', lprior' or g' not finite: status NAN, else OK.  h stays.
+ *   DECIDE   (first = 0, status OK) the flag set: logr = -inf; else a non-finite trial: logr = NaN; else
+ *            logr = ((beta ll' + lprior') - (beta ll + lprior)) + (0.5 qf - 0.5 qb), qf and qb as in the MALA step's DECIDE.
+ *            Then TALLY as above (an accepted trial also commits ll and lprior).
+ *   HOLD     status NAN, or last != 0 (the stage ends): x_trial = x, and nothing more.
+ *   PROPOSE  else, as the MALA step's.
+ * Products are not fused into sums.  DGPAMD_BAD_ARG: the chains' cases, R outside 1 .. DGPAMD_BOXSMC_MAXR, a null pointer.
+ *
+ * dgpamd_boxsmc_temper: one workgroup per draw.  With d_i = m - ll_i, m the largest finite ll of the draw (a particle whose
+ * ll is not finite is dead: weight 0, never an ancestor), a_i(delta) = exp_negated(delta d_i) and
+ * ESS(delta) = (sum a)^2 / sum a^2: delta = 1 - beta if ESS(1 - beta) >= ess_frac R_live, then beta' = 1 exactly; else
+ * the lower end of [0, 1 - beta] after 52 halvings, which keeps ESS >= the target, and beta' = beta + delta.  Then
+ *   log_evidence[p] += delta m + log(sum a / R), stage_ess[p] = ESS(delta), dbeta[p] = delta, beta[p] = beta';
+ *   C_i the inclusive scan of a_i / sum a, clamped to 1 and exactly 1 from the last particle of positive weight on; particle i
+ *   is the ancestor of the slots ceil(R C_{i-1} - u_p) .. ceil(R C_i - u_p) - 1 of anc[p, :] (systematic resampling with the
+ *   one uniform u_p in [0, 1)); x_trial[p, j, :] = x[:, p R + anc[p, j]].
+ * Every sum runs in an order that R alone fixes: a draw's outputs do not depend on P or on the draws beside it.
+ * A draw with beta = 1 or status not OK, and one for which no delta > 0 keeps the target: delta = 0, anc the identity,
+ * x_trial = x, stage_ess NaN, log_evidence as it was.  A draw with status OK and no live particle: status NAN (P) and
+ * log_evidence NaN.  status (P) int32 per draw; DGPAMD_BOXSMC_MAX_STAGES is the driver's.  running (1) int32: set to the
+ * count of draws with status OK and beta' < 1.  DGPAMD_BAD_ARG: the sizes above, ess_frac outside (0, 1), a null pointer. */
+#define DGPAMD_BOXSMC_OK 0
+#define DGPAMD_BOXSMC_NAN 1
+#define DGPAMD_BOXSMC_MAX_STAGES 2
+#define DGPAMD_BOXSMC_COUNT 3
+#define DGPAMD_BOXSMC_MAXR 8192
+size_t dgpamd_boxsmc_workspace(int64_t P, int64_t R, int D);
+int dgpamd_boxsmc_move(dgpamd_ctx *ctx, int64_t P, int64_t R, int D, int K, const double *f, const double *J, const double *par,
+                       const double *par_h, const double *beta, const double *z, const double *logu, double hmin, double hmax,
+                       double up, double down, int adapt, int first, int last, void *work, double *x_trial, double *x, double *ll,
+                       double *lprior, double *h, double *logr, int32_t *status, int32_t *n_prop, int32_t *n_acc);
+int dgpamd_boxsmc_temper(dgpamd_ctx *ctx, int64_t P, int64_t R, int D, double ess_frac, const double *ll, const double *x,
+                         const double *u, double *beta, double *dbeta, double *log_evidence, double *stage_ess, int32_t *status,
+                         int32_t *anc, double *x_trial, int32_t *running);
+
 #ifdef __cplusplus
 }
 #endif
