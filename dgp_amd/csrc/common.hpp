@@ -7,7 +7,7 @@
 
 #include "../../include/dgp_amd.h"
 
-#define NB 64          // factorisation block / tile edge
+#include "tuning.hpp"   // NB, padded_dim, struct Tuning (plain C++: shared with the host-only plan headers)
 #define LDT 66         // LDS leading dimension of a 64-wide f64 tile (conflict-free ds_read_b64 fragments)
 
 #include <array>
@@ -17,15 +17,6 @@
 // kernel classes for the launch-timing facility (dgpamd_prof_*)
 enum { PROF_NONE = 0, PROF_KMATRIX = 1, PROF_POTRF_DIAG = 2, PROF_TRSM = 3, PROF_SYRK = 4, PROF_TRTRI = 5,
        PROF_LAUUM = 6, PROF_GRAD = 7, PROF_LINKGP_J = 8, PROF_GP_QUAD = 9 };
-
-// The DGPAMD_* switches of the C library as dgpamd_create found them (context.hip holds the one table: names, defaults, accepted
-// values).  A context keeps the switches it was created under.  0 stands for "unset" where the default depends on the call.
-struct Tuning {
-    int64_t potrf_mode, fetch_spin, llik_args_copy;
-    int64_t mega_lazy, mega_slazy, mega_near, mega_look, mega_slag, mega_queues, mega_ncrit, mega_split, mega_groups;
-    int64_t jsep_tch, jsexp_tch, pair_chunk, sexp_form1, sexp_poly, jsep_pipe, jsep_log, jsep_noclass, jsep_diag;
-    int64_t nn_filter, nn_store_once, vecchia_lds, poison_lds;
-};
 
 struct dgpamd_ctx {
     int device;
@@ -169,8 +160,6 @@ static inline int graph_run(dgpamd_ctx *ctx, const std::array<uint64_t, 10> &key
         }                                                                     \
     } while (0)
 
-
-static inline int64_t padded_dim(int64_t n) { return ((n + 1 + NB - 1) / NB) * NB; }
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 
@@ -382,7 +371,6 @@ int run_potrf(dgpamd_ctx *ctx, int64_t n, double *A, int64_t stride_a, int batch
 // flags inside their graph): a kernel that runs just before on the same stream may clear them instead (KmatArgs::zero_ptr)
 // and pass sync_cleared = true.
 void potrf_sync_area(dgpamd_ctx *ctx, int64_t n, int batch, bool inv, double *ws, int32_t **ptr, int *words);   // T, S: fused inverse (dgpamd_potrf_inv)
-size_t potrf_ws_doubles(int64_t n, int batch);
 // vecchia_llik for `batch` input sets into caller-provided buffers (partial: batch x n x 2 doubles, out: batch x 2 = (quad,
 // logdet) per set), no allocation; launches made while ctx->pred is set are predicated on it (dgpamd_ess_queue)
 int vecchia_llik_batch_into(dgpamd_ctx *ctx, int kind, int64_t n, int D, int m, const double *X, int64_t x_stride, int batch,

@@ -143,7 +143,7 @@ int dgpamd_potrf(dgpamd_ctx *ctx, int64_t n, double *A, int64_t stride_a, int ba
                  double *logdet, int32_t *info, void *work);
 /* How dgpamd_potrf / dgpamd_potrf_inv (and everything built on them) run the blocked factorisation:
  * mode 1 (default): ONE persistent launch -- a pivot-chain workgroup per matrix plus workers that pull tile tasks
- * from a queue, ordered by per-tile version words (csrc/chol.hip, potrf_mega_kernel); mode 0: one launch per 64-column
+ * from a queue, ordered by per-tile version words (csrc/potrf_mega.hpp, potrf_mega_kernel); mode 0: one launch per 64-column
  * block step, replayed as a hipGraph (no waits between workgroups inside a launch: the mode for a device shared with other
  * processes).  The results are bit-identical (every tile applies its panels in the same order).
  * info[b] = -1 reports a lost in-kernel hand-off (a bounded spin gave up), never a numerical failure: the caller

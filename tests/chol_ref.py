@@ -1,4 +1,4 @@
-"""Host reference of the dense factorisation (csrc/chol.hip, csrc/diagfac.hpp): backward errors of dgpamd_potrf,
+"""Host reference of the dense factorisation (csrc/chol.hip, csrc/potrf_step.hpp, csrc/potrf_mega.hpp, csrc/diagfac.hpp): backward errors of dgpamd_potrf,
 dgpamd_potrf_inv and dgpamd_potri_batched in extended arithmetic, LAPACK's values of the same measures on the same input,
 and matrices that fail at a chosen pivot.  numpy / scipy / mpmath only.
 

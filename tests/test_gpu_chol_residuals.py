@@ -1,4 +1,4 @@
-"""The dense factorisation (csrc/chol.hip, csrc/diagfac.hpp: dgpamd_potrf, dgpamd_potrf_inv, dgpamd_potri_batched) held to
+"""The dense factorisation (csrc/chol.hip, csrc/potrf_step.hpp, csrc/potrf_mega.hpp, csrc/diagfac.hpp: dgpamd_potrf, dgpamd_potrf_inv, dgpamd_potri_batched) held to
 backward-error bounds and to LAPACK's info, in both modes (per-step graphs, one launch).  Needs an MI355X: -m gpu.
 
 The forward comparisons of tests/test_gpu_ops.py (rtol 1e-7 .. 1e-9 against LAPACK's factor) cannot be tighter on kernel

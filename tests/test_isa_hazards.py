@@ -3,7 +3,7 @@
 A 16-byte buffer store reads its data registers over several cycles after it has issued; a VALU / load instruction that
 rewrites one of them too early corrupts the store (documented for gfx9 as "VMEM store of more than 64 bits followed by a write
 of the data VGPRs: wait states"; LLVM inserts them only when the store's soffset is not a register).  In round 4 the chain's
-panel-tile store (csrc/chol.hip store_pt_sc1) lost data that way when other processes' waves shared the CU -- silent wrong
+panel-tile store (csrc/potrf_mega.hpp store_pt_sc1) lost data that way when other processes' waves shared the CU -- silent wrong
 factors, a few launches per thousand.  The source now keeps every value in registers of its own and waits; nothing obliges
 a future compiler to keep that shape, so this test reads the shipped library's code: in potrf_mega_kernel no instruction
 may write a data register of a buffer_store_dwordx4 within the next WAIT wait states."""
@@ -96,7 +96,7 @@ def test_16_byte_stores_keep_their_data_registers(tmp_path):
         # soffset (the operand behind the resource): a literal, never an SGPR -- LLVM inserts its own wait states only then
         soff = ops[ops.index(next(o for o in ops if o.startswith('s['))) + 1]
         assert not re.fullmatch(r's\d+|m0', soff), 'soffset of %s is a register: LLVM\'s hazard recogniser skips this store' % isa[i]
-        # the panel-tile stores: eight consecutive sc1 stores (csrc/chol.hip store_pt_sc1)
+        # the panel-tile stores: eight consecutive sc1 stores (csrc/potrf_mega.hpp store_pt_sc1)
         in_run = all(j < len(isa) and isa[j].startswith('buffer_store_dwordx4') and 'sc1' in isa[j] for j in range(i, i + 1)) and \
             sum(1 for j in range(max(0, i - 7), min(len(isa), i + 8)) if isa[j].startswith('buffer_store_dwordx4')) >= 8
         need = WAIT_PT if in_run else WAIT

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
-"""Timing model of the one-launch factorisation (csrc/chol.hip potrf_mega_kernel): the task-table generator restated in Python
-(build(): the same statements as build_mega_tasks, checked against a table dumped from the library) and a discrete-event simulation
+"""Timing model of the one-launch factorisation (csrc/potrf_mega.hpp potrf_mega_kernel): the task-table generator restated in Python
+(build(): the same statements as csrc/potrf_plan.hpp build_mega_tasks, held to the C++ generator through tools/potrf_table_check.cpp
+--dump by tests/test_potrf_table_host.py, and checked against a table dumped from the library) and a discrete-event simulation
 of the launch -- chains, the two ticket queues per group of matrices, workers that pull in order and wait inside their tasks, the
 split wait, version words with a visibility latency -- with task durations taken from the task logs (profiles/r05_tasklog_*.txt).
 Purpose: try table orders in seconds instead of GPU runs, and say what a change can buy before it is built.
 usage: sim_mega_timing.py [B ...]            (prints model time for potrf / potrf_inv at those batch sizes, current table)
-       sim_mega_timing.py check file.npz     (compare build() with the table in a task log)"""
+       sim_mega_timing.py check file.npz     (compare build() with the table in a task log)
+       sim_mega_timing.py check dump.txt nbk inv B   (... with the output of potrf_table_check --dump nbk inv B: no GPU needed)"""
 import heapq
 import sys
 import numpy as np
@@ -16,7 +18,7 @@ A_, T_, S_ = 0, 1, 2
 
 
 def build(nbk, inv, lazy=10, slazy=10, near=3, lag=0, xcatch=0, stail=0, look=1, slag=0, far_merge=0, critd=0):
-    """-> (tasks, need): tasks = dicts(post, first, bufC, ci, cj, bufL, li, bufR, ri, kb0, nkb, need_c, fin, wk, need2, step, crit)"""
+    """-> (tasks, need): tasks = dicts(post, first, mask, bufC, ci, cj, bufL, li, bufR, ri, kb0, nkb, need_c, fin, wk, need2, step, crit)"""
     tasks, need = [], [(0, 0)] * nbk
     apA = np.zeros((nbk, nbk), int); viA = np.zeros((nbk, nbk), int)
     apT = np.zeros((nbk, nbk), int); viT = np.zeros((nbk, nbk), int)
@@ -26,8 +28,8 @@ def build(nbk, inv, lazy=10, slazy=10, near=3, lag=0, xcatch=0, stail=0, look=1,
             apT[q, :] = q
     cur = dict(step=0, crit=0)
 
-    def emit(post, first, bufC, ci, cj, bufL, li, bufR, ri, kb0, nkb, need_c, fin, wk, need2=0, crit=None):
-        tasks.append(dict(post=post, first=first, bufC=bufC, ci=ci, cj=cj, bufL=bufL, li=li, bufR=bufR, ri=ri, kb0=kb0, nkb=nkb,
+    def emit(post, first, bufC, ci, cj, bufL, li, bufR, ri, kb0, nkb, need_c, fin, wk, need2=0, crit=None, mask=0):
+        tasks.append(dict(post=post, first=first, mask=mask, bufC=bufC, ci=ci, cj=cj, bufL=bufL, li=li, bufR=bufR, ri=ri, kb0=kb0, nkb=nkb,
                           need_c=need_c, fin=fin, wk=wk, need2=need2, step=cur['step'], crit=cur['crit'] if crit is None else crit))
 
     def updA(i, j, upto):
@@ -114,7 +116,7 @@ def build(nbk, inv, lazy=10, slazy=10, near=3, lag=0, xcatch=0, stail=0, look=1,
                     continue
                 ap, nkb = int(apS[q]), int(upto - apS[q])
                 for q2 in range(q + 1):
-                    emit(STORE, int(ap == q), S_, q, q2, T_, q, T_, q2, ap, nkb, viS[q, q2], 0, 0); viS[q, q2] += 1
+                    emit(STORE, int(ap == q), S_, q, q2, T_, q, T_, q2, ap, nkb, viS[q, q2], 0, 0, mask=int(upto == nbk)); viS[q, q2] += 1
                 apS[q] = upto
     return tasks, need
 
@@ -404,11 +406,33 @@ class Sim:
         return self.end
 
 
+def default_params(B, inv, nbk):
+    """the table parameters csrc/potrf_plan.hpp mega_plan chooses under the default switches"""
+    lazy = (12 if (inv or nbk >= 64) else 10) if B >= 6 else (10 if inv else 8)
+    return dict(lazy=lazy, slazy=lazy, near=3, stail=1 if (inv and B <= 3) else 0)
+
+
+def table_rows(nbk, inv, B):
+    """-> (rows, need): the flattened table as the kernel reads it under the default switches on an MI355X, eight ints per task (what
+    dgpamd_debug_mega_table and potrf_table_check --dump give): with two queues (B <= 3) the critical tasks first, their block step in b.y"""
+    tasks, need = build(nbk, bool(inv), **default_params(B, inv, nbk))
+    two = B <= 3
+    order = [t for t in tasks if t['crit']] + [t for t in tasks if not t['crit']] if two else tasks
+    rows = [(t['post'] | t['first'] << 4 | int(t['bufC'] == S_) << 5 | t['mask'] << 6 | t['bufC'] << 8 | t['bufL'] << 10 | t['bufR'] << 12,
+             t['ci'] | t['cj'] << 16, t['li'] | t['ri'] << 16, t['kb0'] | t['nkb'] << 16,
+             t['need_c'], t['fin'] | ((t['step'] << 8) if (two and t['crit']) else 0), t['wk'], t['need2']) for t in order]
+    return [tuple(int(v) for v in r) for r in rows], [tuple(int(v) for v in n) for n in need]
+
+
+def read_dump(text):
+    """potrf_table_check --dump: lines of eight ints (the tasks), then lines of two (chain_need)"""
+    lines = [tuple(int(v) for v in ln.split()) for ln in text.splitlines() if ln.strip()]
+    return [r for r in lines if len(r) == 8], [r for r in lines if len(r) == 2]
+
+
 def model(B, inv, nbk=32, **kw):
     simkw = {k: kw.pop(k) for k in list(kw) if k in ('queues', 'ncrit', 'groups', 'split', 'window')}
-    deep = B >= 6
-    p = dict(lazy=(12 if inv else 10) if deep else (10 if inv else 8), slazy=(12 if inv else 10) if deep else (10 if inv else 8), near=3,
-             stail=1 if (inv and B <= 3) else 0)
+    p = default_params(B, inv, nbk)
     p.update(kw)
     tasks, need = build(nbk, inv, **p)
     s = Sim(tasks, need, B, nbk, inv, **simkw)
@@ -418,21 +442,18 @@ def model(B, inv, nbk=32, **kw):
 
 if __name__ == '__main__':
     if len(sys.argv) > 2 and sys.argv[1] == 'check':
-        z = np.load(sys.argv[2])
-        tab = z['table']
-        inv, nbk, B = int(z['inv']), int(z['nbk']), int(z['B'])
-        deep = B >= 6
-        tasks, need = build(nbk, bool(inv), lazy=(12 if inv else 10) if deep else (10 if inv else 8), slazy=(12 if inv else 10) if deep else (10 if inv else 8),
-                            near=3, stail=1 if (inv and B <= 3) else 0)
-        mine = [t for t in tasks if t['crit']] + [t for t in tasks if not t['crit']]
+        if sys.argv[2].endswith('.npz'):
+            z = np.load(sys.argv[2])
+            tab, their_need = [tuple(int(v) for v in r) for r in z['table']], [tuple(int(v) for v in r) for r in z['need']]
+            inv, nbk, B = int(z['inv']), int(z['nbk']), int(z['B'])
+        else:
+            tab, their_need = read_dump(open(sys.argv[2]).read())
+            nbk, inv, B = (int(v) for v in sys.argv[3:6])
+        mine, need = table_rows(nbk, inv, B)
         assert len(mine) == len(tab), (len(mine), len(tab))
-        bad = 0
-        for t, r in zip(mine, tab):
-            got = (r[0] & 15, (r[0] >> 8) & 3, r[1] & 0xffff, r[1] >> 16, r[3] & 0xffff, r[3] >> 16, r[4], r[5] & 1, r[6], r[7])
-            want = (t['post'], t['bufC'], t['ci'], t['cj'], t['kb0'], t['nkb'], t['need_c'], t['fin'], t['wk'], t['need2'])
-            bad += got != want
-        print('%d tasks, %d differ from the library\'s table; chain needs equal: %s' % (len(tab), bad, np.array_equal(np.array(need), z['need'])))
-        sys.exit(1 if bad else 0)
+        bad = sum(a != b for a, b in zip(mine, tab))
+        print('%d tasks, %d differ from the library\'s table; chain needs equal: %s' % (len(tab), bad, need == their_need))
+        sys.exit(1 if bad or need != their_need else 0)
     for B in [int(v) for v in sys.argv[1:]] or [1, 2, 3, 4, 6, 10]:
         a = model(B, False)
         b = model(B, True)

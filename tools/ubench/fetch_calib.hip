@@ -3,7 +3,7 @@
 // the same 1 GiB (> the 256-MiB Infinity Cache) once each with the load forms of the library's hand-off code:
 //   calib_b128_plain : global_load_dwordx4 (16 B per lane)
 //   calib_b128_sc1   : buffer_load_dwordx4 ... sc1 (16 B per lane: operand tiles of the one-launch factorisation, tile.hpp fetch_mk_sc1)
-//   calib_b64_sc1    : global_load_dwordx2 sc1 (8 B per lane, agent-scope relaxed atomic loads: accumulator tiles, chol.hip load_acc_sc1)
+//   calib_b64_sc1    : global_load_dwordx2 sc1 (8 B per lane, agent-scope relaxed atomic loads: accumulator tiles, chol_tile.hpp load_acc_sc1)
 // run under: rocprofv3 --kernel-trace --pmc FETCH_SIZE -d <dir> --output-format csv -- build_ubench/fetch_calib
 // build: hipcc --offload-arch=gfx950 -O3 -o build_ubench/fetch_calib tools/ubench/fetch_calib.hip
 #include <hip/hip_runtime.h>

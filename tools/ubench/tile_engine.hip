@@ -1,6 +1,6 @@
 // Microbenchmark: steady-state rate of the f64 MFMA tile engine used by the factorisation's bulk tasks
 //   C(tile) -= sum over nkb 64-blocks  L_kb R_kb^T
-// V0: 64x64 output tile per 256-thread workgroup (wave = 16 rows x 64 columns)      -- what csrc/chol.hip does
+// V0: 64x64 output tile per 256-thread workgroup (wave = 16 rows x 64 columns)      -- what csrc/chol_tile.hpp tile_update does
 // V1: 128x64 output tile per workgroup (wave = 32 rows x 64 columns: 6 LDS fragment reads per 8 MFMAs instead of 5 per 4)
 // build: hipcc --offload-arch=gfx950 -O3 -I../../dgp_amd/csrc tile_engine.hip -o tile_engine
 #include <hip/hip_runtime.h>
