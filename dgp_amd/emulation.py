@@ -551,6 +551,13 @@ class emulator:
         particles and evidence; draw_weights() weighs the draws by it, pooled() is the modular posterior."""
         return self.sample_functions(sample_size, n_features).calibrate_smc(y, obs_sd, bounds, **smc_kw)
 
+    def failure_probability(self, threshold, bounds, sample_size=10, n_features=2048, **sus_kw):
+        """Draws sample_size functions (sample_functions(sample_size, n_features)) and returns the
+        reliability.FailureProbability of paths.failure_probability(threshold, bounds, **sus_kw): every draw's probability
+        that the output reaches threshold when x is distributed over the box, by subset simulation on the device (DESIGN
+        I.22); the spread over the draws is the model's uncertainty about that probability."""
+        return self.sample_functions(sample_size, n_features).failure_probability(threshold, bounds, **sus_kw)
+
     def sample_paths_vecchia(self, x, sample_size=50, full_layer=False, m=50):
         """sample_paths by the Vecchia factorisation of each node's joint predictive distribution (vpaths, DESIGN I.11):
         the same container and column layout, for dense and Vecchia emulators and any number of rows.  The rows of x are

@@ -299,6 +299,13 @@ class gp:
         evidence."""
         return self.sample_functions(sample_size, n_features).calibrate_smc(y, obs_sd, bounds, **smc_kw)
 
+    def failure_probability(self, threshold, bounds, sample_size=10, n_features=2048, **sus_kw):
+        """Draws sample_size functions (sample_functions(sample_size, n_features)) and returns the
+        reliability.FailureProbability of paths.failure_probability(threshold, bounds, **sus_kw): every draw's probability
+        that the output reaches threshold when x is distributed over the box, by subset simulation on the device (DESIGN
+        I.22); the spread over the draws is the model's uncertainty about that probability."""
+        return self.sample_functions(sample_size, n_features).failure_probability(threshold, bounds, **sus_kw)
+
     def sample_paths_vecchia(self, x, sample_size=50, m=50):
         """Joint posterior draws of the GP at the rows of x by the Vecchia factorisation of the joint predictive distribution
         (vpaths): (M, sample_size) as sample_paths, for dense and Vecchia-mode models and any M.  The rows are drawn in the

@@ -962,6 +962,79 @@ class Engine:
             _dp(state['running'])))
         return x_trial
 
+    # subset simulation (csrc/boxsus.hip)
+    BOXSUS = dict(ok=0, nan=1, max_stages=2, below_min=3)
+    BOXSUS_MAXR = 8192
+
+    def boxsus_state(self, P, R, D, lo, hi, prior_prec=None, prior_mean=None, step=1.0):
+        """What one run keeps between its boxsus_move and boxsus_level calls: par, the prior and the box on the device --
+        prior_prec (D, None: 0, the uniform prior), prior_mean (D), lo (D), hi (D) -- and par_h, its host copy; per particle
+        x (D, Q) particle fastest, score (Q) and moved, status, n_prop, n_acc (Q) int32, Q = P R; per draw prob (ones), level
+        (-inf), lam (filled with step), sd (P, D) (zeros: the caller fills it before the first move), nsurv, done,
+        draw_status (P) int32, anc (P, R) int32; running (1,) int32."""
+        P, R, D = int(P), int(R), int(D)
+        if P < 1 or not 1 <= R <= Engine.BOXSUS_MAXR or P * R >= 2 ** 31 or not 1 <= D <= _lib.MAXD:
+            raise ValueError('boxsus: need P >= 1, 1 <= R <= %d, P R < 2^31 and 1 <= D <= %d' % (Engine.BOXSUS_MAXR, _lib.MAXD))
+        lo, hi = _f64(lo), _f64(hi)
+        pv = np.zeros(D) if prior_prec is None else _f64(prior_prec)
+        pm = np.zeros(D) if prior_mean is None else _f64(prior_mean)
+        if any(a.size != D for a in (lo, hi, pv, pm)):
+            raise ValueError('boxsus: lo, hi and the prior must hold D = %d entries' % D)
+        par, Q = np.concatenate([pv, pm, lo, hi]), P * R
+        i32 = dict(dtype=torch.int32)
+        return dict(P=P, R=R, D=D, par_h=par, par=self.tensor(par), x=self.zeros(D, Q), score=self.zeros(Q),
+                    moved=self.zeros(Q, **i32), status=self.zeros(Q, **i32), n_prop=self.zeros(Q, **i32),
+                    n_acc=self.zeros(Q, **i32), prob=torch.ones(P, dtype=torch.float64, device=self.device),
+                    level=torch.full((P,), -np.inf, dtype=torch.float64, device=self.device),
+                    lam=torch.full((P,), float(step), dtype=torch.float64, device=self.device), sd=self.zeros(P, D),
+                    nsurv=self.zeros(P, **i32), done=self.zeros(P, **i32), draw_status=self.zeros(P, **i32),
+                    anc=self.zeros(P, R, **i32), running=self.zeros(1, **i32))
+
+    def _boxsus_sizes(self, state, x_trial):
+        if x_trial.dim() != 3 or x_trial.dtype != torch.float64 or not x_trial.is_contiguous():
+            raise ValueError('boxsus: x_trial must be a contiguous float64 tensor (P, R, D)')
+        P, R, D = x_trial.shape
+        Q = P * R
+        sizes = dict(x=Q * D, score=Q, moved=Q, status=Q, n_prop=Q, n_acc=Q, prob=P, level=P, lam=P, sd=P * D, nsurv=P, done=P,
+                     draw_status=P, anc=Q, running=1, par=4 * D)
+        if (state['P'], state['R'], state['D']) != (P, R, D) or state['par_h'].size != 4 * D or \
+                any(state[name].numel() != n or not state[name].is_contiguous() for name, n in sizes.items()):
+            raise ValueError('boxsus: the state was made for another P, R or D')
+        return P, R, D
+
+    def boxsus_move(self, state, f, x_trial, z, logu, threshold, output=0, sign=1.0, first=False, last=False):
+        """One call of every particle's modified Metropolis state machine (dgpamd_boxsus_move).  state: boxsus_state's; f
+        (P, R, K): the walk's values at x_trial (P, R, D), of which column output is read, score = sign (f - threshold) + 0;
+        z, logu (P, R, D): this call's normal draws and logarithms of uniform draws; all contiguous float64 device tensors.
+        first: a stage starts -- the state comes from x_trial.  last: the stage ends -- x_trial <- x instead of a proposal.
+        x_trial is overwritten with the next points to evaluate."""
+        P, R, D = self._boxsus_sizes(state, x_trial)
+        if f.dim() != 3:
+            raise ValueError('boxsus: f must be (P, R, K)')
+        K = f.shape[-1]
+        for t, shape in ((f, (P, R, K)), (z, (P, R, D)), (logu, (P, R, D))):
+            if t.shape != shape or t.dtype != torch.float64 or not t.is_contiguous():
+                raise ValueError('boxsus: f, z, logu must be contiguous float64 tensors (P, R, K), (P, R, D), (P, R, D) beside '
+                                 'x_trial (P, R, D)')
+        self._chk(self._enter() or lib.dgpamd_boxsus_move(
+            self.h, P, R, D, K, int(output), float(sign), float(threshold), _dp(f), _dp(state['par']), _hp(state['par_h']),
+            _dp(state['level']), _dp(state['lam']), _dp(state['sd']), _dp(z), _dp(logu), 1 if first else 0, 1 if last else 0,
+            _dp(x_trial), _dp(state['x']), _dp(state['score']), _dp(state['moved']), _dp(state['status']), _dp(state['n_prop']),
+            _dp(state['n_acc'])))
+        return x_trial
+
+    def boxsus_level(self, state, x_trial, n_s, min_prob=1e-12):
+        """One level step of every draw (dgpamd_boxsus_level): from state's score and x, the n_s-th largest live score as
+        the next level (+0 once it is reached: the draw's final stage), the survivors and their count, prob times their
+        share, the ancestors and the survivors' spread sd; updates prob, level, nsurv, done, draw_status, anc, sd and running
+        in place and gathers the cloned particles into x_trial (P, R, D)."""
+        P, R, D = self._boxsus_sizes(state, x_trial)
+        self._chk(self._enter() or lib.dgpamd_boxsus_level(
+            self.h, P, R, D, int(n_s), float(min_prob), _dp(state['score']), _dp(state['x']), _dp(state['prob']),
+            _dp(state['level']), _dp(state['nsurv']), _dp(state['done']), _dp(state['draw_status']), _dp(state['anc']),
+            _dp(x_trial), _dp(state['sd']), _dp(state['running'])))
+        return x_trial
+
     # --------------------------------------------------------------- vecchia
     def nn_ordered(self, x, m):
         n, D = x.shape

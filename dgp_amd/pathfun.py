@@ -33,6 +33,8 @@ paths.calibrate(y, obs_sd, bounds) (DESIGN I.19) samples every draw's posterior 
 per-path rows feeds batched MALA or HMC chains on the device (calibrate.calibrate, dgpamd_boxmala_step, dgpamd_boxhmc_step).
 paths.calibrate_smc (DESIGN I.21) feeds the same walk to tempered SMC particles, which also give every draw's evidence
 (calibrate.calibrate_smc, dgpamd_boxsmc_temper, dgpamd_boxsmc_move).
+paths.failure_probability (DESIGN I.22) feeds its values to subset-simulation particles: the probability of a rare event of
+every draw (reliability.failure_probability, dgpamd_boxsus_level, dgpamd_boxsus_move).
 """
 import copy
 
@@ -392,6 +394,41 @@ class PathFunctions:
         return calibrate.calibrate_smc(*self._lane_problem(bounds, 'calibrate_smc'), y, obs_sd, bounds, n_particles, n_moves,
                                        ess_frac, max_stages, seed, step, scale, prior, target_accept)
 
+    def failure_probability(self, threshold, bounds, output=0, below=False, n_particles=1024, level_prob=0.1, n_moves=4,
+                            max_stages=50, min_prob=1e-12, seed=None, step=1.0, prior=None, target_accept=0.44):
+        """The probability that output `output` of the last layer reaches threshold (below: falls to it) when x is
+        distributed over the box bounds (Dx, 2), for every draw, on the device (reliability, DESIGN I.22): a
+        reliability.FailureProbability with prob (P,), P = N * sample_size, the estimate of prior{x : f_p(x) >= threshold}
+        by subset simulation, every stage's level, conditional probability, acceptance rate and step (P, T), and x
+        (P, n_particles, Dx), samples of the prior given the event.  prior: None (uniform on the box) or (mean (Dx,), sd
+        (Dx,)), independent normals truncated to the box, as in calibrate.  Draw p's particles start from the prior; a stage
+        takes the floor(level_prob n_particles)-th largest value as the next level, clones the particles at or above it
+        and moves each n_moves times by component-wise Metropolis steps inside the level set, of width step times the
+        survivors' spread per column, the step following the acceptance rate towards target_accept from stage to stage.
+        It takes about log(1 / prob) / log(1 / level_prob) stages of n_particles (n_moves + 1) rows each and no gradient.
+        At most max_stages stages (status max_stages), and none once the running product is under min_prob (status
+        below_min): prob is then an upper bound.  n_particles <= reliability.MAX_PARTICLES.  The random numbers come from
+        np.random.SeedSequence(seed); draw p's do not depend on the draws beside it, and the same arguments give the same
+        bits.  result.summary() gives the predictive probability and its interval over the draws, result.cov() the
+        Monte-Carlo error of a draw's own number.  Raises ValueError for an emulator with a likelihood node or a
+        Categorical top and for bad bounds, output or counts; NotImplementedError for draws made by
+        sample_functions_vecchia."""
+        from . import reliability
+        return reliability.failure_probability(*self._lane_values(bounds, 'failure_probability'), threshold, bounds, output,
+                                               below, n_particles, level_prob, n_moves, max_stages, min_prob, seed, step,
+                                               prior, target_accept)
+
+    def _lane_values(self, bounds, what):
+        """_lane_problem's sibling for a driver without gradients: (engine, P, K, Dx, values) after the same refusals,
+        values the walk at per-path rows (P, R, Dx) -> (P, R, K), no Jacobian."""
+        e, P, K, Dx = self._lane_problem(bounds, what)[:4]
+
+        def values(xt):
+            for cur, _ in self._walk(xt):
+                pass
+            return cur.contiguous()
+        return e, P, K, Dx, values
+
     def _lane_problem(self, bounds, what):
         """What minimize and calibrate hand to their drivers after their common refusals: (engine, P, K, Dx, values,
         value_and_jac, width), the closures over the shared-rows walk and the walk at per-path rows."""
@@ -581,6 +618,25 @@ class GpPaths:
         return calibrate.calibrate_smc(*self._lane_problem(bounds, 'calibrate_smc'), np.reshape(y, (-1, 1)) if np.ndim(y) < 2 else y,
                                        obs_sd, bounds, n_particles, n_moves, ess_frac, max_stages, seed, step, scale, prior,
                                        target_accept)
+
+    def failure_probability(self, threshold, bounds, output=0, below=False, n_particles=1024, level_prob=0.1, n_moves=4,
+                            max_stages=50, min_prob=1e-12, seed=None, step=1.0, prior=None, target_accept=0.44):
+        """PathFunctions.failure_probability for the sample_size draws of a gp model (P = sample_size, one output): every
+        draw's probability of reaching threshold over the box, by subset simulation; a column of x that the GP does not read
+        moves under its prior alone."""
+        from . import reliability
+        return reliability.failure_probability(*self._lane_values(bounds, 'failure_probability'), threshold, bounds, output,
+                                               below, n_particles, level_prob, n_moves, max_stages, min_prob, seed, step,
+                                               prior, target_accept)
+
+    def _lane_values(self, bounds, what):
+        """PathFunctions._lane_values for the one node of a gp model."""
+        e, J, K, Dx = self._lane_problem(bounds, what)[:4]
+        cols = torch.as_tensor(self.columns, device=e.device)
+
+        def values(xt):
+            return self.node(e, xt[:, :, cols].contiguous())[:, :, None].contiguous()
+        return e, J, K, Dx, values
 
     def _lane_problem(self, bounds, what):
         """PathFunctions._lane_problem for the one node of a gp model."""

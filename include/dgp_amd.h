@@ -894,6 +894,64 @@ int dgpamd_boxsmc_temper(dgpamd_ctx *ctx, int64_t P, int64_t R, int D, double es
                          const double *u, double *beta, double *dbeta, double *log_evidence, double *stage_ess, int32_t *status,
                          int32_t *anc, double *x_trial, int32_t *running);
 
+/* ---- subset simulation over a box: the probability of a rare event of a function draw (DESIGN I.22) ----
+ * P draws with R particles each, 1 <= R <= DGPAMD_BOXSUS_MAXR (a level needs R >= 2), lane q = p R + r, P R < 2^31, 1 <= D <= 64.
+ *   score = sign (f[q, output] - threshold) + 0.0 (the + 0.0 turns -0 into +0), sign = +1 or -1; the event is F = {score >= 0}.
+ * A particle whose score is NaN is dead: never a survivor, and the divisor stays R.  n_s = max(1, floor(level_prob R)) is the
+ * caller's, 1 <= n_s < R.  The driver (reliability.failure_probability; tests/boxsus_ref.py restates both calls and the
+ * schedule): particles from the prior on the box, one walk evaluation and MOVE(first, last); sd (P, D) filled by the caller
+ * with the prior particles' spread per column; then stages of LEVEL and n_moves + 1 walk evaluations with MOVE behind each,
+ * first on the first and last on the last; after a stage lam[p] <- clamp(lam[p] exp(acceptance rate - target), 1e-3, 1e2).
+ * State the caller owns and may read: x (D x Q, particle fastest), score (Q), moved, status, n_prop, n_acc (Q) int32 per
+ * particle (status DGPAMD_BOXSUS_OK or _NAN); per draw prob (P, ones at first), level, lam (P), sd (P, D), nsurv, done, status
+ * (P) int32, anc (P, R) int32; running (1) int32.  par and its host copy par_h: pv (D), pm (D), lo (D), hi (D), the prior
+ * prop. to exp(-1/2 sum_d pv_d (x_d - pm_d)^2) on the box, pv_d = 0 flat.
+ *
+ * dgpamd_boxsus_level: one workgroup per draw.  A draw with done = 0: k = min(n_s, live count), b = the k-th largest live
+ * score.  b >= 0: the level is +0.0 and this is the draw's final stage; else the level is b.  Survivors: the live particles
+ * with score >= level, in increasing particle index; n_b their count (ties at the level all survive).  Then
+ *   prob[p] <- prob[p] * ((double)n_b / (double)R); nsurv[p] = n_b; level[p] = the level;
+ *   done[p] <- 1 in the final stage, else when prob[p] < min_prob, with status DGPAMD_BOXSUS_BELOW_MIN;
+ *   anc[p, j] = the (j mod n_b)-th survivor; x_trial[p, j, :] = x[:, p R + anc[p, j]];
+ *   sd[p, d] = sqrt(sum_surv (x_d - mean_d)^2 / n_b), mean_d = sum_surv x_d / n_b, every sum in an order that R alone fixes
+ *   (thread t of T = min(1024, R rounded up to 64) adds its particles t, t + T, ... in order, the 64 lanes of a wave combine
+ *   by an xor butterfly 32, 16, .. 1, the wave totals add in index order); a column whose new value is 0 or not finite keeps
+ *   its old sd.
+ * No live particle: status DGPAMD_BOXSUS_NAN, prob NaN, nsurv 0, done 1, the particles stay.  A draw with done = 1: anc the
+ * identity, x_trial = x, nothing else touched.  running[0] = the number of draws with done = 0 after the call.
+ * A draw's outputs do not depend on P or on the draws beside it.  DGPAMD_BOXSUS_MAX_STAGES is the driver's.
+ * DGPAMD_BAD_ARG: the sizes above, n_s outside 1 .. R - 1, min_prob outside [0, 1), a null pointer.
+ *
+ * dgpamd_boxsus_move: the component-wise modified Metropolis move of Au and Beck (2001), one lane per particle.  f (Q, K): the
+ * walk's values at x_trial (Q, D), of which column `output` alone is read; z, logu (Q, D): this call's normal draws and
+ * logarithms of uniform draws, logu read only where pv_d > 0.  Per particle and call, in this order:
+ *   SCORE    score' as above.
+ *   INIT     (first != 0) (x, score) <- the trial's; counts 0; the moved flag down; score' NaN: status NAN, else OK.
+ *   DECIDE   (first = 0, status OK) accept iff the moved flag is set and score' >= level[p] (a NaN comparison rejects); on
+ *            acceptance (x, score) <- the trial's.  n_prop += 1, n_acc += accepted.
+ *   HOLD     status NAN, or last != 0: x_trial = x, and nothing more.
+ *   PROPOSE  else, on every free column (a column with lo_d = hi_d or sd[p, d] = 0 is fixed: it keeps x_d):
+ *            c = x_d + (lam_p sd_pd) z_d, kept iff lo_d <= c <= hi_d and either pv_d = 0 or
+ *            logu_qd < ((-0.5 (pv_d e')) e') - ((-0.5 (pv_d e)) e), e' = c - pm_d, e = x_d - pm_d;
+ *            a column not kept stays at x_d.  The moved flag is set iff any column was kept (x_trial = x otherwise, and the
+ *            next DECIDE counts a rejection).
+ * Products are not fused into sums; the kernel has no generator and needs no workspace.  DGPAMD_BAD_ARG: the sizes above,
+ * K < 1, output outside 0 .. K - 1, sign not +1 or -1, a threshold that is not finite, a pv that is negative or NaN, a bound
+ * with lo > hi or NaN, a null pointer. */
+#define DGPAMD_BOXSUS_OK 0
+#define DGPAMD_BOXSUS_NAN 1
+#define DGPAMD_BOXSUS_MAX_STAGES 2
+#define DGPAMD_BOXSUS_BELOW_MIN 3
+#define DGPAMD_BOXSUS_COUNT 4
+#define DGPAMD_BOXSUS_MAXR 8192
+int dgpamd_boxsus_move(dgpamd_ctx *ctx, int64_t P, int64_t R, int D, int K, int output, double sign, double threshold,
+                       const double *f, const double *par, const double *par_h, const double *level, const double *lam,
+                       const double *sd, const double *z, const double *logu, int first, int last, double *x_trial, double *x,
+                       double *score, int32_t *moved, int32_t *status, int32_t *n_prop, int32_t *n_acc);
+int dgpamd_boxsus_level(dgpamd_ctx *ctx, int64_t P, int64_t R, int D, int n_s, double min_prob, const double *score,
+                        const double *x, double *prob, double *level, int32_t *nsurv, int32_t *done, int32_t *status, int32_t *anc,
+                        double *x_trial, double *sd, int32_t *running);
+
 #ifdef __cplusplus
 }
 #endif
