@@ -25,6 +25,7 @@ lib = C.CDLL(LIB_PATH)
 _p = C.c_void_p
 _i = C.c_int
 _l = C.c_int64
+_u = C.c_uint64
 _d = C.c_double
 _z = C.c_size_t
 
@@ -143,6 +144,7 @@ SIGNATURES = {
     'dgpamd_boxsmc_temper': (_i, [_p, _l, _l, _i, _d, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     'dgpamd_boxsus_move': (_i, [_p, _l, _l, _i, _i, _i, _d, _d, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     'dgpamd_boxsus_level': (_i, [_p, _l, _l, _i, _i, _d, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'dgpamd_philox_fill': (_i, [_p, _i, _u, _u, _u, _u, _l, _l, _l, _i, _p]),
 }
 
 MISSING = []

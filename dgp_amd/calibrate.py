@@ -9,8 +9,9 @@ it for every draw and pooling the samples with equal weights gives the MODULAR (
 P draws with R chains each are P R independent Metropolis-adjusted Langevin chains.  They advance in lock-step: a round
 evaluates every chain's trial point through the layer walk at per-path rows (P, R, Dx), values and Jacobian, and
 dgpamd_boxmala_step (one lane per chain) decides the proposals, adapts the steps during warm-up, stores the samples and writes
-the next trial points.  The normal and uniform draws come from numpy generators, uploaded in blocks of rounds; nothing visits
-the host until the end.  The starts are the best of n_candidates rows in the box, screened through the shared-rows walk.
+the next trial points.  The normal and uniform draws come from numpy generators, uploaded in blocks of rounds, or with
+rng='device' from counter-based streams filled on the device (dgpamd_philox_fill, DESIGN I.23); nothing visits the host until
+the end.  The starts are the best of n_candidates rows in the box, screened through the shared-rows walk.
 method='hmc' (DESIGN I.20) runs the same loop with dgpamd_boxhmc_step: an iteration is a trajectory of L leapfrog steps, one
 round each, with the walls of the box reflecting; L is n_leapfrog, or with jitter uniform on 1 .. n_leapfrog per iteration.
 calibrate_smc (DESIGN I.21) samples the same posteriors by adaptive likelihood tempering: R particles per draw from the prior,
@@ -113,6 +114,43 @@ class Streams:
         return z, logu
 
 
+# ------------------------------------------------------------------------- random streams made on the device (DESIGN I.23)
+RNGS = ('numpy', 'device')
+STREAM_PRIOR, STREAM_NORMAL, STREAM_LOGU, STREAM_RESAMPLE = 0, 1, 2, 3      # c3 of dgpamd_philox_fill's counter
+
+
+def check_rng(rng, what):
+    if rng not in RNGS:
+        raise ValueError("%s: rng must be 'numpy' or 'device'" % what)
+    return rng == 'device'
+
+
+def stage_round(t, i=0):
+    """The round c2 of move i of stage t in calibrate_smc and failure_probability: (t << 32) | i."""
+    return (int(t) << 32) | int(i)
+
+
+def upload(e, a):
+    """e.tensor for what a numpy stream returns; what a device stream returns is on the device already."""
+    return a if torch.is_tensor(a) else e.tensor(a)
+
+
+class DeviceStreams:
+    """Streams' twin for rng='device': the same method, device tensors, the numbers Philox4x64-10 under the key
+    SeedSequence(seed).generate_state(2, uint64) (Engine.philox_fill).  z is stream 1 with Dx elements per slot, log u stream 2
+    with one; the round c2 is the iteration index, so chain (p, r)'s numbers of iteration c depend on nothing else: not on
+    P, R or the block size."""
+
+    def __init__(self, e, seed, P, R, Dx):
+        self.e, self.key, self.P, self.R, self.Dx, self.c = e, Engine.philox_key(seed), P, R, Dx, 0
+
+    def block(self, rounds):
+        """(z (rounds, P, R, Dx), log u (rounds, P, R)) of the next `rounds` rounds, on the device."""
+        c, self.c = self.c, self.c + rounds
+        return (self.e.philox_fill('normal', self.key, STREAM_NORMAL, c, rounds, self.P, self.R, self.Dx),
+                self.e.philox_fill('log_uniform', self.key, STREAM_LOGU, c, rounds, self.P, self.R, 1).view(rounds, self.P, self.R))
+
+
 # ---------------------------------------------------------------------------------------------- diagnostics (host numpy)
 def split_rhat(x):
     """The split potential scale reduction of x (..., R, S), S >= 4 samples of R chains: every chain is cut in two halves,
@@ -173,13 +211,15 @@ class PathPosterior:
     numbers of calibrate.STATUS (= Engine.BOXMALA, DGPAMD_BOXMALA_*; Engine.BOXHMC carries the same): ok 0; nan 1 the start's
     value or gradient was not finite (the chain repeats its start).  x0 (P, R, Dx): the starts.  rounds: the evaluations of
     the lock-step loop.  method 'mala' or 'hmc'; n_leapfrog: the (largest) trajectory length of 'hmc', 1 for 'mala';
-    evaluations: the walk evaluations of the run (None: rounds).
+    evaluations: the walk evaluations of the run (None: rounds).  rng: 'numpy' or 'device', where the run's normal and uniform
+    numbers were made.
     rhat, ess (P, Dx): the split R-hat over a draw's R chains and the effective sample size of a draw's posterior mean.
     Row p is path p of the draws' container (s * sample_size + j for an emulator)."""
 
-    def __init__(self, x, logp, accept_rate, step, status, x0, rounds, method='mala', n_leapfrog=1, evaluations=None):
+    def __init__(self, x, logp, accept_rate, step, status, x0, rounds, method='mala', n_leapfrog=1, evaluations=None, rng='numpy'):
         self.x, self.logp, self.accept_rate, self.step, self.status, self.x0, self.rounds = x, logp, accept_rate, step, status, x0, rounds
         self.method, self.n_leapfrog, self.evaluations = method, n_leapfrog, rounds if evaluations is None else evaluations
+        self.rng = rng
         self._rhat = self._ess = None
 
     @property
@@ -215,12 +255,14 @@ class PathPosterior:
 
 
 def calibrate(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, n_chains=4, n_samples=500, warmup=500, thin=1,
-              n_candidates=2048, x0=None, seed=None, qmc=False, step=0.1, scale=None, prior=None, target_accept=None, method='mala',
-              n_leapfrog=8, jitter=True):
+              n_candidates=2048, x0=None, seed=None, qmc=False, step=0.1, scale=None, prior=None, rng='numpy', target_accept=None,
+              method='mala', n_leapfrog=8, jitter=True):
     """The driver behind PathFunctions.calibrate and GpPaths.calibrate; values, value_and_jac and width as in
-    optimize.minimize."""
+    optimize.minimize.  rng='device': the chains' normals and uniforms are made on the device (DeviceStreams) instead of by
+    numpy generators and an upload; the candidate design and HMC's trajectory lengths stay numpy's."""
     if method not in TARGET_ACCEPT:
         raise ValueError("calibrate: method must be 'mala' or 'hmc'")
+    device_rng = check_rng(rng, 'calibrate')
     n_leapfrog = int(n_leapfrog)
     if n_leapfrog < 1:
         raise ValueError('calibrate: need n_leapfrog >= 1')
@@ -263,13 +305,13 @@ def calibrate(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, n_ch
     # trajectory with the momenta z_c.
     hmc = method == 'hmc'
     state = (e.boxhmc_state if hmc else e.boxmala_state)(Q, Dx, w, ybar, lo, hi, scale, pv, pm, n_slots=S)
-    streams = Streams(seed, P, R, Dx)
+    streams = DeviceStreams(e, seed, P, R, Dx) if device_rng else Streams(seed, P, R, Dx)
     total = 1 + warmup + S * thin
     lengths = trajectory_lengths(seed, total - 1, n_leapfrog, jitter) if hmc else None
     block = _rounds_per_upload(Q, Dx)
     before, rounds = None, 0
     for c0 in range(0, total, block):
-        zb, ub = map(e.tensor, streams.block(min(block, total - c0)))
+        zb, ub = (upload(e, a) for a in streams.block(min(block, total - c0)))
         for i in range(len(zb)):
             c = c0 + i
             adapt, j = 1 <= c <= warmup, c - warmup
@@ -292,7 +334,7 @@ def calibrate(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, n_ch
     return PathPosterior(np.ascontiguousarray(host['xs'].reshape(S, Dx, P, R).transpose(2, 3, 0, 1)),
                          np.ascontiguousarray(host['lps'].reshape(S, P, R).transpose(1, 2, 0)),
                          (n_acc / np.maximum(n_prop, 1)).reshape(P, R), host['h'].reshape(P, R), host['status'].reshape(P, R),
-                         np.array(x0), rounds, method, n_leapfrog if hmc else 1, rounds)
+                         np.array(x0), rounds, method, n_leapfrog if hmc else 1, rounds, rng)
 
 
 # ------------------------------------------------------------------------- tempered SMC with per-draw evidence (DESIGN I.21)
@@ -361,6 +403,33 @@ class SmcStreams:
         return self._rng(3, t).random(self.P), np.ascontiguousarray(z.transpose(2, 0, 1, 3)), np.ascontiguousarray(logu.transpose(2, 0, 1))
 
 
+class DeviceSmcStreams:
+    """SmcStreams' twin for rng='device' (Engine.philox_fill under the key of the seed): the prior uniforms are stream 0 at
+    round 0; stage t reads its resampling uniform from stream 3 at (c2 = t << 32, r = 0), z from stream 1 (Dx elements) and
+    log u from stream 2 (one element) at c2 = (t << 32) | i for move i.  Particle (p, r)'s numbers depend on nothing but the
+    seed, p, r, t and i."""
+
+    def __init__(self, e, seed, P, R, Dx):
+        self.e, self.key, self.P, self.R, self.Dx, self.t = e, Engine.philox_key(seed), P, R, Dx, 0
+
+    def prior_uniforms(self):
+        """(P, R, Dx) uniforms in [0, 1), on the device."""
+        return self.e.philox_fill('uniform', self.key, STREAM_PRIOR, 0, 1, self.P, self.R, self.Dx)[0]
+
+    def stage(self, rounds):
+        """(u (P,), z (rounds, P, R, Dx), log u (rounds, P, R)) of the next stage, on the device."""
+        t, self.t = self.t, self.t + 1
+        c2, fill = stage_round(t), self.e.philox_fill
+        return (fill('uniform', self.key, STREAM_RESAMPLE, c2, 1, self.P, 1, 1).view(self.P),
+                fill('normal', self.key, STREAM_NORMAL, c2, rounds, self.P, self.R, self.Dx),
+                fill('log_uniform', self.key, STREAM_LOGU, c2, rounds, self.P, self.R, 1).view(rounds, self.P, self.R))
+
+
+def host_uniforms(u):
+    """The prior uniforms on the host: a device stream's visit it once, for prior_draws."""
+    return u.cpu().numpy() if torch.is_tensor(u) else u
+
+
 def _weighted_quantile(v, wt, q):
     """The q-quantile of the columns of v (n, Dx) under the weights wt (n,): the smallest value whose cumulative weight
     reaches q."""
@@ -383,14 +452,16 @@ class ParticlePosterior:
     stage_ess NaN.  step (P, R): the adapted steps.  status (P,): calibrate.SMC_STATUS (= Engine.BOXSMC): ok 0; nan 1 no
     particle had a finite likelihood; max_stages 2 the draw ended below beta = 1 (its particles sample pi_beta, its
     evidence is partial).  n_stages; evaluations: the walk evaluations of the stages, n_stages (n_moves + 1) -- the one of
-    the prior particles comes on top.
+    the prior particles comes on top.  rng: 'numpy' or 'device', where the run's random numbers were made.
     Evidence weighting: draw_weights() is the softmax of log_evidence over the ok draws.  The draws f_p are P samples of the
     emulator's prior-predictive functions, so weighting them by p(y | f_p) is a self-normalised importance estimate of the
     posterior that feeds the observation back to the emulator -- over P functions only.  draw_ess = 1 / sum W^2 says how
     many of them carry it: when it is small, the weighted answer rests on few draws and more of them are needed; pooled()
     with equal weights stays the modular (cut) posterior."""
 
-    def __init__(self, x, loglik, logp, log_evidence, log_norm, betas, stage_ess, accept_rate, step, status, n_stages, evaluations):
+    def __init__(self, x, loglik, logp, log_evidence, log_norm, betas, stage_ess, accept_rate, step, status, n_stages, evaluations,
+                 rng='numpy'):
+        self.rng = rng
         self.x, self.loglik, self.logp, self.log_evidence, self.log_norm = x, loglik, logp, log_evidence, log_norm
         self.betas, self.stage_ess, self.accept_rate, self.step, self.status = betas, stage_ess, accept_rate, step, status
         self.n_stages, self.evaluations = n_stages, evaluations
@@ -451,11 +522,13 @@ class ParticlePosterior:
 
 
 def calibrate_smc(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, n_particles=1024, n_moves=4, ess_frac=0.5,
-                  max_stages=100, seed=None, step=0.1, scale=None, prior=None, target_accept=0.574):
+                  max_stages=100, seed=None, step=0.1, scale=None, prior=None, target_accept=0.574, rng='numpy'):
     """The driver behind PathFunctions.calibrate_smc and GpPaths.calibrate_smc: adaptive likelihood tempering (Del Moral,
     Doucet and Jasra 2006).  A stage is dgpamd_boxsmc_temper, then n_moves + 1 walk evaluations with dgpamd_boxsmc_move
     behind each: the start of the stage at the resampled particles, then n_moves decisions.  Only the count of draws below
-    beta = 1 visits the host, once per stage."""
+    beta = 1 visits the host, once per stage.  rng='device': every random number is made on the device (DeviceSmcStreams);
+    the prior uniforms visit the host once, for prior_draws."""
+    device_rng = check_rng(rng, 'calibrate_smc')
     lo, hi = optimize.check_bounds(bounds, Dx, 'calibrate_smc')
     Dx = len(lo)
     ybar, w = observation(y, obs_sd, K)
@@ -472,15 +545,15 @@ def calibrate_smc(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, 
         raise ValueError('calibrate_smc: scale must be (%d,) finite numbers >= 0' % Dx)
     if not (np.isfinite(step) and HMIN <= step <= HMAX) or not 0.0 < target_accept < 1.0:
         raise ValueError('calibrate_smc: need %g <= step <= %g and 0 < target_accept < 1' % (HMIN, HMAX))
-    streams = SmcStreams(seed, P, R, Dx)
-    xt = e.tensor(np.ascontiguousarray(prior_draws(streams.prior_uniforms(), lo, hi, pv, pm)))
+    streams = DeviceSmcStreams(e, seed, P, R, Dx) if device_rng else SmcStreams(seed, P, R, Dx)
+    xt = e.tensor(np.ascontiguousarray(prior_draws(host_uniforms(streams.prior_uniforms()), lo, hi, pv, pm)))
     state = e.boxsmc_state(P, R, Dx, w, ybar, lo, hi, scale, pv, pm, h0=step)
     # the likelihood of the prior particles: a stage's start under beta = 0 that ends at once (z and log u are not read)
     f, J = value_and_jac(xt)
     e.boxsmc_move(state, f, J, xt, e.zeros(P, R, Dx), e.zeros(P, R), HMIN, HMAX, first=True, last=True)
     betas, stage_ess, accept = [], [], []
     for stage in range(max_stages):
-        u, zb, ub = map(e.tensor, streams.stage(n_moves + 1))
+        u, zb, ub = (upload(e, a) for a in streams.stage(n_moves + 1))
         e.boxsmc_temper(state, xt, u, ess_frac)
         betas.append(state['beta'].clone())
         stage_ess.append(state['stage_ess'].clone())
@@ -501,4 +574,4 @@ def calibrate_smc(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, 
     ll = host['ll'].reshape(P, R)
     return ParticlePosterior(np.ascontiguousarray(host['x'].reshape(Dx, P, R).transpose(1, 2, 0)), ll,
                              ll + host['lprior'].reshape(P, R), host['log_evidence'], log_norm(y, obs_sd, K), stack(betas),
-                             stack(stage_ess), stack(accept), host['h'].reshape(P, R), status, T, T * (n_moves + 1))
+                             stack(stage_ess), stack(accept), host['h'].reshape(P, R), status, T, T * (n_moves + 1), rng)

@@ -1035,6 +1035,47 @@ class Engine:
             _dp(x_trial), _dp(state['sd']), _dp(state['running'])))
         return x_trial
 
+    # counter-based random streams (csrc/philox.hip)
+    PHILOX = dict(bits=0, uniform=1, log_uniform=2, normal=3)
+
+    @staticmethod
+    def philox_key(seed):
+        """(key0, key1) of a seed: numpy.random.SeedSequence(seed).generate_state(2, uint64); None draws fresh entropy."""
+        k = np.random.SeedSequence(seed).generate_state(2, np.uint64)
+        return int(k[0]), int(k[1])
+
+    @staticmethod
+    def philox_check(kind, key, stream, c2_first, rounds, P, R, D):
+        """philox_fill's refusals, which need no device; (kind number, key0, key1, stream, c2_first, rounds, P, R, D)."""
+        if kind not in Engine.PHILOX:
+            raise ValueError('philox: kind must be one of %s' % ', '.join(Engine.PHILOX))
+        try:
+            k0, k1 = (int(k) for k in key)
+        except (TypeError, ValueError):
+            raise ValueError('philox: key must be two integers in 0 .. 2^64 - 1') from None
+        stream, c2_first, rounds, P, R, D = int(stream), int(c2_first), int(rounds), int(P), int(R), int(D)
+        if any(not 0 <= v < 2 ** 64 for v in (k0, k1, stream, c2_first)):
+            raise ValueError('philox: key, stream and c2_first must lie in 0 .. 2^64 - 1')
+        if rounds < 1 or P < 1 or R < 1 or not 1 <= D <= _lib.MAXD:
+            raise ValueError('philox: need rounds >= 1, P >= 1, R >= 1 and 1 <= D <= %d' % _lib.MAXD)
+        if P >= 2 ** 31 or R >= 2 ** 32 or c2_first + rounds >= 2 ** 64 or rounds * P * R > 2 ** 56:
+            raise ValueError('philox: need P < 2^31, R < 2^32, c2_first + rounds < 2^64 and rounds P R <= 2^56')
+        return Engine.PHILOX[kind], k0, k1, stream, c2_first, rounds, P, R, D
+
+    def philox_fill(self, kind, key, stream, c2_first, rounds, P, R, D, out=None):
+        """(rounds, P, R, D) numbers of one Philox4x64-10 stream, made on the device (dgpamd_philox_fill): entry [i, p, r, e] is
+        a pure function of (key, stream, c2_first + i, p, r, e), whatever the shape of the call.  kind: a key of Engine.PHILOX --
+        'bits' the raw words (int64), 'uniform' in [0, 1), 'log_uniform', 'normal' (float64).  key: two 64-bit integers
+        (philox_key(seed)).  out: a contiguous tensor of that shape and type to fill instead of a new one."""
+        args = self.philox_check(kind, key, stream, c2_first, rounds, P, R, D)
+        shape, dtype = args[5:], torch.int64 if kind == 'bits' else torch.float64
+        if out is None:
+            out = self.empty(*shape, dtype=dtype)
+        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or out.device != self.device:
+            raise ValueError('philox: out must be a contiguous %s device tensor (rounds, P, R, D)' % dtype)
+        self._chk(self._enter() or lib.dgpamd_philox_fill(self.h, *args, _dp(out)))
+        return out
+
     # --------------------------------------------------------------- vecchia
     def nn_ordered(self, x, m):
         n, D = x.shape

@@ -350,7 +350,8 @@ class PathFunctions:
                                  seed, qmc, maxiter, gtol, ftol, history, check_every, max_eval)
 
     def calibrate(self, y, obs_sd, bounds, n_chains=4, n_samples=500, warmup=500, thin=1, n_candidates=2048, x0=None, seed=None,
-                  qmc=False, step=0.1, scale=None, prior=None, target_accept=None, method='mala', n_leapfrog=8, jitter=True):
+                  qmc=False, step=0.1, scale=None, prior=None, rng='numpy', target_accept=None, method='mala', n_leapfrog=8,
+                  jitter=True):
         """The posterior of the input x given an observation of the outputs, for every draw, on the device (calibrate,
         DESIGN I.19): a calibrate.PathPosterior with x (P, R, S, Dx), logp (P, R, S), P = N * sample_size draws, R =
         n_chains chains, S = n_samples samples.  Draw p's chains sample p(x | y, f_p) proportional to prior(x) N(y; f_p(x),
@@ -367,17 +368,19 @@ class PathFunctions:
         evaluation each, with the walls of the box reflecting; result.evaluations counts the walk evaluations.
         Starts: x0 (R, Dx) shared or (P, R, Dx), projected into the box; else per draw the n_chains rows of highest posterior density among n_candidates rows in the box (as minimize draws them), ties to
         the lower row.  The normal and uniform draws come from np.random.SeedSequence(seed): the same arguments give the
-        same bits, and chain (p, r) does not depend on the chains beside it.  result.rhat and result.ess (P, Dx) are the
+        same bits, and chain (p, r) does not depend on the chains beside it.  rng='device' makes the normal and uniform numbers on the device instead
+        (Philox4x64-10 streams keyed by the seed, DESIGN I.23: other numbers than rng='numpy' gives, as reproducible, and
+        particle or chain (p, r)'s own whatever runs beside it); result.rng records it.  result.rhat and result.ess (P, Dx) are the
         split R-hat and the effective sample size per draw; result.summary() the pooled mean and interval.  Raises
         ValueError for an emulator with a likelihood node or a Categorical top and for bad bounds, y, obs_sd or counts;
         NotImplementedError for draws made by sample_functions_vecchia."""
         from . import calibrate
         return calibrate.calibrate(*self._lane_problem(bounds, 'calibrate'), y, obs_sd, bounds, n_chains, n_samples, warmup, thin,
-                                   n_candidates, x0, seed, qmc, step, scale, prior, target_accept, method, n_leapfrog,
+                                   n_candidates, x0, seed, qmc, step, scale, prior, rng, target_accept, method, n_leapfrog,
                                    jitter)
 
     def calibrate_smc(self, y, obs_sd, bounds, n_particles=1024, n_moves=4, ess_frac=0.5, max_stages=100, seed=None, step=0.1,
-                      scale=None, prior=None, target_accept=0.574):
+                      scale=None, prior=None, target_accept=0.574, rng='numpy'):
         """calibrate's posteriors by tempered sequential Monte Carlo, with every draw's evidence, on the device (DESIGN
         I.21): a calibrate.ParticlePosterior with x (P, n_particles, Dx) and log_evidence (P,), the estimate of log of the
         integral of prior(x) exp(ll_p(x)) over the box under the normalised prior.  y, obs_sd, bounds, prior, scale, step
@@ -388,14 +391,17 @@ class PathFunctions:
         from the stage's acceptance rate towards target_accept.  The particles do not start in a
         mode, so a multimodal posterior keeps its modes in proportion.  At most max_stages steps: a draw still below
         beta = 1 has status max_stages.  n_particles <= calibrate.MAX_PARTICLES.  The random numbers come from
-        np.random.SeedSequence(seed); draw p's do not depend on the draws beside it.  result.draw_weights() weighs the draws
+        np.random.SeedSequence(seed); draw p's do not depend on the draws beside it.  rng='device' makes the normal and uniform numbers on the device instead
+        (Philox4x64-10 streams keyed by the seed, DESIGN I.23: other numbers than rng='numpy' gives, as reproducible, and
+        particle or chain (p, r)'s own whatever runs beside it); result.rng records it.  result.draw_weights() weighs the draws
         by their evidence; result.pooled() stays the modular posterior.  Raises as calibrate does."""
         from . import calibrate
         return calibrate.calibrate_smc(*self._lane_problem(bounds, 'calibrate_smc'), y, obs_sd, bounds, n_particles, n_moves,
-                                       ess_frac, max_stages, seed, step, scale, prior, target_accept)
+                                       ess_frac, max_stages, seed, step, scale, prior, target_accept, rng)
 
     def failure_probability(self, threshold, bounds, output=0, below=False, n_particles=1024, level_prob=0.1, n_moves=4,
-                            max_stages=50, min_prob=1e-12, seed=None, step=1.0, prior=None, target_accept=0.44):
+                            max_stages=50, min_prob=1e-12, seed=None, step=1.0, prior=None, target_accept=0.44,
+                            rng='numpy'):
         """The probability that output `output` of the last layer reaches threshold (below: falls to it) when x is
         distributed over the box bounds (Dx, 2), for every draw, on the device (reliability, DESIGN I.22): a
         reliability.FailureProbability with prob (P,), P = N * sample_size, the estimate of prior{x : f_p(x) >= threshold}
@@ -409,14 +415,16 @@ class PathFunctions:
         At most max_stages stages (status max_stages), and none once the running product is under min_prob (status
         below_min): prob is then an upper bound.  n_particles <= reliability.MAX_PARTICLES.  The random numbers come from
         np.random.SeedSequence(seed); draw p's do not depend on the draws beside it, and the same arguments give the same
-        bits.  result.summary() gives the predictive probability and its interval over the draws, result.cov() the
+        bits.  rng='device' makes the normal and uniform numbers on the device instead
+        (Philox4x64-10 streams keyed by the seed, DESIGN I.23: other numbers than rng='numpy' gives, as reproducible, and
+        particle or chain (p, r)'s own whatever runs beside it); result.rng records it.  result.summary() gives the predictive probability and its interval over the draws, result.cov() the
         Monte-Carlo error of a draw's own number.  Raises ValueError for an emulator with a likelihood node or a
         Categorical top and for bad bounds, output or counts; NotImplementedError for draws made by
         sample_functions_vecchia."""
         from . import reliability
         return reliability.failure_probability(*self._lane_values(bounds, 'failure_probability'), threshold, bounds, output,
                                                below, n_particles, level_prob, n_moves, max_stages, min_prob, seed, step,
-                                               prior, target_accept)
+                                               prior, target_accept, rng)
 
     def _lane_values(self, bounds, what):
         """_lane_problem's sibling for a driver without gradients: (engine, P, K, Dx, values) after the same refusals,
@@ -601,33 +609,35 @@ class GpPaths:
                                  seed, qmc, maxiter, gtol, ftol, history, check_every, max_eval)
 
     def calibrate(self, y, obs_sd, bounds, n_chains=4, n_samples=500, warmup=500, thin=1, n_candidates=2048, x0=None, seed=None,
-                  qmc=False, step=0.1, scale=None, prior=None, target_accept=None, method='mala', n_leapfrog=8, jitter=True):
+                  qmc=False, step=0.1, scale=None, prior=None, rng='numpy', target_accept=None, method='mala', n_leapfrog=8,
+                  jitter=True):
         """The posterior of the input x given an observation y (a number, (1,) or (T, 1) replicates) of the GP's output, for
         every draw: PathFunctions.calibrate for the sample_size draws of a gp model (P = sample_size, one output), the
         modular posterior when pooled; a column of x that the GP does not read is sampled from its prior."""
         from . import calibrate
         return calibrate.calibrate(*self._lane_problem(bounds, 'calibrate'), np.reshape(y, (-1, 1)) if np.ndim(y) < 2 else y,
                                    obs_sd, bounds, n_chains, n_samples, warmup, thin, n_candidates, x0, seed, qmc, step, scale,
-                                   prior, target_accept, method, n_leapfrog, jitter)
+                                   prior, rng, target_accept, method, n_leapfrog, jitter)
 
     def calibrate_smc(self, y, obs_sd, bounds, n_particles=1024, n_moves=4, ess_frac=0.5, max_stages=100, seed=None, step=0.1,
-                      scale=None, prior=None, target_accept=0.574):
+                      scale=None, prior=None, target_accept=0.574, rng='numpy'):
         """PathFunctions.calibrate_smc for the sample_size draws of a gp model (P = sample_size, one output; y as in
         calibrate): tempered SMC particles of every draw's posterior and its evidence."""
         from . import calibrate
         return calibrate.calibrate_smc(*self._lane_problem(bounds, 'calibrate_smc'), np.reshape(y, (-1, 1)) if np.ndim(y) < 2 else y,
                                        obs_sd, bounds, n_particles, n_moves, ess_frac, max_stages, seed, step, scale, prior,
-                                       target_accept)
+                                       target_accept, rng)
 
     def failure_probability(self, threshold, bounds, output=0, below=False, n_particles=1024, level_prob=0.1, n_moves=4,
-                            max_stages=50, min_prob=1e-12, seed=None, step=1.0, prior=None, target_accept=0.44):
+                            max_stages=50, min_prob=1e-12, seed=None, step=1.0, prior=None, target_accept=0.44,
+                            rng='numpy'):
         """PathFunctions.failure_probability for the sample_size draws of a gp model (P = sample_size, one output): every
         draw's probability of reaching threshold over the box, by subset simulation; a column of x that the GP does not read
         moves under its prior alone."""
         from . import reliability
         return reliability.failure_probability(*self._lane_values(bounds, 'failure_probability'), threshold, bounds, output,
                                                below, n_particles, level_prob, n_moves, max_stages, min_prob, seed, step,
-                                               prior, target_accept)
+                                               prior, target_accept, rng)
 
     def _lane_values(self, bounds, what):
         """PathFunctions._lane_values for the one node of a gp model."""

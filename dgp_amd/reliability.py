@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import optimize
-from .calibrate import check_prior, prior_draws
+from .calibrate import STREAM_LOGU, STREAM_NORMAL, STREAM_PRIOR, check_prior, check_rng, host_uniforms, prior_draws, stage_round, upload
 from .ops import Engine
 
 STATUS = Engine.BOXSUS
@@ -50,6 +50,26 @@ class SusStreams:
         return np.ascontiguousarray(z.transpose(2, 0, 1, 3)), np.ascontiguousarray(logu.transpose(2, 0, 1, 3))
 
 
+class DeviceSusStreams:
+    """SusStreams' twin for rng='device' (Engine.philox_fill under the key of the seed, DESIGN I.23): the prior uniforms are
+    stream 0 at round 0; stage t reads z from stream 1 and log u from stream 2, Dx elements each, at c2 = (t << 32) | i for
+    move i.  Particle (p, r)'s numbers depend on nothing but the seed, p, r, t and i."""
+
+    def __init__(self, e, seed, P, R, Dx):
+        self.e, self.key, self.P, self.R, self.Dx, self.t = e, Engine.philox_key(seed), P, R, Dx, 0
+
+    def prior_uniforms(self):
+        """(P, R, Dx) uniforms in [0, 1), on the device."""
+        return self.e.philox_fill('uniform', self.key, STREAM_PRIOR, 0, 1, self.P, self.R, self.Dx)[0]
+
+    def stage(self, rounds):
+        """(z (rounds, P, R, Dx), log u (rounds, P, R, Dx)) of the next stage, on the device."""
+        t, self.t = self.t, self.t + 1
+        c2, fill = stage_round(t), self.e.philox_fill
+        return (fill('normal', self.key, STREAM_NORMAL, c2, rounds, self.P, self.R, self.Dx),
+                fill('log_uniform', self.key, STREAM_LOGU, c2, rounds, self.P, self.R, self.Dx))
+
+
 def n_survivors(level_prob, R):
     """n_s = max(1, floor(level_prob R)): the rank of the score that becomes the next level."""
     return max(1, int(np.floor(float(level_prob) * int(R))))
@@ -69,11 +89,13 @@ class FailureProbability:
     reliability.STATUS (= Engine.BOXSUS): ok 0; nan 1 no particle had a finite value (prob NaN); max_stages 2 the ladder
     ended below the threshold; below_min 3 the running product fell under min_prob.  For the last two prob estimates
     P(score >= the last level), which bounds P_F from above, and x samples that level set.  n_stages; evaluations: the walk
-    evaluations of the stages, n_stages (n_moves + 1) -- the one of the prior particles comes on top.
+    evaluations of the stages, n_stages (n_moves + 1) -- the one of the prior particles comes on top.  rng: 'numpy' or 'device', where
+    the run's random numbers were made.
     The spread of prob over the draws is the emulator's uncertainty about P_F; cov() is the Monte-Carlo error of one draw's
     number."""
 
-    def __init__(self, prob, levels, cond_prob, accept_rate, step, x, score, status, n_stages, evaluations):
+    def __init__(self, prob, levels, cond_prob, accept_rate, step, x, score, status, n_stages, evaluations, rng='numpy'):
+        self.rng = rng
         self.prob, self.levels, self.cond_prob, self.accept_rate, self.step = prob, levels, cond_prob, accept_rate, step
         self.x, self.score, self.status, self.n_stages, self.evaluations = x, score, status, n_stages, evaluations
 
@@ -131,20 +153,24 @@ def check_arguments(threshold, K, output, n_particles, level_prob, n_moves, max_
 
 
 def failure_probability(e, P, K, Dx, values, threshold, bounds, output=0, below=False, n_particles=1024, level_prob=0.1,
-                        n_moves=4, max_stages=50, min_prob=1e-12, seed=None, step=1.0, prior=None, target_accept=0.44):
+                        n_moves=4, max_stages=50, min_prob=1e-12, seed=None, step=1.0, prior=None, target_accept=0.44,
+                        rng='numpy'):
     """The driver behind PathFunctions.failure_probability and GpPaths.failure_probability.  values(xt (P, R, Dx)) -> (P, R, K):
     the walk at per-path rows, values only.  A stage is dgpamd_boxsus_level, then n_moves + 1 walk evaluations with
     dgpamd_boxsus_move behind each: the start of the stage at the cloned particles, then n_moves decisions.  A draw's step
     lam is fixed within a stage and follows the stage's acceptance rate afterwards, on the device; the width itself is the
-    survivors' spread, which the level step refreshes.  Only the count of unfinished draws visits the host, once per stage."""
+    survivors' spread, which the level step refreshes.  Only the count of unfinished draws visits the host, once per stage.
+    rng='device': every random number is made on the device (DeviceSusStreams); the prior uniforms visit the host once, for
+    prior_draws."""
+    device_rng = check_rng(rng, 'failure_probability')
     lo, hi = optimize.check_bounds(bounds, Dx, 'failure_probability')
     Dx = len(lo)
     pv, pm = check_prior(prior, Dx)
     R, n_s, n_moves, max_stages, output = check_arguments(threshold, K, output, n_particles, level_prob, n_moves, max_stages,
                                                            min_prob, step, target_accept)
     sign = -1.0 if below else 1.0
-    streams = SusStreams(seed, P, R, Dx)
-    x0 = np.ascontiguousarray(prior_draws(streams.prior_uniforms(), lo, hi, pv, pm))
+    streams = DeviceSusStreams(e, seed, P, R, Dx) if device_rng else SusStreams(seed, P, R, Dx)
+    x0 = np.ascontiguousarray(prior_draws(host_uniforms(streams.prior_uniforms()), lo, hi, pv, pm))
     xt = e.tensor(x0)
     state = e.boxsus_state(P, R, Dx, lo, hi, pv, pm, step)
     state['sd'].copy_(e.tensor(prior_spread(x0)))
@@ -153,7 +179,7 @@ def failure_probability(e, P, K, Dx, values, threshold, bounds, output=0, below=
     e.boxsus_move(state, values(xt), xt, zero, zero, threshold, output, sign, first=True, last=True)
     active, levels, nsurv, accept, lams = [], [], [], [], []
     for stage in range(max_stages):
-        zb, ub = map(e.tensor, streams.stage(n_moves + 1))
+        zb, ub = (upload(e, a) for a in streams.stage(n_moves + 1))
         active.append(state['done'] == 0)
         e.boxsus_level(state, xt, n_s, min_prob)
         levels.append(state['level'].clone()), nsurv.append(state['nsurv'].clone()), lams.append(state['lam'].clone())
@@ -173,4 +199,4 @@ def failure_probability(e, P, K, Dx, values, threshold, bounds, output=0, below=
     stack = lambda ts: np.where(on, torch.stack(ts, 1).double().cpu().numpy(), np.nan)
     return FailureProbability(host['prob'], stack(levels), stack(nsurv) / R, stack(accept), stack(lams),
                               np.ascontiguousarray(host['x'].reshape(Dx, P, R).transpose(1, 2, 0)), host['score'].reshape(P, R),
-                              status, T, T * (n_moves + 1))
+                              status, T, T * (n_moves + 1), rng)

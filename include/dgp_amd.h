@@ -952,6 +952,33 @@ int dgpamd_boxsus_level(dgpamd_ctx *ctx, int64_t P, int64_t R, int D, int n_s, d
                         const double *x, double *prob, double *level, int32_t *nsurv, int32_t *done, int32_t *status, int32_t *anc,
                         double *x_trial, double *sd, int32_t *running);
 
+/* ---- counter-based random streams on the device: Philox4x64-10 (DESIGN I.23) ----
+ * dgpamd_philox_fill fills out, a contiguous (rounds, P, R, D) array of 8-byte entries, with the numbers of one stream.  The
+ * generator is Philox4x64-10 of Salmon et al. (2011), the function of numpy.random.Philox: multipliers 0xD2E7470EE14C6C93 and
+ * 0xCA5A826395121157, key increments 0x9E3779B97F4A7C15 and 0xBB67AE8584CAA73B, ten rounds, the key bumped before rounds
+ * 2 to 10.  The key (key0, key1) is the caller's; the drivers use numpy.random.SeedSequence(seed).generate_state(2, uint64).
+ * The counter contract: entry [i, p, r, e] is word e mod 4 of the block of the counter
+ *   c0 = 1 + e div 4,  c1 = (p << 32) | r,  c2 = c2_first + i,  c3 = stream,
+ * a pure function of (key, stream, c2, p, r, e): it does not depend on rounds, P, R, D or on how the rounds are split over
+ * calls.  With the 1 + it is the e-th output of numpy.random.Philox(counter=[0, c1, c2, c3], key=key).random_raw().
+ * Kinds, w the word:
+ *   DGPAMD_PHILOX_BITS         w itself (out is int64 / uint64);
+ *   DGPAMD_PHILOX_UNIFORM      (w >> 11) 2^-53 in [0, 1), numpy's mapping, bit for bit;
+ *   DGPAMD_PHILOX_LOG_UNIFORM  log of that uniform by the device library's log; a zero uniform gives -inf;
+ *   DGPAMD_PHILOX_NORMAL       Box and Muller on the pairs of words (0, 1) and (2, 3) of a block: u1 = ((w_a >> 11) + 1) 2^-53 in
+ *                              (0, 1], u2 = (w_b >> 11) 2^-53, rho = sqrt(-2 log u1); elements 4 j + 2 q and 4 j + 2 q + 1 are
+ *                              rho cos(2 pi u2) and rho sin(2 pi u2), by the device library's log and sincospi(2 u2).
+ * One lane per block of four elements; stores are guarded at a partial last block.  No workspace, no LDS, no atomics.
+ * DGPAMD_BAD_ARG, before anything is launched: an unknown kind; rounds, P or R < 1; D outside 1 .. DGPAMD_MAXD; P >= 2^31 or
+ * R >= 2^32; c2_first + rounds wrapping; rounds P R > 2^56; a null out. */
+#define DGPAMD_PHILOX_BITS 0
+#define DGPAMD_PHILOX_UNIFORM 1
+#define DGPAMD_PHILOX_LOG_UNIFORM 2
+#define DGPAMD_PHILOX_NORMAL 3
+#define DGPAMD_PHILOX_COUNT 4
+int dgpamd_philox_fill(dgpamd_ctx *ctx, int kind, uint64_t key0, uint64_t key1, uint64_t stream, uint64_t c2_first,
+                       int64_t rounds, int64_t P, int64_t R, int D, void *out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,13 @@ tools/gpu_calibrate_bench.py (n = 2000, d = 5, emulator(N=10), sample_size = 10:
   (2) paths.failure_probability at a threshold whose probability is about 1e-5 (found by the run itself: the pooled level that
       a first run reaches after five stages of 0.1) against plain Monte Carlo through paths(x) with the same number of
       evaluated rows: time, stages, cov(), the spread over 5 seeds, and the hits the plain estimate got.
-Usage: python tools/gpu_sus_bench.py [file that also receives the lines]"""
+  (3) with --rng ARMS (profiles/rng_bench.txt; DESIGN I.23) instead of (1) and (2): the end-to-end run of (2) and one
+      paths.calibrate_smc run at R = 1024 (y and obs_sd of tools/gpu_smc_bench.py) under every arm of the comma-separated
+      list, the arms alternating inside every seed, by device events around the whole call: 'none' calls without the rng
+      keyword (any tree), 'numpy' and 'device' pass it.  --tree DIR imports bench and dgp_amd from another checkout (the
+      parent commit with its own library, run as a process of its own between runs of this tree).  For 'device' also the
+      fill kernels of one stage by device events, and for the numpy arms the host's share as (2) reports it.
+Usage: python tools/gpu_sus_bench.py [file that also receives the lines] [--rng none,numpy,device] [--tree DIR]"""
 import os
 import sys
 import time
@@ -14,7 +20,20 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+
+
+def option(name):
+    """The value behind `name` on the command line, taken out of it; None without it."""
+    if name not in sys.argv:
+        return None
+    i = sys.argv.index(name)
+    value = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
+    return value
+
+
+ARMS, TREE = option('--rng'), option('--tree')
+sys.path.insert(0, os.path.abspath(TREE) if TREE else ROOT)
 LOG = open(sys.argv[1], 'w') if len(sys.argv) > 1 else None
 REPEATS, WARM, R2, SEEDS = 20, 3, 1024, 5
 
@@ -128,6 +147,63 @@ def runs(e, pf, bounds):
     say('the random numbers of a run, drawn on the host: %.1f ms, %.1f %% of it' % (t_rng, 100.0 * t_rng / np.median(ms)))
 
 
+def event_ms(e, f):
+    a, c = e.event(), e.event()
+    e.record(a)
+    out = f()
+    e.record(c)
+    e.sync()
+    return out, e.elapsed_ms(a, c)
+
+
+def spans(ms):
+    return '%.1f ms (%.1f .. %.1f)' % (np.median(ms), min(ms), max(ms))
+
+
+def rng_arms(e, pf, bounds, arms):
+    """(3) of the module's docstring."""
+    from dgp_amd import optimize
+    P, D = pf.N * pf.sample_size, bounds.shape[0]
+    kw = {arm: {} if arm == 'none' else dict(rng=arm) for arm in arms}
+    v = pf(np.random.default_rng(1).uniform(bounds[:, 0], bounds[:, 1], (4096, D)))[0]
+    beyond = float(v.max() + 10.0 * (v.max() - v.min()))
+    probe = pf.failure_probability(beyond, bounds, n_particles=R2, max_stages=5, seed=1)
+    t = beyond + float(np.median(probe.levels[:, -1]))
+    say('threshold %.6g; arms %s, alternating inside every seed, device events around the whole call' % (t, ', '.join(arms)))
+    ms, stages, means = {a: [] for a in arms}, {a: [] for a in arms}, {a: [] for a in arms}
+    for seed in [0] + list(range(SEEDS)):                                         # (the first pass is warm-up and dropped)
+        for arm in arms:
+            r, t_ms = event_ms(e, lambda: pf.failure_probability(t, bounds, n_particles=R2, seed=seed, **kw[arm]))
+            ms[arm].append(t_ms), stages[arm].append(r.n_stages), means[arm].append(r.summary()['mean'])
+    for arm in arms:
+        say('failure_probability, rng %s: %d paths x %d particles, %s over %d seeds; stages %s; mean of P^ per seed %s'
+            % (arm, P, R2, spans(ms[arm][1:]), SEEDS, stages[arm][1:], ' '.join('%.3g' % m for m in means[arm][1:])))
+    n_stages = int(np.median(stages[arms[0]][1:]))
+    from dgp_amd import reliability
+    if 'device' in arms:
+        streams = reliability.DeviceSusStreams(e, 0, P, R2, D)
+        fills = [event_ms(e, lambda: streams.stage(5))[1] for _ in range(WARM + REPEATS)][WARM:]
+        _, t_prior = timed(lambda: streams.prior_uniforms().cpu())
+        say('device streams: the two fills of one stage (5 rounds x %d x %d x %d normals and log-uniforms) %s; the prior uniforms, filled '
+            'and fetched, %.2f ms; the fills of a run of %d stages %.2f ms'
+            % (P, R2, D, '%.3f ms (%.3f .. %.3f)' % (np.median(fills), min(fills), max(fills)), t_prior, n_stages, n_stages * np.median(fills)))
+    host = reliability.SusStreams(0, P, R2, D)
+    _, t_rng = timed(lambda: [host.prior_uniforms()] + [host.stage(5) for _ in range(n_stages)])
+    say('numpy streams: the random numbers of a run of %d stages, drawn on the host, %.1f ms' % (n_stages, t_rng))
+    # one calibrate_smc run per arm at R = 1024, the observation of tools/gpu_smc_bench.py
+    fc = pf(optimize.candidates(bounds[:, 0], bounds[:, 1], 2048, 3))[0]
+    y, sd = float(pf(bounds.mean(1)[None])[0].mean()), 0.1 * float(np.median(fc.max(0) - fc.min(0)))
+    ms, stages = {a: [] for a in arms}, {a: [] for a in arms}
+    for rep in range(4):                                                          # (the first pass is warm-up and dropped)
+        for arm in arms:
+            r, t_ms = event_ms(e, lambda: pf.calibrate_smc(y, sd, bounds, n_particles=R2, seed=3, **kw[arm]))
+            ms[arm].append(t_ms), stages[arm].append(r.n_stages)
+    for arm in arms:
+        say('calibrate_smc, rng %s: %d paths x %d particles, y = %.4g, obs_sd = %.4g, %s over 3 runs; stages %s'
+            % (arm, P, R2, y, sd, spans(ms[arm][1:]), stages[arm][1:]))
+    say('not measured: hardware counters, other shapes, calibrate with mala or hmc, more than these %d seeds' % SEEDS)
+
+
 def main():
     import bench
     from dgp_amd import emulator
@@ -139,6 +215,8 @@ def main():
     pf = emu.sample_functions(sample_size=J, n_features=F)
     bounds = np.stack((X.min(0), X.max(0)), 1)
     say('n = %d, d = %d, %d paths, F = %d, box = the range of X' % (n, d, N * J, F))
+    if ARMS:
+        return rng_arms(e, pf, bounds, ARMS.split(','))
     kernels(e, pf, bounds)
     runs(e, pf, bounds)
     say('not measured: hardware counters, other D, P or level_prob, n_moves other than 4, a prior, and the spread of the estimate '
