@@ -29,8 +29,10 @@ __global__ __launch_bounds__(256) void cross_corr_kernel(CrossArgs a) {
     for (int idx = tid; idx < 64 * D; idx += 256) {
         int row = idx / D, d = idx - row * D;
         int64_t gi = i0 + row, gt = a.t0 + c0 + row;
-        WT[d * 64 + row] = (gi < a.n ? a.W[gi * D + d] : 0.0) * a.inv_len[d];
-        XT[d * 64 + row] = (gt < a.M ? a.x[gt * D + d] : 0.0) * a.inv_len[d];
+        // relative to the first training point: scaled raw coordinates lose eps |w| / l of every difference below
+        const double c = a.W[d];
+        WT[d * 64 + row] = (gi < a.n ? a.W[gi * D + d] - c : 0.0) * a.inv_len[d];
+        XT[d * 64 + row] = (gt < a.M ? a.x[gt * D + d] - c : 0.0) * a.inv_len[d];
     }
     __syncthreads();
     double s[4][4], pr[4][4];

@@ -183,7 +183,13 @@ __device__ __forceinline__ TilePlace tile_place(const LinkArgs &a, int tc) {
 }
 
 // WiT / WjT [d][64] <- the tile's 64 rows and 64 columns of [W | Wg] (zero past n).  GLOBALS = false: W alone.
-template <bool GLOBALS = true>
+// CENTRE: the local columns relative to the first training point, w_k - W[0][k].  The expanded SExp forms build their
+// exponent from products of the staged coordinates themselves (row term, column term, dot product: each of size c1 w^2,
+// cancelling to the exponent), so they lose eps (|w| / l)^2 where the forms that difference first lose eps |w| / l; with
+// the centre taken out |w| is at most the data's diameter.  W[0] needs no reduction and no launch, and it is the same in
+// every chunk and launch of a call; the forms take it from m likewise (where they form 2 m, and in sexp_records_kernel),
+// so that w - m and w_i - w_j stay what they were.  The global inputs enter as differences already.
+template <bool GLOBALS = true, bool CENTRE = false>
 __device__ __forceinline__ void stage_tile_inputs(const LinkArgs &a, const TilePlace &p, double *WiT, double *WjT) {
     const int Dw = a.Dw, Dz = a.Dz, DT = GLOBALS ? Dw + Dz : Dw;
     const int64_t n = a.n;
@@ -192,8 +198,9 @@ __device__ __forceinline__ void stage_tile_inputs(const LinkArgs &a, const TileP
         int64_t gi = p.i0 + row, gj = p.j0 + row;
         double vi = 0.0, vj = 0.0;
         if (!GLOBALS || d < Dw) {
-            if (gi < n) vi = a.W[gi * Dw + d];
-            if (gj < n) vj = a.W[gj * Dw + d];
+            const double c = CENTRE ? a.W[d] : 0.0;
+            if (gi < n) vi = CENTRE ? a.W[gi * Dw + d] - c : a.W[gi * Dw + d];
+            if (gj < n) vj = CENTRE ? a.W[gj * Dw + d] - c : a.W[gj * Dw + d];
         } else {
             if (gi < n) vi = a.Wg[gi * Dz + d - Dw];
             if (gj < n) vj = a.Wg[gj * Dz + d - Dw];

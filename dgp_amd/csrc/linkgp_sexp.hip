@@ -10,6 +10,9 @@
 // test point the 64 x 64 x Dw products of a tile are a handful of v_mfma_f64_16x16x4 (accumulated on top of base_ij,
 // which sits in the accumulator layout), and the VALU work per pair drops from 3 Dw + exp to 2 adds + exp.  The row /
 // column terms and the A operand of test point t+1 are staged (double buffered in LDS) while t is evaluated.
+// The three terms cancel to the exponent, so w and m are taken relative to W[0] where they are staged (stage_tile_inputs,
+// CENTRE; m where 2 m is formed below) -- the exponent depends on w_i + w_j - 2 m alone -- which keeps each term at the size of
+// (the data's diameter / l)^2 wherever the inputs lie.
 __global__ __launch_bounds__(256, 3) void linkgp_Jsexp_kernel(LinkArgs a) {
     extern __shared__ double lds[];
     const int Dw = a.Dw, Dz = a.Dz;
@@ -21,7 +24,7 @@ __global__ __launch_bounds__(256, 3) void linkgp_Jsexp_kernel(LinkArgs a) {
     const int bi = pl.bi, bj = pl.bj, nt = pl.nt;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
 
-    stage_tile_inputs(a, pl, WiT, WjT);
+    stage_tile_inputs<true, true>(a, pl, WiT, WjT);   // (w relative to W[0]: linkgp.hpp; m below)
     stage_test_points(a, pl, tm, tv, tz);
     for (int g = tid; g < Dz; g += 256) ilg[g] = 1.0 / a.len[Dw + g];
     __syncthreads();
@@ -41,7 +44,7 @@ __global__ __launch_bounds__(256, 3) void linkgp_Jsexp_kernel(LinkArgs a) {
     for (int idx = tid; idx < nt * Dw; idx += 256) {
         const double l = a.len[idx % Dw];
         tv[idx] = 1.0 / (8.0 * tv[idx] + 2.0 * l * l);
-        tm[idx] = 2.0 * tm[idx];
+        tm[idx] = 2.0 * (tm[idx] - a.W[idx % Dw]);   // (relative to W[0], as the staged w)
     }
     // staging of test point t: 128 point tasks (64 row points: A operand + row term; 64 column points: column term)
     // on the even threads, so that the four waves share them evenly
@@ -127,8 +130,9 @@ __global__ __launch_bounds__(256) void sexp_records_kernel(LinkArgs a, int KPA) 
     double rr = 0.0, ss = 0.0;
     if (i < a.n) {
         for (int k = 0; k < a.Dw; ++k) {
-            const double l = a.len[k], c1 = 1.0 / (8.0 * a.v[t * a.Dw + k] + 2.0 * l * l), w = a.W[i * a.Dw + k];
-            const double d = w - 2.0 * a.m[t * a.Dw + k], cw = c1 * d;
+            // (w and m relative to W[0], as the pair kernel stages its B operand: linkgp.hpp, stage_tile_inputs)
+            const double l = a.len[k], c1 = 1.0 / (8.0 * a.v[t * a.Dw + k] + 2.0 * l * l), c = a.W[k], w = a.W[i * a.Dw + k] - c;
+            const double d = w - 2.0 * (a.m[t * a.Dw + k] - c), cw = c1 * d;
             ra[k] = 2.0 * cw;
             rr = fma(cw, d, rr);
             ss = fma(c1 * w, w, ss);
@@ -165,7 +169,7 @@ __global__ __launch_bounds__(256, 2) void linkgp_Jsexp2_kernel(LinkArgs a) {
     for (int j = tid; j < EXPN_TAB; j += 256) etab[j] = exp2((double)j * (1.0 / EXPN_TAB));
     const int64_t i0 = pl.i0, j0 = pl.j0, n = a.n;
     const int64_t tt0 = (int64_t)blockIdx.y * tch2;
-    stage_tile_inputs<false>(a, pl, WiT, WjT);   // (the global inputs' terms come in the records)
+    stage_tile_inputs<false, true>(a, pl, WiT, WjT);   // (the global inputs' terms come in the records; w relative to W[0] as in the records)
     __syncthreads();
     const int mrow = 16 * wave + (lane >> 4), mcol = lane & 15, kq = lane >> 4, mi = lane & 15;
     const int kqS = (Dw + 1) & 3;   // (the ss row: k = Dw + 1, in k-step (Dw + 1) >> 2 == KS - 1)

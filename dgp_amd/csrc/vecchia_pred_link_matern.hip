@@ -12,7 +12,8 @@
 // multiply-adds) and selects by the coordinates -- the same multiply-adds in the same order as the LDS kernel's pair loop
 // (vecchia_linkgp_kernel, csrc/vecchia_gp.hip), so J holds the same bits.  Only the dimension loop is a run-time loop (the
 // coordinate of the dimension is re-read from memory: a run-time index into a register array would put it in scratch); K is
-// built from scaled coordinates held in registers, then the elimination of the squared-exponential kernel takes over.
+// built from the coordinates held in registers relative to the test point and scaled, (w - m) / l and (wg - z) / l (only their
+// differences enter K, and scaling the raw coordinates first would lose eps |w| / l of each), then the elimination of the squared-exponential kernel takes over.
 // The LDS kernel spent 68 ms per 100 000 points (pm = 50, Dw = Dz = 8) on dependent LDS round trips in its two
 // column-parallel substitutions and its pair loops.
 template <int DGM>
@@ -34,16 +35,16 @@ __global__ __launch_bounds__(256) void vecchia_linkgp_matern_reg_kernel(VLinkArg
         for (int g = 0; g < DGM; ++g) {
             ug[g] = 0.0;
             if (g < Dz) {
-                const double x = a.wg[row * Dz + g];
-                corr_accum_matern((x - a.z[t * Dz + g]) / a.len[Dw + g], pr, sg);
-                ug[g] = act ? x / a.len[Dw + g] : 0.0;
+                const double u = (a.wg[row * Dz + g] - a.z[t * Dz + g]) / a.len[Dw + g];
+                corr_accum_matern(u, pr, sg);
+                ug[g] = act ? u : 0.0;   // (relative to the test point, as the SExp kernel holds them: K's differences are unchanged)
             }
         }
         if (DGM > 0) Iz = pr * exp(-SQRT5 * sg);
     }
     double uw[DLM];
 #pragma unroll
-    for (int k = 0; k < DLM; ++k) uw[k] = (k < Dw && act) ? a.w1[row * Dw + k] / a.len[k] : 0.0;
+    for (int k = 0; k < DLM; ++k) uw[k] = (k < Dw && act) ? (a.w1[row * Dw + k] - a.m[t * Dw + k]) / a.len[k] : 0.0;   // (w / l alone loses eps |w| / l of every difference)
     double jm[VL_BC];
     static_for<0, VL_BC>([&](auto ic) {
         constexpr int c = decltype(ic)::value;
