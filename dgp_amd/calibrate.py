@@ -25,6 +25,9 @@ import torch
 
 from . import optimize, pathfun
 from .ops import Engine
+# (the plumbing shared with reliability.py; its names stay importable from here)
+from .population import (RNGS, STREAM_LOGU, STREAM_NORMAL, STREAM_PRIOR, STREAM_RESAMPLE, DeviceStageStreams, HostStreams, check_prior,
+                         check_rng, draw_status, host_uniforms, particles, prior_draws, prior_particles, run_stages, stage_round, upload)
 
 STATUS = Engine.BOXMALA
 HMIN, HMAX = 1e-10, 1e2       # the clamp of a chain's step, in units of `scale`
@@ -65,24 +68,22 @@ def observation(y, obs_sd, K):
     return ybar, T / (np.broadcast_to(sd, (K,)) * np.broadcast_to(sd, (K,)))
 
 
-def check_prior(prior, Dx):
-    """(precision (Dx,), mean (Dx,)) of prior = None or (mean (Dx,), sd (Dx,)); an infinite sd is a flat column."""
-    if prior is None:
-        return np.zeros(Dx), np.zeros(Dx)
-    try:
-        mean, sd = (np.asarray(a, dtype=np.float64) for a in prior)
-    except (TypeError, ValueError):
-        raise ValueError('calibrate: prior must be None or (mean (Dx,), sd (Dx,))') from None
-    if mean.shape != (Dx,) or sd.shape != (Dx,) or not np.all(np.isfinite(mean)) or np.any(np.isnan(sd)) or not np.all(sd > 0.0):
-        raise ValueError('calibrate: prior must be (mean, sd), (%d,) each, mean finite and sd > 0 (inf: flat)' % Dx)
-    return 1.0 / (sd * sd), mean
-
-
 def check_counts(n_chains, n_samples, warmup, thin):
     n_chains, n_samples, warmup, thin = int(n_chains), int(n_samples), int(warmup), int(thin)
     if n_chains < 1 or n_samples < 1 or thin < 1 or warmup < 0:
         raise ValueError('calibrate: need n_chains >= 1, n_samples >= 1, thin >= 1 and warmup >= 0')
     return n_chains, n_samples, warmup, thin
+
+
+def check_step(what, lo, hi, scale, step, target_accept):
+    """scale (Dx,), hi - lo for None, after the refusals that the chains and the SMC moves share."""
+    Dx = len(lo)
+    scale = hi - lo if scale is None else np.asarray(scale, dtype=np.float64)
+    if scale.shape != (Dx,) or not np.all(np.isfinite(scale)) or np.any(scale < 0.0):
+        raise ValueError('%s: scale must be (%d,) finite numbers >= 0' % (what, Dx))
+    if not (np.isfinite(step) and HMIN <= step <= HMAX) or not 0.0 < target_accept < 1.0:
+        raise ValueError('%s: need %g <= step <= %g and 0 < target_accept < 1' % (what, HMIN, HMAX))
+    return scale
 
 
 def trajectory_lengths(seed, iterations, n_leapfrog, jitter):
@@ -115,26 +116,6 @@ class Streams:
 
 
 # ------------------------------------------------------------------------- random streams made on the device (DESIGN I.23)
-RNGS = ('numpy', 'device')
-STREAM_PRIOR, STREAM_NORMAL, STREAM_LOGU, STREAM_RESAMPLE = 0, 1, 2, 3      # c3 of dgpamd_philox_fill's counter
-
-
-def check_rng(rng, what):
-    if rng not in RNGS:
-        raise ValueError("%s: rng must be 'numpy' or 'device'" % what)
-    return rng == 'device'
-
-
-def stage_round(t, i=0):
-    """The round c2 of move i of stage t in calibrate_smc and failure_probability: (t << 32) | i."""
-    return (int(t) << 32) | int(i)
-
-
-def upload(e, a):
-    """e.tensor for what a numpy stream returns; what a device stream returns is on the device already."""
-    return a if torch.is_tensor(a) else e.tensor(a)
-
-
 class DeviceStreams:
     """Streams' twin for rng='device': the same method, device tensors, the numbers Philox4x64-10 under the key
     SeedSequence(seed).generate_state(2, uint64) (Engine.philox_fill).  z is stream 1 with Dx elements per slot, log u stream 2
@@ -273,11 +254,7 @@ def calibrate(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, n_ch
     ybar, w = observation(y, obs_sd, K)
     pv, pm = check_prior(prior, Dx)
     R, S, warmup, thin = check_counts(n_chains, n_samples, warmup, thin)
-    scale = hi - lo if scale is None else np.asarray(scale, dtype=np.float64)
-    if scale.shape != (Dx,) or not np.all(np.isfinite(scale)) or np.any(scale < 0.0):
-        raise ValueError('calibrate: scale must be (%d,) finite numbers >= 0' % Dx)
-    if not (np.isfinite(step) and HMIN <= step <= HMAX) or not 0.0 < target_accept < 1.0:
-        raise ValueError('calibrate: need %g <= step <= %g and 0 < target_accept < 1' % (HMIN, HMAX))
+    scale = check_step('calibrate', lo, hi, scale, step, target_accept)
     seen = torch.as_tensor(np.nonzero(w > 0.0)[0], device=e.device)
     wd, yd, pvd, pmd = e.tensor(w[w > 0.0]), e.tensor(ybar[w > 0.0]), e.tensor(pv), e.tensor(pm)
 
@@ -355,18 +332,6 @@ def log_norm(y, obs_sd, K):
     return float(-0.5 * np.sum(T * np.log(2.0 * np.pi * sd2)) - 0.5 * np.sum(within / sd2))
 
 
-def prior_draws(u, lo, hi, pv, pm):
-    """x (..., Dx) in the box with the prior's distribution from uniforms u (..., Dx) in [0, 1), by the inverse cdf: a flat
-    column (pv_d = 0) is lo + u (hi - lo); another one is N(pm_d, 1 / pv_d) truncated to [lo_d, hi_d]; lo_d = hi_d keeps it."""
-    from scipy.special import ndtr, ndtri
-    x = lo + u * (hi - lo)
-    for d in np.nonzero((pv > 0.0) & (hi > lo))[0]:
-        sd = 1.0 / np.sqrt(pv[d])
-        a, b = ndtr((lo[d] - pm[d]) / sd), ndtr((hi[d] - pm[d]) / sd)
-        x[..., d] = pm[d] + sd * ndtri(a + u[..., d] * (b - a))
-    return np.minimum(np.maximum(x, lo), hi)
-
-
 def stage_gain(stage, rate, target_accept):
     """The factor on a draw's step after stage `stage` whose moves were accepted at `rate`: exp(rate - target_accept).  The
     step is held fixed within a stage and is one number per draw, set from the acceptance of all the draw's particles: every
@@ -377,18 +342,11 @@ def stage_gain(stage, rate, target_accept):
     return float(np.exp(rate - target_accept))
 
 
-class SmcStreams:
+class SmcStreams(HostStreams):
     """The random numbers of an SMC run, children of np.random.SeedSequence(seed) by spawn key: (0, r) the prior uniforms of
     particle slot r, (P, Dx); (1, r, t) and (2, r, t) the normal and the uniform draws of slot r in stage t, (P, rounds, Dx)
     and (P, rounds), path first; (3, t) the resampling uniforms of stage t, (P,).  A generator is read path by path, so
     path p's numbers do not depend on P, nor a slot's on R."""
-
-    def __init__(self, seed, P, R, Dx):
-        self.entropy = np.random.SeedSequence(seed).entropy
-        self.P, self.R, self.Dx, self.t = P, R, Dx, 0
-
-    def _rng(self, *key):
-        return np.random.default_rng(np.random.SeedSequence(self.entropy, spawn_key=key))
 
     def prior_uniforms(self):
         """(P, R, Dx) uniforms in [0, 1)."""
@@ -403,31 +361,12 @@ class SmcStreams:
         return self._rng(3, t).random(self.P), np.ascontiguousarray(z.transpose(2, 0, 1, 3)), np.ascontiguousarray(logu.transpose(2, 0, 1))
 
 
-class DeviceSmcStreams:
-    """SmcStreams' twin for rng='device' (Engine.philox_fill under the key of the seed): the prior uniforms are stream 0 at
-    round 0; stage t reads its resampling uniform from stream 3 at (c2 = t << 32, r = 0), z from stream 1 (Dx elements) and
-    log u from stream 2 (one element) at c2 = (t << 32) | i for move i.  Particle (p, r)'s numbers depend on nothing but the
-    seed, p, r, t and i."""
+class DeviceSmcStreams(DeviceStageStreams):
+    """SmcStreams' twin for rng='device': population.DeviceStageStreams with one log u per particle and round and the
+    resampling uniform; stage(rounds) gives (u (P,), z (rounds, P, R, Dx), log u (rounds, P, R))."""
 
     def __init__(self, e, seed, P, R, Dx):
-        self.e, self.key, self.P, self.R, self.Dx, self.t = e, Engine.philox_key(seed), P, R, Dx, 0
-
-    def prior_uniforms(self):
-        """(P, R, Dx) uniforms in [0, 1), on the device."""
-        return self.e.philox_fill('uniform', self.key, STREAM_PRIOR, 0, 1, self.P, self.R, self.Dx)[0]
-
-    def stage(self, rounds):
-        """(u (P,), z (rounds, P, R, Dx), log u (rounds, P, R)) of the next stage, on the device."""
-        t, self.t = self.t, self.t + 1
-        c2, fill = stage_round(t), self.e.philox_fill
-        return (fill('uniform', self.key, STREAM_RESAMPLE, c2, 1, self.P, 1, 1).view(self.P),
-                fill('normal', self.key, STREAM_NORMAL, c2, rounds, self.P, self.R, self.Dx),
-                fill('log_uniform', self.key, STREAM_LOGU, c2, rounds, self.P, self.R, 1).view(rounds, self.P, self.R))
-
-
-def host_uniforms(u):
-    """The prior uniforms on the host: a device stream's visit it once, for prior_draws."""
-    return u.cpu().numpy() if torch.is_tensor(u) else u
+        super().__init__(e, seed, P, R, Dx, logu_elements=1, resample=True)
 
 
 def _weighted_quantile(v, wt, q):
@@ -524,10 +463,10 @@ class ParticlePosterior:
 def calibrate_smc(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, n_particles=1024, n_moves=4, ess_frac=0.5,
                   max_stages=100, seed=None, step=0.1, scale=None, prior=None, target_accept=0.574, rng='numpy'):
     """The driver behind PathFunctions.calibrate_smc and GpPaths.calibrate_smc: adaptive likelihood tempering (Del Moral,
-    Doucet and Jasra 2006).  A stage is dgpamd_boxsmc_temper, then n_moves + 1 walk evaluations with dgpamd_boxsmc_move
-    behind each: the start of the stage at the resampled particles, then n_moves decisions.  Only the count of draws below
-    beta = 1 visits the host, once per stage.  rng='device': every random number is made on the device (DeviceSmcStreams);
-    the prior uniforms visit the host once, for prior_draws."""
+    Doucet and Jasra 2006) on population.run_stages.  A stage is dgpamd_boxsmc_temper, then n_moves + 1 walk evaluations with
+    dgpamd_boxsmc_move behind each: the start of the stage at the resampled particles, then n_moves decisions.  Only the count
+    of draws below beta = 1 visits the host, once per stage.  rng='device': every random number is made on the device
+    (DeviceSmcStreams); the prior uniforms visit the host once, for prior_draws."""
     device_rng = check_rng(rng, 'calibrate_smc')
     lo, hi = optimize.check_bounds(bounds, Dx, 'calibrate_smc')
     Dx = len(lo)
@@ -540,38 +479,26 @@ def calibrate_smc(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, 
         raise ValueError('calibrate_smc: need n_moves >= 1 and max_stages >= 1')
     if not 0.0 < ess_frac < 1.0:
         raise ValueError('calibrate_smc: ess_frac must lie in (0, 1)')
-    scale = hi - lo if scale is None else np.asarray(scale, dtype=np.float64)
-    if scale.shape != (Dx,) or not np.all(np.isfinite(scale)) or np.any(scale < 0.0):
-        raise ValueError('calibrate_smc: scale must be (%d,) finite numbers >= 0' % Dx)
-    if not (np.isfinite(step) and HMIN <= step <= HMAX) or not 0.0 < target_accept < 1.0:
-        raise ValueError('calibrate_smc: need %g <= step <= %g and 0 < target_accept < 1' % (HMIN, HMAX))
+    scale = check_step('calibrate_smc', lo, hi, scale, step, target_accept)
     streams = DeviceSmcStreams(e, seed, P, R, Dx) if device_rng else SmcStreams(seed, P, R, Dx)
-    xt = e.tensor(np.ascontiguousarray(prior_draws(host_uniforms(streams.prior_uniforms()), lo, hi, pv, pm)))
+    xt = e.tensor(prior_particles(streams, lo, hi, pv, pm))
     state = e.boxsmc_state(P, R, Dx, w, ybar, lo, hi, scale, pv, pm, h0=step)
-    # the likelihood of the prior particles: a stage's start under beta = 0 that ends at once (z and log u are not read)
-    f, J = value_and_jac(xt)
-    e.boxsmc_move(state, f, J, xt, e.zeros(P, R, Dx), e.zeros(P, R), HMIN, HMAX, first=True, last=True)
-    betas, stage_ess, accept = [], [], []
-    for stage in range(max_stages):
-        u, zb, ub = (upload(e, a) for a in streams.stage(n_moves + 1))
+    betas, stage_ess = [], []
+
+    move = lambda z, logu, first, last: e.boxsmc_move(state, *value_and_jac(xt), xt, z, logu, HMIN, HMAX, first=first, last=last)
+
+    def temper(u):
         e.boxsmc_temper(state, xt, u, ess_frac)
-        betas.append(state['beta'].clone())
-        stage_ess.append(state['stage_ess'].clone())
-        for i in range(n_moves + 1):
-            f, J = value_and_jac(xt)
-            e.boxsmc_move(state, f, J, xt, zb[i], ub[i], HMIN, HMAX, first=i == 0, last=i == n_moves)
-        # the draw's step for the next stage, from this stage's acceptance over all its particles (see stage_gain)
-        rate = state['n_acc'].view(P, R).sum(1).double() / state['n_prop'].view(P, R).sum(1).clamp(min=1).double()
-        accept.append(rate)
-        state['h'].view(P, R).mul_(torch.exp(rate - target_accept)[:, None]).clamp_(HMIN, HMAX)
-        if int(state['running'].item()) == 0:
-            break
+        betas.append(state['beta'].clone()), stage_ess.append(state['stage_ess'].clone())
+    # the likelihood of the prior particles: a stage's start under beta = 0 that ends at once (z and log u are not read)
+    move(e.zeros(P, R, Dx), e.zeros(P, R), first=True, last=True)
+    # the draw's step for the next stage follows this stage's acceptance over all its particles (see stage_gain)
+    accept = run_stages(e, streams, state, n_moves, max_stages, target_accept, temper, move,
+                        lambda gain: state['h'].view(P, R).mul_(gain[:, None]).clamp_(HMIN, HMAX))
     host = {k: state[k].cpu().numpy() for k in ('x', 'll', 'lprior', 'h', 'beta', 'log_evidence', 'draw_status')}
-    status = host['draw_status'].copy()
-    status[(status == SMC_STATUS['ok']) & (host['beta'] < 1.0)] = SMC_STATUS['max_stages']
     T = len(betas)
     stack = lambda ts: np.ascontiguousarray(torch.stack(ts, 1).cpu().numpy())
     ll = host['ll'].reshape(P, R)
-    return ParticlePosterior(np.ascontiguousarray(host['x'].reshape(Dx, P, R).transpose(1, 2, 0)), ll,
-                             ll + host['lprior'].reshape(P, R), host['log_evidence'], log_norm(y, obs_sd, K), stack(betas),
-                             stack(stage_ess), stack(accept), host['h'].reshape(P, R), status, T, T * (n_moves + 1), rng)
+    return ParticlePosterior(particles(host['x'], P, R), ll, ll + host['lprior'].reshape(P, R), host['log_evidence'],
+                             log_norm(y, obs_sd, K), stack(betas), stack(stage_ess), stack(accept), host['h'].reshape(P, R),
+                             draw_status(SMC_STATUS, host['draw_status'], host['beta'] < 1.0), T, T * (n_moves + 1), rng)

@@ -10,11 +10,11 @@
 // and write consecutive doubles.  The loops over D and K run over global memory -- a per-lane array with a runtime index
 // would live in scratch.  No LDS, no cross-lane operation, no atomics: a chain's iterates are one fixed sequence of operations
 // on its own inputs, whatever shares its wave.
-// Both files are compiled with -ffp-contract=off (csrc/Makefile): every product is rounded before it enters a sum, every sum
-// runs in index order, and the kernels use + - * / and comparisons alone, so they perform the operations of their numpy
-// restatements (tests/boxmala_ref.py, whose target tests/boxhmc_ref.py inherits) one for one.  The operand order and the
-// parentheses of every expression here are those roundings: they do not move.  Everything on the device is forced inline, as
-// in wave.hpp: a kernel compiles to what it did with a copy of its own.
+// All three files are compiled with -ffp-contract=off (csrc/Makefile): every product is rounded before it enters a sum, every
+// sum runs in index order, and the kernels use + - * / and comparisons alone, so they perform the operations of their numpy
+// restatements (tests/boxmala_ref.py, whose target tests/boxhmc_ref.py inherits and tests/boxsmc_ref.py tempers) one for one.
+// The operand order and the parentheses of every expression here are those roundings: they do not move.  Everything on the
+// device is forced inline, as in wave.hpp: a kernel compiles to what it did with a copy of its own.
 #pragma once
 #include <math.h>
 
@@ -54,17 +54,21 @@ static size_t boxchain_workspace(int64_t Q, int D) {
     return (size_t)Q * (8 * ((size_t)NV * D + NS) + 4);
 }
 
-template <int NV, int NS>
-__device__ __forceinline__ BoxchainLane boxchain_lane(const BoxchainArgs &a, int64_t q) {
+// The part of a lane that the call's arguments fix: par and the chain's rows of f, J and x_trial
+__device__ __forceinline__ BoxchainLane boxchain_lane_par(const BoxchainArgs &a, int64_t q) {
     BoxchainLane c;
-    const int64_t Q = a.Q;
     const int D = a.D, K = a.K;
-    c.q = q, c.Q = Q, c.D = D, c.K = K;
+    c.q = q, c.Q = a.Q, c.D = D, c.K = K;
     c.w = a.par, c.yb = c.w + K, c.pv = c.yb + K, c.pm = c.pv + D, c.sc = c.pm + D, c.lo = c.sc + D, c.hi = c.lo + D;
-    c.X = a.ws + q, c.G = c.X + (int64_t)D * Q, c.GT = c.G + (int64_t)D * Q, c.LP = c.GT + (int64_t)(NV - 2) * D * Q;
-    c.FLAG = (int32_t *)(a.ws + ((int64_t)NV * D + NS) * Q) + q;
     c.xt = a.x_trial + q * D;
     c.fq = a.f + q * K, c.Jq = a.J + q * K * D;
+    return c;
+}
+template <int NV, int NS>
+__device__ __forceinline__ BoxchainLane boxchain_lane(const BoxchainArgs &a, int64_t q) {
+    BoxchainLane c = boxchain_lane_par(a, q);
+    c.X = a.ws + q, c.G = c.X + (int64_t)a.D * a.Q, c.GT = c.G + (int64_t)a.D * a.Q, c.LP = c.GT + (int64_t)(NV - 2) * a.D * a.Q;
+    c.FLAG = (int32_t *)(a.ws + ((int64_t)NV * a.D + NS) * a.Q) + q;
     return c;
 }
 // the kernel's own fields: vector i >= 3, scalar i >= 1
@@ -75,8 +79,10 @@ __device__ __forceinline__ double *boxchain_scalar(const BoxchainLane &c, int i)
 __device__ __forceinline__ bool boxchain_fixed(const BoxchainLane &c, int d) { return c.sc[d] == 0.0 || c.lo[d] == c.hi[d]; }
 
 // TARGET: lp' and, into the workspace, g' at the trial point; false if either is not finite.  An output with w_k = 0 and a
-// column with pv_d = 0 are not read.
-__device__ __forceinline__ bool boxchain_target(const BoxchainLane &c, double &lpt) {
+// column with pv_d = 0 are not read.  TEMPERED (boxsmc.hip, under prior(x) exp(beta ll(x))): ll' and lprior' come apart and
+// g'_d = beta c_d - pv_d e_d, the likelihood's part times beta before the prior's.  Compile time: the chains gain no multiply.
+template <bool TEMPERED>
+__device__ __forceinline__ bool boxchain_target(const BoxchainLane &c, double beta, double &llt, double &lprt) {
     const int64_t Q = c.Q;
     const int D = c.D, K = c.K;
     double sa = 0.0, sb = 0.0;
@@ -94,20 +100,25 @@ __device__ __forceinline__ bool boxchain_target(const BoxchainLane &c, double &l
             sb = sb + (p * e) * e;
         }
     }
-    lpt = -0.5 * sa - 0.5 * sb;
-    bool finite = isfinite(lpt);
+    llt = TEMPERED ? -0.5 * sa : -0.5 * sa - 0.5 * sb;            // (untempered: lp', and lprt is not written)
+    if (TEMPERED) lprt = -0.5 * sb;
+    bool finite = isfinite(llt) && (!TEMPERED || isfinite(lprt));
     for (int d = 0; d < D; ++d) {
         double g = 0.0;
         for (int k = 0; k < K; ++k) {
             const double wk = c.w[k];
             if (wk > 0.0) g = g + (wk * (c.yb[k] - c.fq[k])) * c.Jq[k * D + d];
         }
+        if (TEMPERED) g = beta * g;
         const double p = c.pv[d];
         if (p > 0.0) g = g - p * (c.xt[d] - c.pm[d]);
         c.GT[d * Q] = g;
         finite = finite && isfinite(g);
     }
     return finite;
+}
+__device__ __forceinline__ bool boxchain_target(const BoxchainLane &c, double &lpt) {
+    return boxchain_target<false>(c, 1.0, lpt, lpt);
 }
 
 // (x, g, lp) <- the trial's
@@ -146,6 +157,36 @@ __device__ __forceinline__ void boxchain_store(const BoxchainArgs &a, const Boxc
 // x_trial <- x: the walk evaluates a point of the box whose values are finite
 __device__ __forceinline__ void boxchain_hold(const BoxchainLane &c) {
     for (int d = 0; d < c.D; ++d) c.xt[d] = c.X[d * c.Q];
+}
+
+// MALA's 0.5 qf - 0.5 qb of DECIDE: the trial was proposed from x with the step hq, and x would be from the trial with it
+__device__ __forceinline__ double boxchain_mala_ratio(const BoxchainLane &c, double hq) {
+    double qf = 0.0, qb = 0.0;
+    for (int d = 0; d < c.D; ++d) {
+        const double sd = c.sc[d];
+        if (boxchain_fixed(c, d)) continue;
+        const double e = (0.5 * (hq * hq)) * (sd * sd), hs = hq * sd, x = c.X[d * c.Q], t = c.xt[d];
+        const double u = ((t - x) - e * c.G[d * c.Q]) / hs, v = ((x - t) - e * c.GT[d * c.Q]) / hs;
+        qf = qf + u * u;
+        qb = qb + v * v;
+    }
+    return 0.5 * qf - 0.5 * qb;
+}
+
+// MALA's PROPOSE: the next trial from x, g, the step and the call's normal draws; outside the box: flag up, the walk evaluates x
+__device__ __forceinline__ void boxchain_mala_propose(const BoxchainArgs &a, const BoxchainLane &c) {
+    const double hq = a.h[c.q];
+    const double *zq = a.z + c.q * c.D;
+    int flag = 0;
+    for (int d = 0; d < c.D; ++d) {
+        const double sd = c.sc[d], l = c.lo[d], u = c.hi[d], x = c.X[d * c.Q];
+        double xp = x;
+        if (!boxchain_fixed(c, d)) xp = (x + ((0.5 * (hq * hq)) * (sd * sd)) * c.G[d * c.Q]) + (hq * sd) * zq[d];
+        if (!(xp >= l && xp <= u)) flag = 1;          // (a NaN is outside)
+        c.xt[d] = xp;
+    }
+    if (flag) boxchain_hold(c);
+    *c.FLAG = flag;
 }
 
 static bool positive_finite(double v) { return v > 0.0 && v <= 1.79769313486231570815e308; }

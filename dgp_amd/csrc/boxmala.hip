@@ -3,23 +3,9 @@
 // A call takes the walk's values (Q, K) and Jacobian (Q, K, D) at the trial points, decides every chain's pending proposal,
 // adapts its step, stores a sample and writes the next trial points from the caller's normal draws z.  Nothing goes to the host.
 // The target, the layout of par and of the workspace, the steps this kernel shares with boxhmc.hip and the roundings that
-// hold it to its numpy restatement (tests/boxmala_ref.py) are boxchain.hpp's.  Its own: the log ratio of the two proposal
-// densities, and PROPOSE.
+// hold it to its numpy restatement (tests/boxmala_ref.py) are boxchain.hpp's, and so are the log ratio of the two proposal
+// densities and PROPOSE, which boxsmc.hip's move shares.  Its own: the order of a call -- DECIDE, STORE, PROPOSE.
 #include "boxchain.hpp"
-
-// 0.5 qf - 0.5 qb of DECIDE: the trial was proposed from x with the step hq, and x would be proposed from the trial with it
-__device__ __forceinline__ double boxmala_proposal_ratio(const BoxchainLane &c, double hq) {
-    double qf = 0.0, qb = 0.0;
-    for (int d = 0; d < c.D; ++d) {
-        const double sd = c.sc[d];
-        if (boxchain_fixed(c, d)) continue;
-        const double e = (0.5 * (hq * hq)) * (sd * sd), hs = hq * sd, x = c.X[d * c.Q], t = c.xt[d];
-        const double u = ((t - x) - e * c.G[d * c.Q]) / hs, v = ((x - t) - e * c.GT[d * c.Q]) / hs;
-        qf = qf + u * u;
-        qb = qb + v * v;
-    }
-    return 0.5 * qf - 0.5 * qb;
-}
 
 __global__ __launch_bounds__(64) void boxmala_step_kernel(BoxchainArgs a) {
     const int64_t q = (int64_t)blockIdx.x * 64 + threadIdx.x;
@@ -42,7 +28,7 @@ __global__ __launch_bounds__(64) void boxmala_step_kernel(BoxchainArgs a) {
             } else if (!finite) {
                 lr = NAN;
             } else {
-                const double lq = boxmala_proposal_ratio(c, hq);      // (before lp is loaded: two VGPRs fewer across the loop)
+                const double lq = boxchain_mala_ratio(c, hq);      // (before lp is loaded: two VGPRs fewer across the loop)
                 lr = (lpt - *c.LP) + lq;
                 acc = a.logu[q] < lr;                 // (a NaN comparison is a rejection)
             }
@@ -55,19 +41,7 @@ __global__ __launch_bounds__(64) void boxmala_step_kernel(BoxchainArgs a) {
         boxchain_hold(c);
         return;
     }
-    // PROPOSE
-    const double hq = a.h[q];
-    const double *zq = a.z + q * c.D;
-    int flag = 0;
-    for (int d = 0; d < c.D; ++d) {
-        const double sd = c.sc[d], l = c.lo[d], u = c.hi[d], x = c.X[d * c.Q];
-        double xp = x;
-        if (!boxchain_fixed(c, d)) xp = (x + ((0.5 * (hq * hq)) * (sd * sd)) * c.G[d * c.Q]) + (hq * sd) * zq[d];
-        if (!(xp >= l && xp <= u)) flag = 1;          // (a NaN is outside)
-        c.xt[d] = xp;
-    }
-    if (flag) boxchain_hold(c);
-    *c.FLAG = flag;
+    boxchain_mala_propose(a, c);
 }
 
 extern "C" size_t dgpamd_boxmala_workspace(int64_t Q, int D) { return boxchain_workspace<3, 1>(Q, D); }

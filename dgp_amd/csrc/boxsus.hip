@@ -13,7 +13,8 @@
 // comparisons alone: it equals its numpy restatement (tests/boxsus_ref.py) bit for bit.
 //
 // dgpamd_boxsus_level: one workgroup per draw, its R particles the parallelism: the level, the survivors, the running product,
-// the ancestors, the gather into x_trial and the survivors' spread per column.
+// the ancestors, the gather into x_trial and the survivors' spread per column.  The workgroup, its reduction, the chunk scan,
+// the gather, the size check and the launch are boxpop.hpp's, as for boxsmc.hip's TEMPER.
 //   Where the numbers live: the scores sit in LDS as order-preserving 64-bit keys (all bits of a negative double flipped, the
 //   sign bit of a non-negative one; a NaN, a dead particle, is key 0, which no number has), 8 R bytes; the survivors' indices
 //   in rank order behind them, 4 R bytes: 96 KB dynamic at the compiled maximum R = DGPAMD_BOXSUS_MAXR = 8192, plus 4.4 KB
@@ -21,15 +22,13 @@
 //   The selection is a most-significant-bit-first radix select: 64 rounds, each an integer count over the thread's keys, a
 //   butterfly inside the wave, one barrier and a sum over at most 16 wave totals.  Integer counts: no summation order to fix.
 //   What bounds it: latency -- 65 + 2 D dependent rounds of a reduction with one barrier each; a draw is one workgroup.
-//   Determinism: the threads of a draw are min(1024, R rounded up to 64), fixed by R; every loop that holds a barrier runs to a
-//   bound that is a constant, R's or D's, and every barrier sits in control flow that the whole workgroup takes (the branches
-//   on done, on the live count and on D are uniform).  The floating sums of sd run lane-strided over the particle index, then
-//   an xor butterfly inside the wave, then the wave totals in index order, as boxsmc_temper's.  Nothing depends on P or on the
-//   other draws of the launch but the running count, an integer.
+//   Determinism: the threads of a draw are fixed by R; every loop that holds a barrier runs to a bound that is a constant,
+//   R's or D's, and every barrier sits in control flow that the whole workgroup takes (the branches on done, on the live count
+//   and on D are uniform).  The floating sums of sd run lane-strided, then through boxpop_reduce, as boxsmc_temper's.
 #include "boxchain.hpp"
+#include "boxpop.hpp"
 
 static_assert(DGPAMD_BOXSUS_OK == BOXCHAIN_OK && DGPAMD_BOXSUS_NAN == BOXCHAIN_NAN, "a particle's status is a chain's");
-#define BOXSUS_THREADS 1024
 #define BOXSUS_ZERO_KEY 0x8000000000000000ULL       // the key of +0.0
 
 struct BoxsusMoveArgs {
@@ -117,35 +116,13 @@ __device__ __forceinline__ double boxsus_unkey(unsigned long long k) {
     return __longlong_as_double((long long)((k >> 63) ? (k ^ BOXSUS_ZERO_KEY) : ~k));
 }
 
-// c <- its sum over the workgroup, in every thread.  buf: one of the two halves of the scratch, used in turn, so that one
-// barrier per call is enough.
-__device__ __forceinline__ int boxsus_count(int c, int *buf, int w, int lane, int NW) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c = c + __shfl_xor(c, off, 64);
-    if (lane == 0) buf[w] = c;
-    __syncthreads();
-    c = buf[0];
-    for (int v = 1; v < NW; ++v) c = c + buf[v];
-    return c;
-}
-// s <- its sum over the workgroup, in every thread: the xor butterfly of the wave (both partners add the same two numbers),
-// then the NW wave totals in index order
-__device__ __forceinline__ double boxsus_sum(double s, double *buf, int w, int lane, int NW) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s = s + __shfl_xor(s, off, 64);
-    if (lane == 0) buf[w] = s;
-    __syncthreads();
-    s = buf[0];
-    for (int v = 1; v < NW; ++v) s = s + buf[v];
-    return s;
-}
-
-__global__ __launch_bounds__(BOXSUS_THREADS) void boxsus_level_kernel(BoxsusLevelArgs a) {
+__global__ __launch_bounds__(BOXPOP_THREADS) void boxsus_level_kernel(BoxsusLevelArgs a) {
     extern __shared__ unsigned long long key[];                   // R keys, then R int32: the survivors in rank order
-    __shared__ int ibuf[2][BOXSUS_THREADS / 64];
-    __shared__ double dbuf[2][BOXSUS_THREADS / 64];
-    __shared__ int tot[BOXSUS_THREADS];
-    const int t = threadIdx.x, NT = blockDim.x, lane = t & 63, w = t >> 6, NW = NT >> 6;
+    __shared__ int ibuf[2][BOXPOP_WAVES];
+    __shared__ double dbuf[2][BOXPOP_WAVES];
+    __shared__ int tot[BOXPOP_THREADS];
+    const BoxpopThread th = boxpop_thread();
+    const int t = th.t, NT = th.NT;
     const int R = a.R, D = a.D;
     int *surv = (int *)(key + R);
     const int64_t p = blockIdx.x, Q = a.P * R, q0 = p * R;
@@ -161,7 +138,7 @@ __global__ __launch_bounds__(BOXSUS_THREADS) void boxsus_level_kernel(BoxsusLeve
             key[i] = k;
             nlive += k != 0ULL;
         }
-        nlive = boxsus_count(nlive, ibuf[turn], w, lane, NW), turn ^= 1;
+        nlive = boxpop_reduce<BoxpopAdd>(th, &ibuf[turn], nlive), turn ^= 1;
         if (nlive == 0) {
             if (t == 0) a.status[p] = DGPAMD_BOXSUS_NAN, a.prob[p] = NAN, a.done[p] = 1, a.nsurv[p] = 0;
             identity = true;
@@ -169,11 +146,7 @@ __global__ __launch_bounds__(BOXSUS_THREADS) void boxsus_level_kernel(BoxsusLeve
     }
     if (identity) {
         // a finished draw, or one without a live particle: the particles stay
-        for (int i = t; i < R; i += NT) anc[i] = i;
-        for (int64_t e = t; e < (int64_t)R * D; e += NT) {
-            const int64_t j = e / D, d = e - j * D;
-            a.x_trial[(q0 + j) * D + d] = a.x[d * Q + q0 + j];
-        }
+        boxpop_stay(th, R, D, Q, q0, a.x, a.x_trial, anc);
         return;
     }
 
@@ -184,34 +157,19 @@ __global__ __launch_bounds__(BOXSUS_THREADS) void boxsus_level_kernel(BoxsusLeve
         const unsigned long long want = (b >> bit) | 1ULL;
         int c = 0;
         for (int i = t; i < R; i += NT) c += (key[i] >> bit) == want;
-        c = boxsus_count(c, ibuf[turn], w, lane, NW), turn ^= 1;
+        c = boxpop_reduce<BoxpopAdd>(th, &ibuf[turn], c), turn ^= 1;
         if (c >= k) b |= 1ULL << bit;
         else k -= c;
     }
     const bool ends = b >= BOXSUS_ZERO_KEY;                      // b >= 0: the level is +0.0, the draw's final stage
     const unsigned long long lk = ends ? BOXSUS_ZERO_KEY : b;
 
-    // the survivors' ranks in index order: a thread counts its chunk, a lane's offset is the sum of the totals of the lanes
-    // before it in its wave, a wave's offset that of the waves before it
-    const int chunk = (R + NT - 1) / NT, i0 = min(t * chunk, R), i1 = min(i0 + chunk, R);
-    int mine = 0;
-    for (int i = i0; i < i1; ++i) mine += key[i] >= lk;           // (a dead key is 0 < lk)
-    tot[t] = mine;
-    __syncthreads();
-    int L = 0;
-    for (int j = 0; j < 63; ++j)
-        if (j < lane) L += tot[w * 64 + j];
-    if (lane == 63) ibuf[turn][w] = L + mine;
-    __syncthreads();
-    int B = 0, nb = 0;
-    for (int v = 0; v < NW; ++v) {
-        const int c = ibuf[turn][v];
-        if (v < w) B += c;
-        nb += c;
-    }
+    // the survivors' ranks in index order, on boxpop_scan's three levels (a dead key is 0 < lk); n_b is its total
+    const BoxpopScan<int> sc = boxpop_scan<true>(th, R, tot, ibuf[turn], [&](int i) { return (int)(key[i] >= lk); });
     turn ^= 1;
-    int rank = B + L;
-    for (int i = i0; i < i1; ++i)
+    const int nb = sc.total;
+    int rank = sc.B + sc.L;
+    for (int i = sc.i0; i < sc.i1; ++i)
         if (key[i] >= lk) surv[rank++] = i;
     __syncthreads();
 
@@ -232,10 +190,7 @@ __global__ __launch_bounds__(BOXSUS_THREADS) void boxsus_level_kernel(BoxsusLeve
 
     // ANCESTORS and GATHER: slot j gets the (j mod n_b)-th survivor
     for (int j = t; j < R; j += NT) anc[j] = surv[j % nb];
-    for (int64_t e = t; e < (int64_t)R * D; e += NT) {
-        const int64_t j = e / D, d = e - j * D;
-        a.x_trial[(q0 + j) * D + d] = a.x[d * Q + q0 + surv[(int)j % nb]];
-    }
+    boxpop_gather(th, R, D, Q, q0, a.x, a.x_trial, [&](int j) { return surv[j % nb]; });
 
     // the survivors' spread per column, two passes; a column whose value is 0 or not finite keeps what it had
     const double n = (double)nb;
@@ -244,29 +199,25 @@ __global__ __launch_bounds__(BOXSUS_THREADS) void boxsus_level_kernel(BoxsusLeve
         double s = 0.0;
         for (int i = t; i < R; i += NT)
             if (key[i] >= lk) s = s + xd[i];
-        const double mean = boxsus_sum(s, dbuf[0], w, lane, NW) / n;
+        const double mean = boxpop_reduce<BoxpopAdd>(th, &dbuf[0], s) / n;
         s = 0.0;
         for (int i = t; i < R; i += NT)
             if (key[i] >= lk) {
                 const double e = xd[i] - mean;
                 s = s + e * e;
             }
-        const double v = sqrt(boxsus_sum(s, dbuf[1], w, lane, NW) / n);
+        const double v = sqrt(boxpop_reduce<BoxpopAdd>(th, &dbuf[1], s) / n);
         if (t == 0 && v > 0.0 && v <= 1.79769313486231570815e308) a.sd[p * D + d] = v;
     }
 }
 
-static bool boxsus_sizes(int64_t P, int64_t R, int D) {
-    return P >= 1 && R >= 1 && R <= DGPAMD_BOXSUS_MAXR && P <= 0x7fffffffLL / R && D >= 1 && D <= DGPAMD_MAXD;
-}
-#define BOXSUS_SIZES "need P >= 1, 1 <= R <= DGPAMD_BOXSUS_MAXR, P R < 2^31 and 1 <= D <= DGPAMD_MAXD"
-
+#define BOXSUS_SIZES BOXPOP_SIZES("DGPAMD_BOXSUS_MAXR")
 extern "C" int dgpamd_boxsus_move(dgpamd_ctx *ctx, int64_t P, int64_t R, int D, int K, int output, double sign, double threshold,
                                   const double *f, const double *par, const double *par_h, const double *level, const double *lam,
                                   const double *sd, const double *z, const double *logu, int first, int last, double *x_trial,
                                   double *x, double *score, int32_t *moved, int32_t *status, int32_t *n_prop, int32_t *n_acc) {
     if (!ctx) return DGPAMD_BAD_ARG;
-    if (!boxsus_sizes(P, R, D)) BAD_ARG(ctx, BOXSUS_SIZES);
+    if (!boxpop_sizes(P, R, D)) BAD_ARG(ctx, BOXSUS_SIZES);
     if (K < 1 || output < 0 || output >= K) BAD_ARG(ctx, "need K >= 1 and 0 <= output < K");
     if (!(sign == 1.0 || sign == -1.0)) BAD_ARG(ctx, "sign must be +1 or -1");
     if (!(threshold >= -1.79769313486231570815e308 && threshold <= 1.79769313486231570815e308))
@@ -293,7 +244,7 @@ extern "C" int dgpamd_boxsus_level(dgpamd_ctx *ctx, int64_t P, int64_t R, int D,
                                    const double *x, double *prob, double *level, int32_t *nsurv, int32_t *done, int32_t *status,
                                    int32_t *anc, double *x_trial, double *sd, int32_t *running) {
     if (!ctx) return DGPAMD_BAD_ARG;
-    if (!boxsus_sizes(P, R, D)) BAD_ARG(ctx, BOXSUS_SIZES);
+    if (!boxpop_sizes(P, R, D)) BAD_ARG(ctx, BOXSUS_SIZES);
     if (n_s < 1 || n_s >= R) BAD_ARG(ctx, "need 1 <= n_s < R");
     if (!(min_prob >= 0.0 && min_prob < 1.0)) BAD_ARG(ctx, "need 0 <= min_prob < 1");
     if (!score || !x || !prob || !level || !nsurv || !done || !status || !anc || !x_trial || !sd || !running)
@@ -302,12 +253,5 @@ extern "C" int dgpamd_boxsus_level(dgpamd_ctx *ctx, int64_t P, int64_t R, int D,
     a.P = P, a.R = (int)R, a.D = D, a.n_s = n_s, a.min_prob = min_prob;
     a.score = score, a.x = x, a.prob = prob, a.level = level, a.sd = sd, a.x_trial = x_trial;
     a.nsurv = nsurv, a.done = done, a.status = status, a.anc = anc, a.running = running;
-    const size_t shm = 12 * (size_t)R;
-    const int rc = set_lds(ctx, (const void *)boxsus_level_kernel, shm);
-    if (rc != DGPAMD_OK) return rc;
-    HIP_TRY(ctx, hipMemsetAsync(running, 0, sizeof(int32_t), ctx->stream));
-    const unsigned threads = (unsigned)(R >= BOXSUS_THREADS ? BOXSUS_THREADS : (R + 63) / 64 * 64);
-    hipLaunchKernelGGL(boxsus_level_kernel, dim3((unsigned)P), dim3(threads), shm, ctx->stream, a);
-    LAUNCH_CHECK(ctx);
-    return DGPAMD_OK;
+    return boxpop_launch(ctx, boxsus_level_kernel, a, P, R, 12 * (size_t)R, running);
 }

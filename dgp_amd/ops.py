@@ -53,6 +53,14 @@ def _f64(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1))
 
 
+def _f64_shapes(message, *pairs):
+    """ValueError(message) unless every (tensor, shape) of pairs is a contiguous float64 tensor of that shape (None: any size)."""
+    for t, shape in pairs:
+        if len(t.shape) != len(shape) or any(n is not None and n != m for n, m in zip(shape, t.shape)) or \
+                t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError(message)
+
+
 class Engine:
     def __init__(self, device=0, stream=None):
         if not torch.cuda.is_available():
@@ -773,9 +781,8 @@ class Engine:
         D, K = x_trial.shape[-1], f.shape[-1]
         lead = x_trial.shape[:-1]
         Q = int(np.prod(lead))
-        for t, shape in ((x_trial, (*lead, D)), (f, (*lead, K)), (J, (*lead, K, D))):
-            if t.shape != shape or t.dtype != torch.float64 or not t.is_contiguous():
-                raise ValueError('boxmin: x_trial, f, J must be contiguous float64 tensors (..., D), (..., K), (..., K, D)')
+        _f64_shapes('boxmin: x_trial, f, J must be contiguous float64 tensors (..., D), (..., K), (..., K, D)',
+                    (x_trial, (*lead, D)), (f, (*lead, K)), (J, (*lead, K, D)))
         sizes = dict(x=Q * D, fun=Q, status=Q, n_iter=Q, n_eval=Q, running=1, lo=D, hi=D)
         if state['work'].numel() < self.boxmin_workspace(Q, D, state['history']) or state['lo_h'].size != D or \
                 state['hi_h'].size != D or any(state[name].numel() != count for name, count in sizes.items()):
@@ -798,14 +805,18 @@ class Engine:
             raise ValueError('%s: need Q >= 1 and 1 <= D <= %d' % (what, _lib.MAXD))
         return nbytes
 
-    def _chain_state(self, what, Q, D, w, ybar, lo, hi, scale, prior_prec, prior_mean, n_slots):
+    def _chain_par(self, what, D, w, ybar, lo, hi, scale, prior_prec, prior_mean, n_slots=0):
+        """(K, par_h) of the chains and of boxsmc's move: w (K), ybar (K), prior_prec (D, None: 0), prior_mean, scale, lo, hi."""
         w, ybar, lo, hi, scale = _f64(w), _f64(ybar), _f64(lo), _f64(hi), _f64(scale)
         pv = np.zeros(D) if prior_prec is None else _f64(prior_prec)
         pm = np.zeros(D) if prior_mean is None else _f64(prior_mean)
         K = w.size
         if K < 1 or ybar.size != K or any(a.size != D for a in (lo, hi, scale, pv, pm)) or n_slots < 0:
             raise ValueError('%s: w and ybar must hold K >= 1 entries; lo, hi, scale and the prior D = %d' % (what, D))
-        par = np.concatenate([w, ybar, pv, pm, scale, lo, hi])
+        return K, np.concatenate([w, ybar, pv, pm, scale, lo, hi])
+
+    def _chain_state(self, what, Q, D, w, ybar, lo, hi, scale, prior_prec, prior_mean, n_slots):
+        K, par = self._chain_par(what, D, w, ybar, lo, hi, scale, prior_prec, prior_mean, n_slots)
         return dict(work=torch.empty(self._chain_workspace(what, Q, D), dtype=torch.uint8, device=self.device), K=K,
                     n_slots=int(n_slots), par_h=par, par=self.tensor(par), h=self.empty(Q), logr=self.empty(Q),
                     status=self.zeros(Q, dtype=torch.int32), n_prop=self.zeros(Q, dtype=torch.int32),
@@ -830,10 +841,8 @@ class Engine:
         D, K = x_trial.shape[-1], f.shape[-1]
         lead = x_trial.shape[:-1]
         Q = int(np.prod(lead))
-        for t, shape in ((x_trial, (*lead, D)), (f, (*lead, K)), (J, (*lead, K, D)), (z, (*lead, D)), (logu, tuple(lead))):
-            if t.shape != shape or t.dtype != torch.float64 or not t.is_contiguous():
-                raise ValueError('%s: x_trial, f, J, z, logu must be contiguous float64 tensors (..., D), (..., K), '
-                                 '(..., K, D), (..., D), (...)' % what)
+        _f64_shapes('%s: x_trial, f, J, z, logu must be contiguous float64 tensors (..., D), (..., K), (..., K, D), (..., D), (...)' % what,
+                    (x_trial, (*lead, D)), (f, (*lead, K)), (J, (*lead, K, D)), (z, (*lead, D)), (logu, tuple(lead)))
         sizes = dict(h=Q, logr=Q, status=Q, n_prop=Q, n_acc=Q, xs=max(state['n_slots'], 1) * D * Q, lps=max(state['n_slots'], 1) * Q,
                      par=2 * K + 5 * D)
         if state['work'].numel() < self._chain_workspace(what, Q, D) or state['K'] != K or state['par_h'].size != 2 * K + 5 * D or \
@@ -884,6 +893,17 @@ class Engine:
         read.  slot >= 0: store the sample."""
         return self._chain_step('boxhmc', state, f, J, x_trial, z, logu, h0, hmin, hmax, up, down, adapt, first, slot, bool(last))
 
+    # populations over a box (csrc/boxpop.hpp: boxsmc.hip, boxsus.hip)
+    def _pop_sizes(self, what, made_for, state, x_trial, more, counts):
+        """(P, R, D) of x_trial after the checks that boxsmc's and boxsus's calls share: x_trial's form, (P, R, D), then state
+        against more(P, R, D), a check of the family's own, and counts(P, R, D, Q), a table name -> element count."""
+        _f64_shapes('%s: x_trial must be a contiguous float64 tensor (P, R, D)' % what, (x_trial, (None, None, None)))
+        P, R, D = x_trial.shape
+        if state['P'] != P or state['R'] != R or not more(P, R, D) or \
+                any(state[name].numel() != n or not state[name].is_contiguous() for name, n in counts(P, R, D, P * R).items()):
+            raise ValueError('%s: the state was made for another %s' % (what, made_for))
+        return P, R, D
+
     # tempered SMC (csrc/boxsmc.hip)
     BOXSMC = dict(ok=0, nan=1, max_stages=2)
     BOXSMC_MAXR = 8192
@@ -902,13 +922,7 @@ class Engine:
         boxmala_state; per particle x (D, Q) particle fastest, ll, lprior, h (filled with h0), logr (Q) and status, n_prop,
         n_acc (Q) int32, Q = P R; per draw beta (zeros), dbeta, log_evidence (zeros), stage_ess (P), draw_status (P) int32,
         anc (P, R) int32; running (1,) int32."""
-        w, ybar, lo, hi, scale = _f64(w), _f64(ybar), _f64(lo), _f64(hi), _f64(scale)
-        pv = np.zeros(D) if prior_prec is None else _f64(prior_prec)
-        pm = np.zeros(D) if prior_mean is None else _f64(prior_mean)
-        K, Q = w.size, int(P) * int(R)
-        if K < 1 or ybar.size != K or any(a.size != D for a in (lo, hi, scale, pv, pm)):
-            raise ValueError('boxsmc: w and ybar must hold K >= 1 entries; lo, hi, scale and the prior D = %d' % D)
-        par = np.concatenate([w, ybar, pv, pm, scale, lo, hi])
+        (K, par), Q = self._chain_par('boxsmc', D, w, ybar, lo, hi, scale, prior_prec, prior_mean), int(P) * int(R)
         return dict(work=torch.empty(self.boxsmc_workspace(P, R, D), dtype=torch.uint8, device=self.device), K=K, P=int(P),
                     R=int(R), par_h=par, par=self.tensor(par), x=self.zeros(D, Q), ll=self.zeros(Q), lprior=self.zeros(Q),
                     h=torch.full((Q,), float(h0), dtype=torch.float64, device=self.device), logr=self.zeros(Q),
@@ -918,16 +932,11 @@ class Engine:
                     anc=self.zeros(P, R, dtype=torch.int32), running=self.zeros(1, dtype=torch.int32))
 
     def _boxsmc_sizes(self, state, x_trial):
-        if x_trial.dim() != 3 or x_trial.dtype != torch.float64 or not x_trial.is_contiguous():
-            raise ValueError('boxsmc: x_trial must be a contiguous float64 tensor (P, R, D)')
-        P, R, D = x_trial.shape
-        Q = P * R
-        sizes = dict(x=Q * D, ll=Q, lprior=Q, h=Q, logr=Q, status=Q, n_prop=Q, n_acc=Q, beta=P, dbeta=P, log_evidence=P,
-                     stage_ess=P, draw_status=P, anc=Q, running=1, par=2 * state['K'] + 5 * D)
-        if state['P'] != P or state['R'] != R or state['work'].numel() < self.boxsmc_workspace(P, R, D) or \
-                state['par_h'].size != 2 * state['K'] + 5 * D or any(state[name].numel() != n for name, n in sizes.items()):
-            raise ValueError('boxsmc: the state was made for another P, R, D or K')
-        return P, R, D
+        return self._pop_sizes(
+            'boxsmc', 'P, R, D or K', state, x_trial,
+            lambda P, R, D: state['work'].numel() >= self.boxsmc_workspace(P, R, D) and state['par_h'].size == 2 * state['K'] + 5 * D,
+            lambda P, R, D, Q: dict(x=Q * D, ll=Q, lprior=Q, h=Q, logr=Q, status=Q, n_prop=Q, n_acc=Q, beta=P, dbeta=P, log_evidence=P,
+                                    stage_ess=P, draw_status=P, anc=Q, running=1, par=2 * state['K'] + 5 * D))
 
     def boxsmc_move(self, state, f, J, x_trial, z, logu, hmin=1e-10, hmax=1e2, up=1.0, down=1.0, adapt=False, first=False,
                     last=False):
@@ -938,10 +947,8 @@ class Engine:
         overwritten with the next points to evaluate."""
         P, R, D = self._boxsmc_sizes(state, x_trial)
         K = state['K']
-        for t, shape in ((f, (P, R, K)), (J, (P, R, K, D)), (z, (P, R, D)), (logu, (P, R))):
-            if t.shape != shape or t.dtype != torch.float64 or not t.is_contiguous():
-                raise ValueError('boxsmc: f, J, z, logu must be contiguous float64 tensors (P, R, K), (P, R, K, D), (P, R, D), '
-                                 '(P, R) beside x_trial (P, R, D)')
+        _f64_shapes('boxsmc: f, J, z, logu must be contiguous float64 tensors (P, R, K), (P, R, K, D), (P, R, D), (P, R) beside '
+                    'x_trial (P, R, D)', (f, (P, R, K)), (J, (P, R, K, D)), (z, (P, R, D)), (logu, (P, R)))
         self._chk(self._enter() or lib.dgpamd_boxsmc_move(
             self.h, P, R, D, K, _dp(f), _dp(J), _dp(state['par']), _hp(state['par_h']), _dp(state['beta']), _dp(z), _dp(logu),
             float(hmin), float(hmax), float(up), float(down), 1 if adapt else 0, 1 if first else 0, 1 if last else 0,
@@ -954,8 +961,7 @@ class Engine:
         float64 device tensor, the step of beta that keeps ESS >= ess_frac R_live; updates beta, dbeta, log_evidence,
         stage_ess, draw_status, anc and running in place and gathers the resampled particles into x_trial (P, R, D)."""
         P, R, D = self._boxsmc_sizes(state, x_trial)
-        if u.shape != (P,) or u.dtype != torch.float64 or not u.is_contiguous():
-            raise ValueError('boxsmc: u must be a contiguous float64 tensor (P,)')
+        _f64_shapes('boxsmc: u must be a contiguous float64 tensor (P,)', (u, (P,)))
         self._chk(self._enter() or lib.dgpamd_boxsmc_temper(
             self.h, P, R, D, float(ess_frac), _dp(state['ll']), _dp(state['x']), _dp(u), _dp(state['beta']), _dp(state['dbeta']),
             _dp(state['log_evidence']), _dp(state['stage_ess']), _dp(state['draw_status']), _dp(state['anc']), _dp(x_trial),
@@ -991,16 +997,10 @@ class Engine:
                     anc=self.zeros(P, R, **i32), running=self.zeros(1, **i32))
 
     def _boxsus_sizes(self, state, x_trial):
-        if x_trial.dim() != 3 or x_trial.dtype != torch.float64 or not x_trial.is_contiguous():
-            raise ValueError('boxsus: x_trial must be a contiguous float64 tensor (P, R, D)')
-        P, R, D = x_trial.shape
-        Q = P * R
-        sizes = dict(x=Q * D, score=Q, moved=Q, status=Q, n_prop=Q, n_acc=Q, prob=P, level=P, lam=P, sd=P * D, nsurv=P, done=P,
-                     draw_status=P, anc=Q, running=1, par=4 * D)
-        if (state['P'], state['R'], state['D']) != (P, R, D) or state['par_h'].size != 4 * D or \
-                any(state[name].numel() != n or not state[name].is_contiguous() for name, n in sizes.items()):
-            raise ValueError('boxsus: the state was made for another P, R or D')
-        return P, R, D
+        return self._pop_sizes(
+            'boxsus', 'P, R or D', state, x_trial, lambda P, R, D: state['D'] == D and state['par_h'].size == 4 * D,
+            lambda P, R, D, Q: dict(x=Q * D, score=Q, moved=Q, status=Q, n_prop=Q, n_acc=Q, prob=P, level=P, lam=P, sd=P * D, nsurv=P,
+                                    done=P, draw_status=P, anc=Q, running=1, par=4 * D))
 
     def boxsus_move(self, state, f, x_trial, z, logu, threshold, output=0, sign=1.0, first=False, last=False):
         """One call of every particle's modified Metropolis state machine (dgpamd_boxsus_move).  state: boxsus_state's; f
@@ -1012,10 +1012,8 @@ class Engine:
         if f.dim() != 3:
             raise ValueError('boxsus: f must be (P, R, K)')
         K = f.shape[-1]
-        for t, shape in ((f, (P, R, K)), (z, (P, R, D)), (logu, (P, R, D))):
-            if t.shape != shape or t.dtype != torch.float64 or not t.is_contiguous():
-                raise ValueError('boxsus: f, z, logu must be contiguous float64 tensors (P, R, K), (P, R, D), (P, R, D) beside '
-                                 'x_trial (P, R, D)')
+        _f64_shapes('boxsus: f, z, logu must be contiguous float64 tensors (P, R, K), (P, R, D), (P, R, D) beside x_trial (P, R, D)',
+                    (f, (P, R, K)), (z, (P, R, D)), (logu, (P, R, D)))
         self._chk(self._enter() or lib.dgpamd_boxsus_move(
             self.h, P, R, D, K, int(output), float(sign), float(threshold), _dp(f), _dp(state['par']), _hp(state['par_h']),
             _dp(state['level']), _dp(state['lam']), _dp(state['sd']), _dp(z), _dp(logu), 1 if first else 0, 1 if last else 0,

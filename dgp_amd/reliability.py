@@ -16,26 +16,19 @@ import numpy as np
 import torch
 
 from . import optimize
-from .calibrate import STREAM_LOGU, STREAM_NORMAL, STREAM_PRIOR, check_prior, check_rng, host_uniforms, prior_draws, stage_round, upload
 from .ops import Engine
+from .population import DeviceStageStreams, HostStreams, check_prior, check_rng, draw_status, particles, prior_particles, run_stages
 
 STATUS = Engine.BOXSUS
 MAX_PARTICLES = Engine.BOXSUS_MAXR
 LAM_MIN, LAM_MAX = 1e-3, 1e2       # the clamp of a draw's step, in units of its survivors' spread
 
 
-class SusStreams:
+class SusStreams(HostStreams):
     """The random numbers of a subset-simulation run, children of np.random.SeedSequence(seed) by spawn key: (0, p) the prior
     uniforms of path p, (R, Dx); (1, p, t) and (2, p, t) the normal and the uniform draws of path p in stage t, (R, rounds,
     Dx) each, slot first.  A generator fills its array in index order, so slot r's numbers do not depend on R, and path p has
     generators of its own, so its numbers do not depend on P.  (rounds is one number per run: n_moves + 1.)"""
-
-    def __init__(self, seed, P, R, Dx):
-        self.entropy = np.random.SeedSequence(seed).entropy
-        self.P, self.R, self.Dx, self.t = P, R, Dx, 0
-
-    def _rng(self, *key):
-        return np.random.default_rng(np.random.SeedSequence(self.entropy, spawn_key=key))
 
     def prior_uniforms(self):
         """(P, R, Dx) uniforms in [0, 1)."""
@@ -50,24 +43,12 @@ class SusStreams:
         return np.ascontiguousarray(z.transpose(2, 0, 1, 3)), np.ascontiguousarray(logu.transpose(2, 0, 1, 3))
 
 
-class DeviceSusStreams:
-    """SusStreams' twin for rng='device' (Engine.philox_fill under the key of the seed, DESIGN I.23): the prior uniforms are
-    stream 0 at round 0; stage t reads z from stream 1 and log u from stream 2, Dx elements each, at c2 = (t << 32) | i for
-    move i.  Particle (p, r)'s numbers depend on nothing but the seed, p, r, t and i."""
+class DeviceSusStreams(DeviceStageStreams):
+    """SusStreams' twin for rng='device': population.DeviceStageStreams with Dx log u per particle and round and no resampling
+    uniform; stage(rounds) gives (z (rounds, P, R, Dx), log u (rounds, P, R, Dx))."""
 
     def __init__(self, e, seed, P, R, Dx):
-        self.e, self.key, self.P, self.R, self.Dx, self.t = e, Engine.philox_key(seed), P, R, Dx, 0
-
-    def prior_uniforms(self):
-        """(P, R, Dx) uniforms in [0, 1), on the device."""
-        return self.e.philox_fill('uniform', self.key, STREAM_PRIOR, 0, 1, self.P, self.R, self.Dx)[0]
-
-    def stage(self, rounds):
-        """(z (rounds, P, R, Dx), log u (rounds, P, R, Dx)) of the next stage, on the device."""
-        t, self.t = self.t, self.t + 1
-        c2, fill = stage_round(t), self.e.philox_fill
-        return (fill('normal', self.key, STREAM_NORMAL, c2, rounds, self.P, self.R, self.Dx),
-                fill('log_uniform', self.key, STREAM_LOGU, c2, rounds, self.P, self.R, self.Dx))
+        super().__init__(e, seed, P, R, Dx, logu_elements=Dx, resample=False)
 
 
 def n_survivors(level_prob, R):
@@ -156,8 +137,8 @@ def failure_probability(e, P, K, Dx, values, threshold, bounds, output=0, below=
                         n_moves=4, max_stages=50, min_prob=1e-12, seed=None, step=1.0, prior=None, target_accept=0.44,
                         rng='numpy'):
     """The driver behind PathFunctions.failure_probability and GpPaths.failure_probability.  values(xt (P, R, Dx)) -> (P, R, K):
-    the walk at per-path rows, values only.  A stage is dgpamd_boxsus_level, then n_moves + 1 walk evaluations with
-    dgpamd_boxsus_move behind each: the start of the stage at the cloned particles, then n_moves decisions.  A draw's step
+    the walk at per-path rows, values only.  A stage of population.run_stages is dgpamd_boxsus_level, then n_moves + 1 walk
+    evaluations with dgpamd_boxsus_move behind each: the start at the cloned particles, then n_moves decisions.  A draw's step
     lam is fixed within a stage and follows the stage's acceptance rate afterwards, on the device; the width itself is the
     survivors' spread, which the level step refreshes.  Only the count of unfinished draws visits the host, once per stage.
     rng='device': every random number is made on the device (DeviceSusStreams); the prior uniforms visit the host once, for
@@ -170,33 +151,27 @@ def failure_probability(e, P, K, Dx, values, threshold, bounds, output=0, below=
                                                            min_prob, step, target_accept)
     sign = -1.0 if below else 1.0
     streams = DeviceSusStreams(e, seed, P, R, Dx) if device_rng else SusStreams(seed, P, R, Dx)
-    x0 = np.ascontiguousarray(prior_draws(host_uniforms(streams.prior_uniforms()), lo, hi, pv, pm))
+    x0 = prior_particles(streams, lo, hi, pv, pm)
     xt = e.tensor(x0)
     state = e.boxsus_state(P, R, Dx, lo, hi, pv, pm, step)
     state['sd'].copy_(e.tensor(prior_spread(x0)))
-    # the scores of the prior particles: a stage's start that ends at once (z and log u are not read)
-    zero = e.zeros(P, R, Dx)
-    e.boxsus_move(state, values(xt), xt, zero, zero, threshold, output, sign, first=True, last=True)
-    active, levels, nsurv, accept, lams = [], [], [], [], []
-    for stage in range(max_stages):
-        zb, ub = (upload(e, a) for a in streams.stage(n_moves + 1))
+    active, levels, nsurv, lams = [], [], [], []
+
+    move = lambda z, logu, first, last: e.boxsus_move(state, values(xt), xt, z, logu, threshold, output, sign, first=first, last=last)
+
+    def level():
         active.append(state['done'] == 0)
         e.boxsus_level(state, xt, n_s, min_prob)
         levels.append(state['level'].clone()), nsurv.append(state['nsurv'].clone()), lams.append(state['lam'].clone())
-        for i in range(n_moves + 1):
-            e.boxsus_move(state, values(xt), xt, zb[i], ub[i], threshold, output, sign, first=i == 0, last=i == n_moves)
-        # the draw's step for the next stage, from this stage's acceptance over all its particles
-        rate = state['n_acc'].view(P, R).sum(1).double() / state['n_prop'].view(P, R).sum(1).clamp(min=1).double()
-        accept.append(rate)
-        state['lam'].mul_(torch.exp(rate - target_accept)).clamp_(LAM_MIN, LAM_MAX)
-        if int(state['running'].item()) == 0:
-            break
+    # the scores of the prior particles: a stage's start that ends at once (z and log u are not read)
+    move(e.zeros(P, R, Dx), e.zeros(P, R, Dx), first=True, last=True)
+    # the draw's step for the next stage follows this stage's acceptance over all its particles
+    accept = run_stages(e, streams, state, n_moves, max_stages, target_accept, level, move,
+                        lambda gain: state['lam'].mul_(gain).clamp_(LAM_MIN, LAM_MAX))
     host = {k: state[k].cpu().numpy() for k in ('x', 'score', 'prob', 'done', 'draw_status')}
-    status = host['draw_status'].copy()
-    status[(status == STATUS['ok']) & (host['done'] == 0)] = STATUS['max_stages']
     T = len(levels)
     on = torch.stack(active, 1).cpu().numpy()
     stack = lambda ts: np.where(on, torch.stack(ts, 1).double().cpu().numpy(), np.nan)
-    return FailureProbability(host['prob'], stack(levels), stack(nsurv) / R, stack(accept), stack(lams),
-                              np.ascontiguousarray(host['x'].reshape(Dx, P, R).transpose(1, 2, 0)), host['score'].reshape(P, R),
-                              status, T, T * (n_moves + 1), rng)
+    return FailureProbability(host['prob'], stack(levels), stack(nsurv) / R, stack(accept), stack(lams), particles(host['x'], P, R),
+                              host['score'].reshape(P, R), draw_status(STATUS, host['draw_status'], host['done'] == 0), T,
+                              T * (n_moves + 1), rng)
