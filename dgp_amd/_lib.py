@@ -142,6 +142,7 @@ SIGNATURES = {
     'dgpamd_boxsmc_move': (_i, [_p, _l, _l, _i, _i, _p, _p, _p, _p, _p, _p, _p, _d, _d, _d, _d, _i, _i, _i, _p, _p, _p, _p, _p, _p,
                                 _p, _p, _p, _p]),
     'dgpamd_boxsmc_temper': (_i, [_p, _l, _l, _i, _d, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    'dgpamd_boxsites_fold': (_i, [_p, _l, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     'dgpamd_boxsus_move': (_i, [_p, _l, _l, _i, _i, _i, _d, _d, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     'dgpamd_boxsus_level': (_i, [_p, _l, _l, _i, _i, _d, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     'dgpamd_philox_fill': (_i, [_p, _i, _u, _u, _u, _u, _l, _l, _l, _i, _p]),

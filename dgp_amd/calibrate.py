@@ -197,6 +197,8 @@ class PathPosterior:
     rhat, ess (P, Dx): the split R-hat over a draw's R chains and the effective sample size of a draw's posterior mean.
     Row p is path p of the draws' container (s * sample_size + j for an emulator)."""
 
+    columns = controls = None     # (with controls: the calibration columns of the walk's input (Dx,) and the sites' settings (T, Dc))
+
     def __init__(self, x, logp, accept_rate, step, status, x0, rounds, method='mala', n_leapfrog=1, evaluations=None, rng='numpy'):
         self.x, self.logp, self.accept_rate, self.step, self.status, self.x0, self.rounds = x, logp, accept_rate, step, status, x0, rounds
         self.method, self.n_leapfrog, self.evaluations = method, n_leapfrog, rounds if evaluations is None else evaluations
@@ -236,11 +238,13 @@ class PathPosterior:
 
 
 def calibrate(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, n_chains=4, n_samples=500, warmup=500, thin=1,
-              n_candidates=2048, x0=None, seed=None, qmc=False, step=0.1, scale=None, prior=None, rng='numpy', target_accept=None,
-              method='mala', n_leapfrog=8, jitter=True):
+              n_candidates=2048, x0=None, seed=None, qmc=False, step=0.1, scale=None, *, problem=None, prior=None, rng='numpy',
+              target_accept=None, method='mala', n_leapfrog=8, jitter=True):
     """The driver behind PathFunctions.calibrate and GpPaths.calibrate; values, value_and_jac and width as in
     optimize.minimize.  rng='device': the chains' normals and uniforms are made on the device (DeviceStreams) instead of by
-    numpy generators and an upload; the candidate design and HMC's trajectory lengths stay numpy's."""
+    numpy generators and an upload; the candidate design and HMC's trajectory lengths stay numpy's.  problem: a prepared
+    fieldcal.FieldProblem (DESIGN I.24) -- its K, Dx, closures, width and pseudo-observation stand for the arguments' and for
+    observation(y, obs_sd, K), and the result carries its columns and controls."""
     if method not in TARGET_ACCEPT:
         raise ValueError("calibrate: method must be 'mala' or 'hmc'")
     device_rng = check_rng(rng, 'calibrate')
@@ -249,9 +253,11 @@ def calibrate(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, n_ch
         raise ValueError('calibrate: need n_leapfrog >= 1')
     if target_accept is None:
         target_accept = TARGET_ACCEPT[method]
+    if problem is not None:
+        K, Dx, values, value_and_jac, width = problem.K, problem.Dx, problem.values, problem.value_and_jac, problem.width
     lo, hi = optimize.check_bounds(bounds, Dx, 'calibrate')
     Dx = len(lo)
-    ybar, w = observation(y, obs_sd, K)
+    ybar, w = observation(y, obs_sd, K) if problem is None else (problem.ybar, problem.w)
     pv, pm = check_prior(prior, Dx)
     R, S, warmup, thin = check_counts(n_chains, n_samples, warmup, thin)
     scale = check_step('calibrate', lo, hi, scale, step, target_accept)
@@ -308,10 +314,13 @@ def calibrate(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, n_ch
                 before = state['n_prop'].clone(), state['n_acc'].clone()
     host = {k: state[k].cpu().numpy() for k in ('xs', 'lps', 'h', 'status', 'n_prop', 'n_acc')}
     n_prop, n_acc = host['n_prop'] - before[0].cpu().numpy(), host['n_acc'] - before[1].cpu().numpy()
-    return PathPosterior(np.ascontiguousarray(host['xs'].reshape(S, Dx, P, R).transpose(2, 3, 0, 1)),
-                         np.ascontiguousarray(host['lps'].reshape(S, P, R).transpose(1, 2, 0)),
-                         (n_acc / np.maximum(n_prop, 1)).reshape(P, R), host['h'].reshape(P, R), host['status'].reshape(P, R),
-                         np.array(x0), rounds, method, n_leapfrog if hmc else 1, rounds, rng)
+    res = PathPosterior(np.ascontiguousarray(host['xs'].reshape(S, Dx, P, R).transpose(2, 3, 0, 1)),
+                        np.ascontiguousarray(host['lps'].reshape(S, P, R).transpose(1, 2, 0)),
+                        (n_acc / np.maximum(n_prop, 1)).reshape(P, R), host['h'].reshape(P, R), host['status'].reshape(P, R),
+                        np.array(x0), rounds, method, n_leapfrog if hmc else 1, rounds, rng)
+    if problem is not None:
+        res.columns, res.controls = problem.columns, problem.controls
+    return res
 
 
 # ------------------------------------------------------------------------- tempered SMC with per-draw evidence (DESIGN I.21)
@@ -398,6 +407,8 @@ class ParticlePosterior:
     many of them carry it: when it is small, the weighted answer rests on few draws and more of them are needed; pooled()
     with equal weights stays the modular (cut) posterior."""
 
+    columns = controls = None     # (as PathPosterior's)
+
     def __init__(self, x, loglik, logp, log_evidence, log_norm, betas, stage_ess, accept_rate, step, status, n_stages, evaluations,
                  rng='numpy'):
         self.rng = rng
@@ -461,16 +472,19 @@ class ParticlePosterior:
 
 
 def calibrate_smc(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, n_particles=1024, n_moves=4, ess_frac=0.5,
-                  max_stages=100, seed=None, step=0.1, scale=None, prior=None, target_accept=0.574, rng='numpy'):
+                  max_stages=100, seed=None, step=0.1, scale=None, prior=None, target_accept=0.574, *, problem=None, rng='numpy'):
     """The driver behind PathFunctions.calibrate_smc and GpPaths.calibrate_smc: adaptive likelihood tempering (Del Moral,
     Doucet and Jasra 2006) on population.run_stages.  A stage is dgpamd_boxsmc_temper, then n_moves + 1 walk evaluations with
     dgpamd_boxsmc_move behind each: the start of the stage at the resampled particles, then n_moves decisions.  Only the count
     of draws below beta = 1 visits the host, once per stage.  rng='device': every random number is made on the device
-    (DeviceSmcStreams); the prior uniforms visit the host once, for prior_draws."""
+    (DeviceSmcStreams); the prior uniforms visit the host once, for prior_draws.  problem: as in calibrate; its log_norm is the
+    result's."""
     device_rng = check_rng(rng, 'calibrate_smc')
+    if problem is not None:
+        K, Dx, value_and_jac = problem.K, problem.Dx, problem.value_and_jac
     lo, hi = optimize.check_bounds(bounds, Dx, 'calibrate_smc')
     Dx = len(lo)
-    ybar, w = observation(y, obs_sd, K)
+    ybar, w = observation(y, obs_sd, K) if problem is None else (problem.ybar, problem.w)
     pv, pm = check_prior(prior, Dx)
     R, n_moves, max_stages = int(n_particles), int(n_moves), int(max_stages)
     if not 1 <= R <= MAX_PARTICLES:
@@ -499,6 +513,10 @@ def calibrate_smc(e, P, K, Dx, values, value_and_jac, width, y, obs_sd, bounds, 
     T = len(betas)
     stack = lambda ts: np.ascontiguousarray(torch.stack(ts, 1).cpu().numpy())
     ll = host['ll'].reshape(P, R)
-    return ParticlePosterior(particles(host['x'], P, R), ll, ll + host['lprior'].reshape(P, R), host['log_evidence'],
-                             log_norm(y, obs_sd, K), stack(betas), stack(stage_ess), stack(accept), host['h'].reshape(P, R),
-                             draw_status(SMC_STATUS, host['draw_status'], host['beta'] < 1.0), T, T * (n_moves + 1), rng)
+    res = ParticlePosterior(particles(host['x'], P, R), ll, ll + host['lprior'].reshape(P, R), host['log_evidence'],
+                            log_norm(y, obs_sd, K) if problem is None else problem.log_norm, stack(betas), stack(stage_ess),
+                            stack(accept), host['h'].reshape(P, R),
+                            draw_status(SMC_STATUS, host['draw_status'], host['beta'] < 1.0), T, T * (n_moves + 1), rng)
+    if problem is not None:
+        res.columns, res.controls = problem.columns, problem.controls
+    return res

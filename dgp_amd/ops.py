@@ -968,6 +968,41 @@ class Engine:
             _dp(state['running'])))
         return x_trial
 
+    # the whitening fold of field calibration (csrc/boxsites.hip)
+    BOXSITES_MAXT = 256
+
+    def boxsites_plan(self, W, cols):
+        """What the folds of one run share (boxsites_fold's W): W (K, T, T), a host array or a device tensor, the whitening
+        matrix W[k, t, s] of every output, transposed once into the kernel's layout Wt[k, s, t]; cols, Dt distinct ints, on the
+        device and on the host."""
+        Wd = W if torch.is_tensor(W) else self.tensor(np.asarray(W, dtype=np.float64))
+        if Wd.dim() != 3 or Wd.shape[1] != Wd.shape[2] or Wd.dtype != torch.float64:
+            raise ValueError('boxsites: W must be float64 (K, T, T)')
+        cols_h = np.ascontiguousarray(np.asarray(cols, dtype=np.int32).reshape(-1))
+        return dict(K=int(Wd.shape[0]), T=int(Wd.shape[1]), Wt=Wd.transpose(1, 2).contiguous(), cols_h=cols_h,
+                    cols=torch.as_tensor(cols_h, device=self.device) if cols_h.size else None)
+
+    def boxsites_fold(self, f, J, W, cols=None, out=None):
+        """(ft (Q, T K), Jt (Q, T K, Dt)) = dgpamd_boxsites_fold: ft[q, t K + k] = sum_{s <= t} W[k, t, s] f[q, s, k] and
+        Jt[q, t K + k, d] = sum_{s <= t} W[k, t, s] J[q, s, k, cols[d]], in the order of s, exact zeros of W skipped.  f
+        (Q, T, K), J (Q, T, K, Dx): contiguous float64 device tensors; J None: the values alone, Jt None.  W: boxsites_plan's
+        dict (cols is then its own), or (K, T, T) with cols beside it -- a plan made for this call.  out: (ft, Jt) to write
+        into.  The layouts are those boxmala_step, boxhmc_step and boxsmc_move take as f and J."""
+        plan = W if isinstance(W, dict) else self.boxsites_plan(W, [] if cols is None else cols)
+        _f64_shapes('boxsites: f must be a contiguous float64 tensor (Q, T, K)', (f, (None, plan['T'], plan['K'])))
+        Q, T, K = f.shape
+        Dt = 0 if J is None else int(plan['cols_h'].size)
+        if J is not None:
+            _f64_shapes('boxsites: J must be a contiguous float64 tensor (Q, T, K, Dx)', (J, (Q, T, K, None)))
+        Dx = 1 if J is None else int(J.shape[3])
+        ft, Jt = (self.empty(Q, T * K), None if J is None else self.empty(Q, T * K, Dt)) if out is None else out
+        _f64_shapes('boxsites: out must be contiguous float64 tensors (Q, T K), (Q, T K, Dt)',
+                    *([(ft, (Q, T * K))] + ([] if J is None else [(Jt, (Q, T * K, Dt))])))
+        self._chk(self._enter() or lib.dgpamd_boxsites_fold(
+            self.h, Q, T, K, Dx, Dt, _dp(plan['cols']) if Dt else None, _hp(plan['cols_h']) if Dt else None, _dp(plan['Wt']),
+            _dp(f), _dp(J), _dp(ft), _dp(Jt) if Dt else None))
+        return ft, Jt
+
     # subset simulation (csrc/boxsus.hip)
     BOXSUS = dict(ok=0, nan=1, max_stages=2, below_min=3)
     BOXSUS_MAXR = 8192

@@ -350,8 +350,8 @@ class PathFunctions:
                                  seed, qmc, maxiter, gtol, ftol, history, check_every, max_eval)
 
     def calibrate(self, y, obs_sd, bounds, n_chains=4, n_samples=500, warmup=500, thin=1, n_candidates=2048, x0=None, seed=None,
-                  qmc=False, step=0.1, scale=None, prior=None, rng='numpy', target_accept=None, method='mala', n_leapfrog=8,
-                  jitter=True):
+                  qmc=False, step=0.1, scale=None, *, controls=None, control_columns=None, obs_cov=None, prior=None, rng='numpy',
+                  target_accept=None, method='mala', n_leapfrog=8, jitter=True):
         """The posterior of the input x given an observation of the outputs, for every draw, on the device (calibrate,
         DESIGN I.19): a calibrate.PathPosterior with x (P, R, S, Dx), logp (P, R, S), P = N * sample_size draws, R =
         n_chains chains, S = n_samples samples.  Draw p's chains sample p(x | y, f_p) proportional to prior(x) N(y; f_p(x),
@@ -373,14 +373,23 @@ class PathFunctions:
         particle or chain (p, r)'s own whatever runs beside it); result.rng records it.  result.rhat and result.ess (P, Dx) are the
         split R-hat and the effective sample size per draw; result.summary() the pooled mean and interval.  Raises
         ValueError for an emulator with a likelihood node or a Categorical top and for bad bounds, y, obs_sd or counts;
-        NotImplementedError for draws made by sample_functions_vecchia."""
-        from . import calibrate
-        return calibrate.calibrate(*self._lane_problem(bounds, 'calibrate'), y, obs_sd, bounds, n_chains, n_samples, warmup, thin,
-                                   n_candidates, x0, seed, qmc, step, scale, prior, rng, target_accept, method, n_leapfrog,
-                                   jitter)
+        NotImplementedError for draws made by sample_functions_vecchia.
+        Field data (DESIGN I.24): controls (T, Dc), T <= fieldcal.MAX_SITES, are the known settings of T measurements and
+        control_columns their Dc columns of the input; the other columns, in increasing order, are the calibration parameters
+        theta, shared by all sites, and everything that described x describes theta: bounds (Dtheta, 2), prior, scale, x0 and
+        result.x have Dtheta columns; result.columns names them, result.controls keeps the settings.  y is (T, K), row t
+        measured at controls[t] (repeated rows are replicates), NaN unobserved; obs_sd a positive scalar, (K,) or (T, K);
+        obs_cov None, (T, T) or (K, T, T): the covariance across the sites of output k's error (a model discrepancy) on top of
+        the independent obs_sd^2, the outputs independent of each other.  A covariance that does not factor raises
+        ValueError, and so does obs_cov without controls."""
+        from . import calibrate, fieldcal
+        lane, problem = fieldcal.prepare(self._lane_problem, 'calibrate', y, obs_sd, bounds, controls, control_columns, obs_cov)
+        return calibrate.calibrate(*lane, y, obs_sd, bounds, n_chains, n_samples, warmup, thin, n_candidates, x0, seed, qmc, step,
+                                   scale, problem=problem, prior=prior, rng=rng, target_accept=target_accept, method=method,
+                                   n_leapfrog=n_leapfrog, jitter=jitter)
 
     def calibrate_smc(self, y, obs_sd, bounds, n_particles=1024, n_moves=4, ess_frac=0.5, max_stages=100, seed=None, step=0.1,
-                      scale=None, prior=None, target_accept=0.574, rng='numpy'):
+                      scale=None, prior=None, target_accept=0.574, *, controls=None, control_columns=None, obs_cov=None, rng='numpy'):
         """calibrate's posteriors by tempered sequential Monte Carlo, with every draw's evidence, on the device (DESIGN
         I.21): a calibrate.ParticlePosterior with x (P, n_particles, Dx) and log_evidence (P,), the estimate of log of the
         integral of prior(x) exp(ll_p(x)) over the box under the normalised prior.  y, obs_sd, bounds, prior, scale, step
@@ -394,10 +403,14 @@ class PathFunctions:
         np.random.SeedSequence(seed); draw p's do not depend on the draws beside it.  rng='device' makes the normal and uniform numbers on the device instead
         (Philox4x64-10 streams keyed by the seed, DESIGN I.23: other numbers than rng='numpy' gives, as reproducible, and
         particle or chain (p, r)'s own whatever runs beside it); result.rng records it.  result.draw_weights() weighs the draws
-        by their evidence; result.pooled() stays the modular posterior.  Raises as calibrate does."""
-        from . import calibrate
-        return calibrate.calibrate_smc(*self._lane_problem(bounds, 'calibrate_smc'), y, obs_sd, bounds, n_particles, n_moves,
-                                       ess_frac, max_stages, seed, step, scale, prior, target_accept, rng)
+        by their evidence; result.pooled() stays the modular posterior.  Raises as calibrate does.  controls,
+        control_columns and obs_cov: field data as in calibrate; log_norm is then -sum_k (T_k / 2 log 2 pi + sum log diag L_k),
+        L_k the factor of output k's covariance over its observed sites, and log_evidence + log_norm still estimates
+        log p(y | f_p)."""
+        from . import calibrate, fieldcal
+        lane, problem = fieldcal.prepare(self._lane_problem, 'calibrate_smc', y, obs_sd, bounds, controls, control_columns, obs_cov)
+        return calibrate.calibrate_smc(*lane, y, obs_sd, bounds, n_particles, n_moves, ess_frac, max_stages, seed, step, scale,
+                                       prior, target_accept, problem=problem, rng=rng)
 
     def failure_probability(self, threshold, bounds, output=0, below=False, n_particles=1024, level_prob=0.1, n_moves=4,
                             max_stages=50, min_prob=1e-12, seed=None, step=1.0, prior=None, target_accept=0.44,
@@ -609,24 +622,28 @@ class GpPaths:
                                  seed, qmc, maxiter, gtol, ftol, history, check_every, max_eval)
 
     def calibrate(self, y, obs_sd, bounds, n_chains=4, n_samples=500, warmup=500, thin=1, n_candidates=2048, x0=None, seed=None,
-                  qmc=False, step=0.1, scale=None, prior=None, rng='numpy', target_accept=None, method='mala', n_leapfrog=8,
-                  jitter=True):
+                  qmc=False, step=0.1, scale=None, *, controls=None, control_columns=None, obs_cov=None, prior=None, rng='numpy',
+                  target_accept=None, method='mala', n_leapfrog=8, jitter=True):
         """The posterior of the input x given an observation y (a number, (1,) or (T, 1) replicates) of the GP's output, for
         every draw: PathFunctions.calibrate for the sample_size draws of a gp model (P = sample_size, one output), the
-        modular posterior when pooled; a column of x that the GP does not read is sampled from its prior."""
-        from . import calibrate
-        return calibrate.calibrate(*self._lane_problem(bounds, 'calibrate'), np.reshape(y, (-1, 1)) if np.ndim(y) < 2 else y,
-                                   obs_sd, bounds, n_chains, n_samples, warmup, thin, n_candidates, x0, seed, qmc, step, scale,
-                                   prior, rng, target_accept, method, n_leapfrog, jitter)
+        modular posterior when pooled; a column of x that the GP does not read is sampled from its prior.  controls,
+        control_columns and obs_cov: field data as in PathFunctions.calibrate, y (T,) or (T, 1)."""
+        from . import calibrate, fieldcal
+        y = np.reshape(y, (-1, 1)) if np.ndim(y) < 2 else y
+        lane, problem = fieldcal.prepare(self._lane_problem, 'calibrate', y, obs_sd, bounds, controls, control_columns, obs_cov)
+        return calibrate.calibrate(*lane, y, obs_sd, bounds, n_chains, n_samples, warmup, thin, n_candidates, x0, seed, qmc, step,
+                                   scale, problem=problem, prior=prior, rng=rng, target_accept=target_accept, method=method,
+                                   n_leapfrog=n_leapfrog, jitter=jitter)
 
     def calibrate_smc(self, y, obs_sd, bounds, n_particles=1024, n_moves=4, ess_frac=0.5, max_stages=100, seed=None, step=0.1,
-                      scale=None, prior=None, target_accept=0.574, rng='numpy'):
+                      scale=None, prior=None, target_accept=0.574, *, controls=None, control_columns=None, obs_cov=None, rng='numpy'):
         """PathFunctions.calibrate_smc for the sample_size draws of a gp model (P = sample_size, one output; y as in
         calibrate): tempered SMC particles of every draw's posterior and its evidence."""
-        from . import calibrate
-        return calibrate.calibrate_smc(*self._lane_problem(bounds, 'calibrate_smc'), np.reshape(y, (-1, 1)) if np.ndim(y) < 2 else y,
-                                       obs_sd, bounds, n_particles, n_moves, ess_frac, max_stages, seed, step, scale, prior,
-                                       target_accept, rng)
+        from . import calibrate, fieldcal
+        y = np.reshape(y, (-1, 1)) if np.ndim(y) < 2 else y
+        lane, problem = fieldcal.prepare(self._lane_problem, 'calibrate_smc', y, obs_sd, bounds, controls, control_columns, obs_cov)
+        return calibrate.calibrate_smc(*lane, y, obs_sd, bounds, n_particles, n_moves, ess_frac, max_stages, seed, step, scale,
+                                       prior, target_accept, problem=problem, rng=rng)
 
     def failure_probability(self, threshold, bounds, output=0, below=False, n_particles=1024, level_prob=0.1, n_moves=4,
                             max_stages=50, min_prob=1e-12, seed=None, step=1.0, prior=None, target_accept=0.44,

@@ -894,6 +894,27 @@ int dgpamd_boxsmc_temper(dgpamd_ctx *ctx, int64_t P, int64_t R, int D, double es
                          const double *u, double *beta, double *dbeta, double *log_evidence, double *stage_ess, int32_t *status,
                          int32_t *anc, double *x_trial, int32_t *running);
 
+/* ---- the whitening fold of field calibration: known control inputs, correlated errors (DESIGN I.24) ----
+ * Q chains, each evaluated at T sites, 1 <= T <= DGPAMD_BOXSITES_MAXT: f (Q, T, K) and J (Q, T, K, Dx) are the walk's values and
+ * Jacobian at the chain's T rows, W_k (T, T) the lower-triangular whitening matrix of output k (the inverse of the Cholesky
+ * factor of the error covariance across sites; a site that was not observed has a zero row and a zero column), cols the Dt
+ * columns of the walk's input that are calibrated.  The fold writes the pseudo-outputs j = t K + k that the chain steps and
+ * dgpamd_boxsmc_move take as their K = T K outputs and D = Dt columns, in their layouts:
+ *   ft[q, t K + k]    = sum_{s = 0 .. t} W[k, t, s] f[q, s, k]                  ft (Q, T K)
+ *   Jt[q, t K + k, d] = sum_{s = 0 .. t} W[k, t, s] J[q, s, k, cols[d]]         Jt (Q, T K, Dt)
+ * Each sum starts from 0.0 and runs in the order of s; products are not fused into sums (the file is built without contraction);
+ * a term whose W[k, t, s] is exactly 0 is skipped, not multiplied, so a NaN in f or J at a site that was not observed reaches
+ * nothing, and that site's own outputs are 0.  tests/boxsites_ref.py restates it.  W is passed transposed, Wt[k, s, t] =
+ * W[k, t, s], (K, T, T) contiguous: the thread that owns row t reads addresses consecutive in t.  Entries with s > t are not read.
+ * cols: Dt int32 on the device; cols_h: their host copy, which the checks read.  Dt = 0: the values alone -- cols, cols_h, J and
+ * Jt are not read and may be null.  One workgroup per (chain, output); 16 KiB of LDS; no atomics, no workspace: an element
+ * depends on its own chain's inputs alone, not on Q or on what shares the launch.
+ * DGPAMD_BAD_ARG before any launch: Q < 1 or Q >= 2^31, T outside 1 .. DGPAMD_BOXSITES_MAXT, K outside 1 .. 65535, Dx < 1,
+ * Dt < 0, Dt > DGPAMD_MAXD or Dt > Dx, Q T K Dx over 2^60, a column outside 0 .. Dx - 1 or named twice, a null pointer. */
+#define DGPAMD_BOXSITES_MAXT 256
+int dgpamd_boxsites_fold(dgpamd_ctx *ctx, int64_t Q, int T, int K, int Dx, int Dt, const int32_t *cols, const int32_t *cols_h,
+                         const double *Wt, const double *f, const double *J, double *ft, double *Jt);
+
 /* ---- subset simulation over a box: the probability of a rare event of a function draw (DESIGN I.22) ----
  * P draws with R particles each, 1 <= R <= DGPAMD_BOXSUS_MAXR (a level needs R >= 2), lane q = p R + r, P R < 2^31, 1 <= D <= 64.
  *   score = sign (f[q, output] - threshold) + 0.0 (the + 0.0 turns -0 into +0), sign = +1 or -1; the event is F = {score >= 0}.
